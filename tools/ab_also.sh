@@ -3,7 +3,7 @@
 line=$1; reps=$2; shift; shift
 for r in $(seq 1 $reps); do
   for lib in "$@"; do
-    FDH_LIB=$lib python bench.py --no-cpu-baseline --also-select $line --steps 5 --warmup 2 2>/dev/null | python -c "
+    FDH_LIB=$lib python bench.py --full --no-cpu-baseline --also-select $line --steps 5 --warmup 2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 for a in d.get('also', []):

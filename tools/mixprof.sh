@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/mixprof_$TAG
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/p -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --also-select mix > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/p -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --also-select mix > $OUT/log.txt 2>&1
 python3 - <<PY
 import csv, glob
 for f in glob.glob("$OUT/p/**/*kernel_stats.csv", recursive=True):

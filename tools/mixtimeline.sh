@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/mixtl_$TAG
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT/p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --also-select mix > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/p -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --also-select mix > $OUT/log.txt 2>&1
 python3 - <<PY > gpurun_out/mixtl_$TAG.txt
 import csv, glob
 rows = []
