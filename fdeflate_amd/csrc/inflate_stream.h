@@ -122,19 +122,21 @@ __device__ __forceinline__ FlushState flush_ring(WaveIo* iop, uint8_t* out_al, u
                                                            uint32_t adler_b, bool final, int lane) {
     WaveIo& io = *iop;
     wave_sync();
-    uint32_t q_lo = flushed + gmis;
-    uint32_t q_hi = opos + gmis;
-    if (!final) q_hi &= ~15u;
+    // (q-space positions are 64-bit: a slot may end within a block of 2^32, where `it + kWave * 16` in 32 bits came
+    //  round to the slot's first bytes and the loop never ended -- tests/test_gpu_limits.py decodes 2^32 - 3 bytes)
+    uint64_t q_lo = (uint64_t)flushed + gmis;
+    uint64_t q_hi = (uint64_t)opos + gmis;
+    if (!final) q_hi &= ~15ull;
     if (q_hi <= q_lo) return FlushState{flushed, adler_a, adler_b};
-    for (uint32_t it = q_lo & ~15u; it < q_hi; it += kWave * 16) {
-        uint32_t lq = it + lane * 16;  // this lane's line, q-space
-        uint32_t blk_hi = min(q_hi, it + kWave * 16);
-        uint32_t blk_lo = max(q_lo, it);
+    for (uint64_t it = q_lo & ~15ull; it < q_hi; it += kWave * 16) {
+        uint64_t lq = it + lane * 16;  // this lane's line, q-space
+        uint64_t blk_hi = min(q_hi, it + kWave * 16);
+        uint64_t blk_lo = max(q_lo, it);
         uint32_t s = 0, t = 0;
         if (lq < blk_hi && lq + 16 > blk_lo) {
-            uint32_t lo = (blk_lo > lq) ? blk_lo - lq : 0;
-            uint32_t hi = (blk_hi < lq + 16) ? blk_hi - lq : 16;
-            uint32_t W = blk_hi - lq;  // weight of byte j is W - j
+            uint32_t lo = (blk_lo > lq) ? (uint32_t)(blk_lo - lq) : 0;
+            uint32_t hi = (blk_hi < lq + 16) ? (uint32_t)(blk_hi - lq) : 16;
+            uint32_t W = (uint32_t)(blk_hi - lq);  // weight of byte j is W - j
             if (lo == 0 && hi == 16) {
                 uint4 v = *reinterpret_cast<const uint4*>(&io.out_ring[lq & kOutMask]);
                 *reinterpret_cast<uint4*>(out_al + lq) = v;
@@ -155,11 +157,11 @@ __device__ __forceinline__ FlushState flush_ring(WaveIo* iop, uint8_t* out_al, u
         }
         uint32_t S = wave_sum_u32(s);
         uint32_t Tt = wave_sum_u32(t);
-        uint32_t Lb = blk_hi - blk_lo;
+        uint32_t Lb = (uint32_t)(blk_hi - blk_lo);
         adler_b = (uint32_t)(((uint64_t)adler_b + (uint64_t)Lb * adler_a + Tt) % kAdlerMod);
         adler_a = (adler_a + S) % kAdlerMod;
     }
-    flushed = q_hi - gmis;
+    flushed = (uint32_t)(q_hi - gmis);
     wave_sync();
     return FlushState{flushed, adler_a, adler_b};
 }

@@ -223,7 +223,9 @@ int fdh_png_filter_batch(const uint8_t *pix, const uint64_t *pix_off, const uint
 /* Filtering fused into the ultra-fast encoder: pixel rows in (`pix`, rows_i x row_bytes), one filter
  * type per row in `types`, out the zlib stream compress_to_vec_ultra_fast(filtered image) -- what an
  * IDAT holds.  The filtered bytes exist only in registers (no intermediate buffer).  Slots of at
- * least fdh_ultrafast_bound(rows_i * (row_bytes + 1)) bytes; out_len[i] = 0 where png_status[i] != 0. */
+ * least fdh_ultrafast_bound(rows_i * (row_bytes + 1)) bytes; out_len[i] = 0 where png_status[i] != 0.
+ * A slot that is too small for the stream is no PNG error: png_status[i] = 0 and out_len[i] = 0xFFFFFFFF, as
+ * with fdh_deflate_ultrafast_batch (nothing valid in the slot, nothing written outside it). */
 int fdh_png_filter_deflate_ultrafast_batch(const uint8_t *pix, const uint64_t *pix_off,
                                            const uint8_t *types, const uint64_t *types_off,
                                            uint8_t *out, const uint64_t *out_off, uint32_t *out_len,

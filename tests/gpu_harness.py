@@ -47,6 +47,124 @@ def gpu_inflate(blobs, caps, flags=0, guard=5, fill=0xA5):
     return st, ln, ad, outs, guards_ok
 
 
+_CHUNK = 1 << 28   # device comparisons of big slots go 256 MiB at a time (the temporaries stay small)
+
+
+def _all_fill(t, fill):
+    """Device reduction: every byte of the uint8 tensor `t` is `fill`."""
+    for c in range(0, t.numel(), _CHUNK):
+        if not bool((t[c:c + _CHUNK] == fill).all()):
+            return False
+    return True
+
+
+def _equal_on_device(t, expected):
+    """torch.equal of the device tensor `t` with host bytes `expected` (same length), uploaded in pieces."""
+    import torch
+    e = np.frombuffer(expected, dtype=np.uint8)
+    assert e.size == t.numel()
+    for c in range(0, e.size, _CHUNK):
+        if not torch.equal(t[c:c + _CHUNK], torch.from_numpy(e[c:c + _CHUNK].copy()).cuda()):
+            return False
+    return True
+
+
+def pad_to(blob, n, seed=1):
+    """`blob` brought to exactly n bytes by junk behind its Adler-32 trailer (which a decoder ignores)."""
+    assert len(blob) <= n, (len(blob), n)
+    junk = np.random.default_rng(seed).integers(1, 256, n - len(blob), dtype=np.uint8).tobytes()
+    return bytes(blob) + junk
+
+
+class DeviceSlots:
+    """The output slots of one gpu_inflate_big call, still on the device."""
+
+    def __init__(self, d_out, out_off, fill):
+        self.d_out, self.out_off, self.fill = d_out, out_off, fill
+
+    def head_equals(self, i, data):
+        """The first len(data) bytes of slot i are `data` (bytes / uint8 array; uploaded, torch.equal)."""
+        o0, o1 = int(self.out_off[2 * i]), int(self.out_off[2 * i + 1])
+        assert len(data) <= o1 - o0
+        return _equal_on_device(self.d_out[o0:o0 + len(data)], data)
+
+    def untouched(self, i, start=0):
+        """Slot i still holds the fill byte from byte `start` to its end (device reduction)."""
+        o0, o1 = int(self.out_off[2 * i]), int(self.out_off[2 * i + 1])
+        return _all_fill(self.d_out[min(o0 + start, o1):o1], self.fill)
+
+
+def gpu_inflate_big(blobs, caps, flags=0, guard=5, fill=0xA5):
+    """gpu_inflate for slots too large to bring back: the same odd guard slots, but every comparison stays on the
+    device -- expected bytes are uploaded per stream and compared with torch.equal (DeviceSlots.head_equals), untouched
+    parts of a slot and the guard slots are checked against `fill` by a device reduction.  Only status / length /
+    Adler-32 come to the host.  -> (status, out_len, adler, slots[DeviceSlots], guards_ok)"""
+    import torch
+    import fdeflate_amd as fd
+
+    n = len(blobs)
+    in_off = np.zeros(2 * n + 1, dtype=np.int64)
+    in_off[1::2] = [len(b) for b in blobs]
+    in_off = np.cumsum(in_off)
+    d_in = torch.zeros(max(int(in_off[-1]), 1), dtype=torch.uint8, device="cuda")
+    for i, b in enumerate(blobs):
+        a = np.frombuffer(b, dtype=np.uint8)
+        for c in range(0, a.size, _CHUNK):
+            o = int(in_off[2 * i]) + c
+            piece = a[c:c + _CHUNK]
+            d_in[o:o + piece.size] = torch.from_numpy(piece.copy()).cuda()
+    out_off = np.zeros(2 * n + 1, dtype=np.int64)
+    out_off[1::2] = caps
+    out_off[2::2] = guard
+    out_off = np.cumsum(out_off)
+    d_out = torch.full((max(int(out_off[-1]), 1),), fill, dtype=torch.uint8, device="cuda")
+    out_len, status, adler = fd.inflate_batch(d_in, torch.from_numpy(in_off).cuda(), d_out, torch.from_numpy(out_off).cuda(),
+                                              flags=flags)
+    torch.cuda.synchronize()
+    st = status.cpu().numpy().view(np.uint32)[0::2]
+    ln = out_len.cpu().numpy().view(np.uint32)[0::2]
+    ad = adler.cpu().numpy().view(np.uint32)[0::2]
+    guards_ok = all(_all_fill(d_out[int(out_off[2 * i + 1]):int(out_off[2 * i + 2])], fill) for i in range(n))
+    return st, ln, ad, DeviceSlots(d_out, out_off, fill), guards_ok
+
+
+def encoder_guard_faults(h, out_off, ln, empty, fill):
+    """The guard slots (odd entries) of an encoder batch: each holds the stream of an empty input, `empty`, and behind it
+    bytes that nobody may write -- still `fill`.  -> list of faults (empty: all is well)"""
+    faults = []
+    for i in range(1, len(out_off) - 1, 2):
+        g = h[int(out_off[i]):int(out_off[i + 1])]
+        if int(ln[i]) != len(empty) or g[:len(empty)].tobytes() != empty:
+            faults.append((i // 2, "guard slot's empty stream damaged", int(ln[i]), g[:len(empty)].tobytes().hex()))
+        if not np.all(g[len(empty):] == fill):
+            faults.append((i // 2, "guard bytes changed", g[len(empty):].tobytes().hex()))
+    return faults
+
+
+def gpu_encode_slots(encode, raws, caps, empty, guard=3, fill=0x5A):
+    """Runs a batched encoder into slots of caps[i] bytes, packed back to back at odd alignments.  Behind each comes a
+    guard slot: an empty input, whose stream `empty` fits, and `guard` bytes more that must keep the fill byte.
+    encode(d_in, d_in_off, d_out, d_out_off) -> out_len tensor.
+    -> (out_len[n] uint32, slots[list of uint8 arrays: the whole slot], guard_faults[empty list: all is well])"""
+    import torch
+
+    n = len(raws)
+    all_raw, all_caps = [], []
+    for r, c in zip(raws, caps):
+        all_raw += [r, b""]
+        all_caps += [c, len(empty) + guard]
+    buf, in_off = streams.pack_exact(all_raw)
+    out_off = np.zeros(2 * n + 1, dtype=np.int64)
+    out_off[1:] = np.cumsum(np.asarray(all_caps, dtype=np.int64))
+    d_out = torch.full((max(int(out_off[-1]), 1),), fill, dtype=torch.uint8, device="cuda")
+    out_len = encode(_t(buf), _t(in_off.astype(np.int64)), d_out, _t(out_off))
+    torch.cuda.synchronize()
+    h = d_out.cpu().numpy()
+    ln = out_len.cpu().numpy().view(np.uint32)
+    slots = [h[int(out_off[2 * i]):int(out_off[2 * i + 1])] for i in range(n)]
+    return ln[0::2], slots, encoder_guard_faults(h, out_off, ln, empty, fill)
+
+
 def oracle_inflate(blobs, caps, ignore_adler32=False):
     sts, lens, ads, outs = [], [], [], []
     for b, c in zip(blobs, caps):
