@@ -8,7 +8,8 @@ from .api import (Decompressor, DecompressionError, OutputTooLarge, STATUS_NAMES
                   FLAG_SERIAL_ONLY, FLAG_GENERAL_ONLY, FLAG_NO_RECHECK, compress_to_vec_ultra_fast, debug_build_tables,
                   decompress_to_vec, decompress_to_vec_bounded, deflate_ultrafast_batch,
                   inflate_batch, inflate_batch_resumable, ultrafast_bound, compress_to_vec_stored, deflate_stored_batch,
-                  stored_size, compress_to_vec, compress_to_vec_rle, compress_bound, deflate_general_batch,
+                  stored_size, compress_to_vec, compress_to_vec_rle, compress_to_vec_with_level, compress_bound,
+                  deflate_general_batch, MODE_LEVEL2, MODE_LEVEL3,
                   MODE_LEVEL1, MODE_RLE, inflate_batch_multi, init_devices, shutdown_devices, multi_uses_rccl,
                   png_unfilter_batch, png_filter_batch, inflate_png_batch, png_filter_deflate_ultrafast_batch)
 
@@ -17,6 +18,7 @@ __all__ = [
     "FLAG_SERIAL_ONLY", "FLAG_GENERAL_ONLY", "FLAG_NO_RECHECK", "compress_to_vec_ultra_fast", "debug_build_tables", "decompress_to_vec",
     "decompress_to_vec_bounded", "deflate_ultrafast_batch", "inflate_batch", "inflate_batch_resumable", "ultrafast_bound",
     "compress_to_vec_stored", "deflate_stored_batch", "stored_size", "compress_to_vec", "compress_to_vec_rle",
-    "compress_bound", "deflate_general_batch", "MODE_LEVEL1", "MODE_RLE", "inflate_batch_multi", "init_devices",
+    "compress_bound", "deflate_general_batch", "MODE_LEVEL1", "MODE_RLE", "MODE_LEVEL2", "MODE_LEVEL3",
+    "compress_to_vec_with_level", "inflate_batch_multi", "init_devices",
     "shutdown_devices", "multi_uses_rccl", "png_unfilter_batch", "png_filter_batch", "inflate_png_batch", "png_filter_deflate_ultrafast_batch",
 ]

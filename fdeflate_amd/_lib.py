@@ -81,6 +81,8 @@ def lib():
     L.fdh_compress_to_vec.argtypes = [vp, sz, pp, C.POINTER(sz)]
     L.fdh_compress_to_vec_rle.restype = C.c_int
     L.fdh_compress_to_vec_rle.argtypes = [vp, sz, pp, C.POINTER(sz)]
+    L.fdh_compress_to_vec_with_level.restype = C.c_int
+    L.fdh_compress_to_vec_with_level.argtypes = [vp, sz, u32, pp, C.POINTER(sz)]
     L.fdh_decompressor_new.restype = vp
     L.fdh_decompressor_new.argtypes = []
     L.fdh_decompressor_free.argtypes = [vp]
@@ -109,6 +111,7 @@ EXPORTED_SYMBOLS = [
     "fdh_decompressor_new", "fdh_decompressor_free", "fdh_decompressor_ignore_adler32",
     "fdh_decompressor_is_done", "fdh_decompressor_read", "fdh_decompressor_attempts", "fdh_decompressor_decoded_bytes", "fdh_decompressor_device_bytes",
     "fdh_compress_bound", "fdh_deflate_general_batch", "fdh_compress_to_vec", "fdh_compress_to_vec_rle",
+    "fdh_compress_to_vec_with_level",
     "fdh_png_unfilter_batch", "fdh_png_filter_batch", "fdh_inflate_png_batch", "fdh_png_filter_deflate_ultrafast_batch",
     "fdh_init", "fdh_shutdown", "fdh_multi_device_count", "fdh_multi_uses_rccl", "fdh_inflate_batch_multi",
 ]

@@ -200,17 +200,36 @@ def compress_to_vec_rle(data):
     return _take(out, n.value)
 
 
+LEVELS_PROVIDED = (0, 1, 2, 3)
+
+
+def compress_to_vec_with_level(data, level):
+    """fdeflate::compress_to_vec_with_level (src/compress/mod.rs:299): level 0 stored, levels 1-3 the
+    greedy parser with the hash table (1) or the hash chains (2, 3).  Levels 4-9 (the lazy parser)
+    are not provided: ValueError."""
+    if isinstance(level, bool) or not isinstance(level, int) or level not in LEVELS_PROVIDED:
+        raise ValueError("compression level %r is not provided (levels 0, 1, 2 and 3 are)" % (level,))
+    L = _lib.lib()
+    data = bytes(data)
+    out = C.c_void_p()
+    n = C.c_size_t()
+    _lib.check(L.fdh_compress_to_vec_with_level(data, len(data), level, C.byref(out), C.byref(n)))
+    return _take(out, n.value)
+
+
 def compress_bound(n):
     return int(_lib.lib().fdh_compress_bound(int(n)))
 
 
 MODE_LEVEL1 = 1
 MODE_RLE = 2
+MODE_LEVEL2 = 3
+MODE_LEVEL3 = 4
 
 
 def deflate_general_batch(raw, in_off, out, out_off, mode, out_len=None):
-    """Level-1 / RLE encode of n buffers (fdh_deflate_general_batch): a parser kernel (one stream per
-    lane) that records the back-references, then a block-writer kernel (one stream per wavefront).
+    """Level-1 / -2 / -3 / RLE encode of n buffers (fdh_deflate_general_batch): a parser kernel (one stream
+    per lane) that records the back-references, then a block-writer kernel (one stream per wavefront).
     Returns when the work has finished."""
     import torch
     n = in_off.numel() - 1

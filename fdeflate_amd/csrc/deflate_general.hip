@@ -1,10 +1,11 @@
-// deflate_general.hip -- the general encoder at level 1 (`compress_to_vec`) and in RLE mode
-// (`compress_to_vec_rle`), bit-exact with the reference, in two kernels.
+// deflate_general.hip -- the general encoder at levels 1 (`compress_to_vec`), 2 and 3
+// (`compress_to_vec_with_level`) and in RLE mode (`compress_to_vec_rle`), bit-exact with the
+// reference, in two kernels.
 //
 // Reference: Compressor src/compress/mod.rs:47-217 (level 1 = GreedyParser + HashTableMatchFinder
-// :76, RLE = RleParser :107-123), parsers src/compress/parse/{mod,greedy,rle}.rs, match finders
-// src/compress/matchfinder/{mod,hashtable}.rs, block writer src/compress/bitstream.rs:41-325,
-// bit writer src/compress/bitwriter.rs.
+// :76, levels 2 / 3 = GreedyParser + HashChainMatchFinder :77-79, RLE = RleParser :107-123), parsers
+// src/compress/parse/{mod,greedy,rle}.rs, match finders src/compress/matchfinder/{mod,hashtable,
+// hashchain}.rs, block writer src/compress/bitstream.rs:41-325, bit writer src/compress/bitwriter.rs.
 //
 // 1. deflate_parse_kernel -- ONE STREAM PER LANE.  LZ77 parsing with a hash table is order-dependent
 //    inside a stream (every decision depends on what the table held, i.e. on all earlier decisions),
@@ -54,6 +55,7 @@ __device__ __forceinline__ void g_length_symbol(uint32_t length, uint32_t& sym, 
 }
 
 constexpr uint32_t kGHashSize = 1u << 16;
+constexpr uint32_t kGWindow = 32768;  // WINDOW_SIZE: entries of a hash chain's `links` ring
 constexpr uint32_t kGBlockSymbols = 16384;
 
 // What the parser hands to the block writer.  Back-references never overlap and are at least 4
@@ -100,8 +102,19 @@ struct GMatch {
 
 // ============================ kernel 1: the parser, one stream per lane ============================
 
-struct GParser {
-    uint32_t* hash;     // this lane's table (level 1)
+// CH: 0 = level 1 (HashTableMatchFinder) and RLE, 2 / 3 = the level whose HashChainMatchFinder the
+// parser uses (compress/mod.rs:77-79).  Everything CH selects is a compile-time constant, so the
+// level-1 / RLE instantiations are the code they were before the chain finder existed.
+template <int CH>
+struct GParserT {
+    static constexpr bool kChain = CH != 0;
+    static constexpr uint32_t kShift = kChain ? 6 : 5;  // skip_ahead_shift (compress/mod.rs:76-79, :114)
+    // HashChainMatchFinder::new(min_match, search_depth, nice_length) (compress/mod.rs:78, :79)
+    static constexpr uint32_t kMinMatch = CH == 2 ? 8 : 6, kDepth = 16, kNice = CH == 2 ? 64 : 32;
+    static constexpr uint64_t kMask = ~0ull >> (8 * (8 - kMinMatch));  // hashchain.rs:34
+
+    uint32_t* hash;     // this lane's table (level 1) / head table (levels 2, 3)
+    uint32_t* links;    // this lane's ring of kGWindow chain links (levels 2, 3)
     GMatchRec* mrec;    // this stream's slices
     GBlockRec* brec;
     uint32_t nmatch, nblock;
@@ -178,24 +191,29 @@ struct GParser {
         return k;
     }
 
-    // match_length::<true> (matchfinder/mod.rs:51-111)
-    __device__ static void match_length8(uint64_t value, const uint8_t* data, uint64_t len, uint64_t anchor, uint64_t ip,
-                                         uint64_t prev_index, uint32_t& out_len, uint64_t& out_start) {
-        if (value != g_load64(data + prev_index)) {
+    // match_length::<MIN8> (matchfinder/mod.rs:51-111): 8 equal bytes admit a candidate, or 4 with
+    // the length starting at the equal bytes of the first eight (4..8)
+    template <bool MIN8>
+    __device__ static void match_length(uint64_t value, const uint8_t* data, uint64_t len, uint64_t anchor, uint64_t ip,
+                                        uint64_t prev_index, uint32_t& out_len, uint64_t& out_start) {
+        const uint64_t x = value ^ g_load64(data + prev_index);
+        if (MIN8 ? x != 0 : (uint32_t)x != 0) {
             out_len = 0;
             out_start = ip;
             return;
         }
-        uint64_t length = 8;
+        uint64_t length = MIN8 || x == 0 ? 8 : (uint64_t)__builtin_ctzll(x) >> 3;
         {   // backwards while length < 258 && ip > anchor && prev_index > 0 && the bytes in front agree
-            const uint32_t n = back_equal(data, ip, prev_index, (uint32_t)min(min((uint64_t)250, ip - anchor), prev_index));
+            const uint32_t n = back_equal(data, ip, prev_index, (uint32_t)min(min((uint64_t)258 - length, ip - anchor), prev_index));
             length += n;
             ip -= n;
             prev_index -= n;
         }
         uint64_t slice = len - ip - length;
         if (slice > 258 - length) slice = 258 - length;
-        length += fwd_equal(data + ip + length, data + prev_index + length, (uint32_t)slice, ip + length + slice + 8 <= len);
+        // (x != 0: the byte at ip + length is the one that differed, wherever the walk backwards put ip)
+        if (MIN8 || x == 0)
+            length += fwd_equal(data + ip + length, data + prev_index + length, (uint32_t)slice, ip + length + slice + 8 <= len);
         out_len = (uint32_t)length;
         out_start = ip;
     }
@@ -282,8 +300,56 @@ struct GParser {
         return r;
     }
 
+    // HashChainMatchFinder::get_and_insert (hashchain.rs:40-107), as written there:
+    // - the link of the new position is stored BEFORE the walk, so a candidate at exactly ip - 32768
+    //   (which passes min_offset) reads the slot just replaced and the walk goes round to the head's
+    //   old value until the depth is used up; that decides which match wins and is kept;
+    // - `ip + length == len` takes the caller's ip with a length that includes the bytes gained
+    //   backwards, and len is the length of the pass's slice;
+    // - `l > best_len` is strict: of equal candidates the nearer one wins.
+    // A link slot is only ever read for an offset that came out of the head table or a link, is
+    // >= min_offset >= 1, and therefore was stored by get_and_insert / insert of THIS stream -- which
+    // wrote links[offset % 32768] in the same step.  So no slot is read before this stream has written
+    // it and the ring is not cleared between streams (by argument; tests/level_model.py counts such
+    // reads and finds none).  The head table is cleared: it starts as zeros (hashchain.rs:28).
+    __device__ GMatch chain_get_and_insert(const uint8_t* data, uint64_t len, uint32_t base_index, uint64_t anchor, uint64_t value) {
+        const uint32_t h = g_hash(value & kMask);
+        const uint32_t offset = hash[h];
+        const uint32_t new_offset = (uint32_t)ip + base_index;
+        hash[h] = new_offset;
+        links[new_offset % kGWindow] = offset;
+        return chain_walk(data, len, base_index, anchor, value, offset);
+    }
+    // "Visit previous matches" (hashchain.rs:68-106) from the head's old value `offset`; the position at
+    // `ip` is in the head table and its link stored.  The link of a candidate is fetched together with
+    // the candidate's bytes, not after they have been compared (the walk stores nothing, so the value is
+    // the same; it is not used when the walk ends at this candidate).
+    __device__ GMatch chain_walk(const uint8_t* data, uint64_t len, uint32_t base_index, uint64_t anchor, uint64_t value, uint32_t offset) {
+        const uint32_t sub = (uint32_t)ip > 32768 ? (uint32_t)ip - 32768 : 0;
+        const uint32_t min_offset = max(base_index + sub, 1u);
+        uint32_t best_offset = 0, best_length = kMinMatch - 1;
+        uint64_t best_start = 0;
+#pragma nounroll
+        for (uint32_t n = kDepth; offset >= min_offset;) {
+            const uint32_t next = links[offset % kGWindow];
+            uint32_t l;
+            uint64_t st;
+            match_length<CH == 2>(value, data, len, anchor, ip, (uint64_t)(offset - base_index), l, st);
+            if (l > best_length) {
+                best_length = l;
+                best_offset = offset;
+                best_start = st;
+            }
+            if (l >= kNice || ip + l == len) break;
+            if (--n == 0) break;
+            offset = next;
+        }
+        if (best_length >= kMinMatch) return GMatch{best_length, (uint32_t)(ip - (uint64_t)(best_offset - base_index)), best_start};
+        return GMatch{0, 0, 0};
+    }
+
     // ParserInner::get_match (parse/mod.rs:58-85) with HashTableMatchFinder::get_and_insert
-    // (hashtable.rs:16-50) / NullMatchFinder
+    // (hashtable.rs:16-50) / HashChainMatchFinder::get_and_insert / NullMatchFinder
     template <bool RLE>
     __device__ GMatch get_match(const uint8_t* data, uint64_t len, uint32_t base_index, bool fizzle) {
         const uint64_t current = g_load64(data + ip);
@@ -295,16 +361,20 @@ struct GParser {
         GMatch r{0, 0, 0};
         if (!RLE) {
             const uint64_t anchor = fizzle ? ip : last_match;
-            const uint32_t sub = (uint32_t)ip > 32768 ? (uint32_t)ip - 32768 : 0;
-            const uint32_t min_offset = max(base_index + sub, 1u);
-            const uint32_t h = g_hash(current);
-            const uint32_t offset = hash[h];
-            hash[h] = (uint32_t)ip + base_index;
-            if (offset >= min_offset) {
-                uint32_t l;
-                uint64_t st;
-                match_length8(current, data, len, anchor, ip, (uint64_t)(offset - base_index), l, st);
-                if (l >= 8) r = GMatch{l, (uint32_t)(ip - (uint64_t)(offset - base_index)), st};
+            if constexpr (kChain) {
+                r = chain_get_and_insert(data, len, base_index, anchor, current);
+            } else {
+                const uint32_t sub = (uint32_t)ip > 32768 ? (uint32_t)ip - 32768 : 0;
+                const uint32_t min_offset = max(base_index + sub, 1u);
+                const uint32_t h = g_hash(current);
+                const uint32_t offset = hash[h];
+                hash[h] = (uint32_t)ip + base_index;
+                if (offset >= min_offset) {
+                    uint32_t l;
+                    uint64_t st;
+                    match_length<true>(current, data, len, anchor, ip, (uint64_t)(offset - base_index), l, st);
+                    if (l >= 8) r = GMatch{l, (uint32_t)(ip - (uint64_t)(offset - base_index)), st};
+                }
             }
             if (fizzle && r.length != 0) {  // parse/mod.rs:72-81: take bytes in front of the match while they agree
                 const uint64_t room = r.start > (uint64_t)r.distance + 1 ? r.start - r.distance - 1 : 0;  // (never down to byte 0)
@@ -324,7 +394,10 @@ struct GParser {
     // the path the scan follows while it finds nothing: all the data loads, then all the table loads,
     // then the decisions one by one in order.  The loads of a group are issued before its stores, so
     // an entry that an earlier step of the same group would have replaced is patched from registers;
-    // the steps behind a hit are dropped without having stored anything.
+    // the steps behind a hit are dropped without having stored anything.  The chain finder's scan is
+    // the same scan: a step stores a link as well, and the walk of the one step that has a candidate
+    // runs behind the unrolled part (65 536 x 64 KiB: 57.2 -> 48.7 ms at level 2, 595 -> 553 ms at level
+    // 3 against one step at a time; at level 3 a third of the steps have a candidate).
     static constexpr int kGroup = 16;
     template <bool RLE>
     __device__ GMatch advance_to_match(const uint8_t* data, uint64_t len, uint32_t base_index, uint64_t max_ip) {
@@ -337,12 +410,12 @@ struct GParser {
                 p[k] = q;
                 cur[k] = g_load64(data + (q < max_ip ? q : ip));
                 q++;
-                q += (q - last_match) >> 5;  // skip_ahead_shift = 5 (compress/mod.rs:76, :114)
+                q += (q - last_match) >> kShift;
             }
             if (!RLE) {
 #pragma unroll
                 for (int k = 0; k < kGroup; k++) {
-                    h[k] = g_hash(cur[k]);
+                    h[k] = g_hash(kChain ? cur[k] & kMask : cur[k]);
                     off[k] = hash[h[k]];
                 }
             }
@@ -362,12 +435,17 @@ struct GParser {
                         event = 1;
                     } else if ((uint32_t)cur[k] == (uint32_t)(cur[k] >> 8)) {
                         event = 2;
-                    } else if (!RLE) {  // HashTableMatchFinder::get_and_insert (hashtable.rs:16-50)
+                    } else if (!RLE) {  // HashTableMatchFinder::get_and_insert (hashtable.rs:16-50) / the insert
+                        // of HashChainMatchFinder::get_and_insert (hashchain.rs:59-66): with a chain a step also
+                        // stores its link -- the head's old value, patched like the head itself.  Links are only
+                        // read by a walk, and the one walk of a group (below, at the step that has a candidate)
+                        // comes after the stores of every step in front of it.
                         uint32_t offset = off[k];
 #pragma unroll
                         for (int j = 0; j < k; j++)
                             if (h[j] == h[k]) offset = (uint32_t)p[j] + base_index;
                         hash[h[k]] = (uint32_t)p[k] + base_index;
+                        if constexpr (kChain) links[((uint32_t)p[k] + base_index) % kGWindow] = offset;
                         const uint32_t sub = (uint32_t)p[k] > 32768 ? (uint32_t)p[k] - 32768 : 0;
                         if (offset >= max(base_index + sub, 1u)) {
                             event = 3;
@@ -390,14 +468,22 @@ struct GParser {
                 ip = r.end() - 3;
                 return r;
             }
-            uint32_t l;
-            uint64_t st;
-            GT0(2);
-            match_length8(ev_cur, data, len, last_match, ip, (uint64_t)(ev_off - base_index), l, st);
-            GT1(2);
-            ip++;
-            if (l >= 8) return GMatch{l, (uint32_t)(ev_p - (uint64_t)(ev_off - base_index)), st};
-            ip += (ip - last_match) >> 5;
+            if constexpr (kChain) {
+                GT0(2);
+                const GMatch r = chain_walk(data, len, base_index, last_match, ev_cur, ev_off);
+                GT1(2);
+                ip++;
+                if (r.length != 0) return r;
+            } else {
+                uint32_t l;
+                uint64_t st;
+                GT0(2);
+                match_length<true>(ev_cur, data, len, last_match, ip, (uint64_t)(ev_off - base_index), l, st);
+                GT1(2);
+                ip++;
+                if (l >= 8) return GMatch{l, (uint32_t)(ev_p - (uint64_t)(ev_off - base_index)), st};
+            }
+            ip += (ip - last_match) >> kShift;
         }
         return GMatch{0, 0, 0};
     }
@@ -406,7 +492,15 @@ struct GParser {
     // table; four at a time (the loads are independent, the stores stay in position order)
     template <bool RLE>
     __device__ void advance(const uint8_t* data, uint64_t len, uint32_t base_index, uint64_t end) {
-        if (!RLE) {
+        if constexpr (kChain) {  // HashChainMatchFinder::insert (hashchain.rs:109-114)
+            const uint64_t stop = min(end, len - 8);
+            for (uint64_t j = ip; j < stop; j++) {
+                const uint32_t h = g_hash(g_load64(data + j) & kMask), offset = base_index + (uint32_t)j;
+                const uint32_t prev = hash[h];
+                hash[h] = offset;
+                links[offset % kGWindow] = prev;
+            }
+        } else if (!RLE) {
             const uint64_t stop = min(end, len - 8);
             uint64_t j = ip;
             for (; j + 4 <= stop; j += 4) {
@@ -526,19 +620,21 @@ struct GParseArgs {
     const uint8_t* in;
     const uint64_t* in_off;
     uint64_t n;
-    uint32_t* hash;      // kGHashSize entries per resident lane (level 1)
+    uint32_t* hash;      // per resident lane kGHashSize entries (level 1), + kGWindow links (levels 2, 3)
     GMatchRec* matches;  // slices by g_match_slice
     GBlockRec* blocks;   // slices by g_block_slice
     uint32_t* nblocks;   // per stream; 0xFFFFFFFF = not supported (longer than 1 GiB)
     uint32_t lanes;      // streams per wavefront (1..64)
 };
 
-template <bool RLE>
+template <bool RLE, int CH = 0>
 __global__ __launch_bounds__(kWave) void deflate_parse_kernel(GParseArgs a) {
+    static_assert(!(RLE && CH != 0), "the RLE parser has no match finder");
     const uint32_t lane = threadIdx.x;
     const uint32_t L = a.lanes;
     const uint64_t in0 = a.in_off[0];
-    uint32_t* wave_hash = RLE ? nullptr : a.hash + (uint64_t)blockIdx.x * L * kGHashSize;
+    // a wavefront's tables: the L head tables first (cleared together below), then the L link rings
+    uint32_t* wave_hash = RLE ? nullptr : a.hash + (uint64_t)blockIdx.x * L * (kGHashSize + (CH != 0 ? kGWindow : 0u));
     for (uint64_t sid0 = (uint64_t)blockIdx.x * L; sid0 < a.n; sid0 += (uint64_t)gridDim.x * L) {
         if (!RLE) {
             // HashTableMatchFinder::new (hashtable.rs:10-14): the tables of the wavefront's streams
@@ -557,8 +653,9 @@ __global__ __launch_bounds__(kWave) void deflate_parse_kernel(GParseArgs a) {
             a.nblocks[sid] = 0xFFFFFFFFu;
             continue;
         }
-        GParser ps;
+        GParserT<CH> ps;
         ps.hash = RLE ? nullptr : wave_hash + (uint64_t)lane * kGHashSize;
+        ps.links = CH != 0 ? wave_hash + (uint64_t)L * kGHashSize + (uint64_t)lane * kGWindow : nullptr;
         ps.mrec = a.matches + g_match_slice(off - in0, sid);
         ps.brec = a.blocks + g_block_slice(off - in0, sid);
         ps.nmatch = ps.nblock = ps.nsym = 0;
@@ -576,7 +673,7 @@ __global__ __launch_bounds__(kWave) void deflate_parse_kernel(GParseArgs a) {
 #pragma nounroll
         for (int pass = 0; pass < 2; pass++) {
             if (pass) start = written > window ? written - window : 0;
-            const uint64_t r = ps.compress<RLE>(input + start, len - start, (uint32_t)start, pass ? written - start : 0, pass != 0);
+            const uint64_t r = ps.template compress<RLE>(input + start, len - start, (uint32_t)start, pass ? written - start : 0, pass != 0);
             if (!pass) written = r;
         }
         a.nblocks[sid] = ps.nblock;
@@ -1456,7 +1553,10 @@ extern "C" int fdh_debug_gen_timers(uint64_t* host /* 8 x 32768 */) {
 }
 #endif
 
-extern "C" size_t fdh_deflate_general_hash_bytes(void) { return (size_t)fdh::kGHashSize * 4; }
+// table bytes per resident stream; kind: 0 level 1, 1 RLE, 2 / 3 levels 2 / 3 (head table + link ring)
+extern "C" size_t fdh_deflate_general_hash_bytes(int kind) {
+    return kind == 1 ? 0 : ((size_t)fdh::kGHashSize + (kind >= 2 ? fdh::kGWindow : 0u)) * 4;
+}
 // record slices for a batch whose inputs span `total_in` bytes: element counts
 extern "C" size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n) { return (size_t)fdh::g_match_slice(total_in, n) + 2; }
 extern "C" size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n) { return (size_t)fdh::g_block_slice(total_in, n) + 4; }
@@ -1464,13 +1564,17 @@ extern "C" size_t fdh_deflate_general_match_record_bytes(void) { return sizeof(f
 extern "C" size_t fdh_deflate_general_block_record_bytes(void) { return sizeof(fdh::GBlockRec); }
 
 extern "C" int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                                          uint32_t* out_len, uint64_t n, int rle, void* hash, void* matches, void* blocks,
+                                          uint32_t* out_len, uint64_t n, int kind, void* hash, void* matches, void* blocks,
                                           uint32_t* nblocks, unsigned waves, unsigned lanes, hipStream_t stream) {
     if (n == 0) return 0;
     fdh::GParseArgs p{in, in_off, n, static_cast<uint32_t*>(hash), static_cast<fdh::GMatchRec*>(matches),
                       static_cast<fdh::GBlockRec*>(blocks), nblocks, lanes};
-    if (rle)
+    if (kind == 1)
         hipLaunchKernelGGL(fdh::deflate_parse_kernel<true>, dim3(waves), dim3(fdh::kWave), 0, stream, p);
+    else if (kind == 2)
+        hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 2>), dim3(waves), dim3(fdh::kWave), 0, stream, p);
+    else if (kind == 3)
+        hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 3>), dim3(waves), dim3(fdh::kWave), 0, stream, p);
     else
         hipLaunchKernelGGL(fdh::deflate_parse_kernel<false>, dim3(waves), dim3(fdh::kWave), 0, stream, p);
     fdh::GWriteArgs w{in, in_off, out, out_off, out_len, n, static_cast<const fdh::GMatchRec*>(matches),

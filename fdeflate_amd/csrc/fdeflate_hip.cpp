@@ -28,7 +28,7 @@ int fdh_launch_png_filter_deflate_ultrafast(const uint8_t* pix, const uint64_t* 
 int fdh_launch_deflate_ultrafast(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
                                  uint32_t* out_len, uint64_t n, hipStream_t stream);
 int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                               uint32_t* out_len, uint64_t n, int rle, void* hash, void* matches, void* blocks,
+                               uint32_t* out_len, uint64_t n, int kind, void* hash, void* matches, void* blocks,
                                uint32_t* nblocks, unsigned waves, unsigned lanes, hipStream_t stream);
 int fdh_launch_png_unfilter(const uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off,
                             uint32_t* status, const uint32_t* gate, const uint32_t* gate_len, uint64_t n,
@@ -36,7 +36,7 @@ int fdh_launch_png_unfilter(const uint8_t* filt, const uint64_t* filt_off, uint8
 int fdh_launch_png_filter(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
                           uint8_t* filt, const uint64_t* filt_off, uint32_t* status, uint64_t n, uint32_t row_bytes,
                           uint32_t bpp, hipStream_t stream);
-size_t fdh_deflate_general_hash_bytes(void);
+size_t fdh_deflate_general_hash_bytes(int kind);
 size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n);
 size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n);
 size_t fdh_deflate_general_match_record_bytes(void);
@@ -259,11 +259,11 @@ int fdh_inflate_png_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* fi
     return FDH_SUCCESS;
 }
 
-// ---- general encoder (level 1 / RLE): per-device workspace, grown on demand, never shrunk ----
+// ---- general encoder (levels 1-3 / RLE): per-device workspace, grown on demand, never shrunk ----
 namespace {
 struct GenWork {
     std::mutex mutex;         // the workspace is shared by the calls on ITS device only
-    void* hash = nullptr;     // one 64 Ki-entry table per resident lane of the parser (level 1)
+    void* hash = nullptr;     // per resident lane of the parser one 64 Ki-entry table (level 1), + a 32 Ki-entry link ring (levels 2, 3)
     void* matches = nullptr;  // what the parser hands to the block writer, sliced per stream
     void* blocks = nullptr;
     void* nblocks = nullptr;
@@ -295,7 +295,8 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
     if (n == 0) return FDH_SUCCESS;
     if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
     if (!out) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");  // (`in` may be null for a batch of empty inputs: below)
-    if (mode != FDH_MODE_LEVEL1 && mode != FDH_MODE_RLE) return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
+    if (mode != FDH_MODE_LEVEL1 && mode != FDH_MODE_RLE && mode != FDH_MODE_LEVEL2 && mode != FDH_MODE_LEVEL3)
+        return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call");
     if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
@@ -320,18 +321,26 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
     // 16 GiB.  (Round 5: the cap was 8 GiB and applied to the RLE parser too, which has no tables: 65 536 streams ran as
     // 1 024 wavefronts of 32 lanes in two rounds, one wavefront per SIMD.  All of them in flight: level 1 39.2 -> 31.7 ms,
     // RLE 25.4 -> 21.9 ms.)
+    // Levels 2 and 3 run the same parser with the hash-chain finder, one stream per lane as well: a head table and a
+    // link ring per stream (384 KiB), so fewer streams are resident under the same 16 GiB (43 690 instead of 65 536).
     const bool rle = mode == FDH_MODE_RLE;
+    const int kind = rle ? 1 : mode == FDH_MODE_LEVEL2 ? 2 : mode == FDH_MODE_LEVEL3 ? 3 : 0;  // the launcher's numbering
+    const size_t table_bytes = fdh_deflate_general_hash_bytes(kind);
+    const uint64_t table_cap = rle ? (1ull << 40) : (16ull << 30) / table_bytes;
     unsigned lanes = 64;
-    const uint64_t want_waves = (uint64_t)cus * (rle ? 16 : 8);
+    // (the chain parsers: 204 VGPRs, 8 wavefronts per CU resident like level 1, but asked for twice as many, i.e. half as
+    // many lanes each: 65 536 streams as 16 lanes x 2 730 wavefronts ran 42.9 / 499.7 ms at levels 2 / 3, as 32 lanes x 1 365
+    // -- all that 16 GiB of tables allow at that width -- 48.3 / 562.6 ms)
+    const uint64_t want_waves = (uint64_t)cus * (kind == 0 ? 8 : 16);
     while (lanes > 4 && (n + lanes - 1) / lanes < want_waves) lanes /= 2;
     if (const char* e = std::getenv("FDH_GEN_LANES")) {
         const int v = std::atoi(e);
         if (v >= 1 && v <= 64) lanes = (unsigned)v;
     }
-    uint64_t max_resident = rle ? (1ull << 40) : 65536;
+    uint64_t max_resident = table_cap;
     if (const char* e = std::getenv("FDH_GEN_RESIDENT")) {
         const long long v = std::atoll(e);
-        if (v >= 64 && v <= (1 << 20)) max_resident = (uint64_t)v;
+        if (v >= 64 && v <= (1 << 20)) max_resident = kind >= 2 ? std::min<uint64_t>((uint64_t)v, table_cap) : (uint64_t)v;  // (the new modes keep the 16 GiB)
     }
     unsigned waves = (unsigned)std::min<uint64_t>((n + lanes - 1) / lanes, std::max<uint64_t>(1, max_resident / lanes));
     GenWork& w = g_gen_work[dev];
@@ -341,7 +350,7 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
         // exactly the resident lanes' tables (no headroom: at the cap that is the documented 8 GiB);
         // on a smaller or busy device the batch runs with fewer resident wavefronts instead of failing
         for (;;) {
-            rc = grow(&w.hash, &w.hash_bytes, (size_t)waves * lanes * fdh_deflate_general_hash_bytes(), "hipMalloc(hash tables)", false);
+            rc = grow(&w.hash, &w.hash_bytes, (size_t)waves * lanes * table_bytes, "hipMalloc(hash tables)", false);
             if (rc == FDH_SUCCESS || waves <= 1) break;
             (void)hipGetLastError();
             waves /= 2;
@@ -355,7 +364,7 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
                   "hipMalloc(block records)");
     if (rc == FDH_SUCCESS) rc = grow(&w.nblocks, &w.nblock_bytes, (size_t)n * 4, "hipMalloc(block counts)");
     if (rc != FDH_SUCCESS) return rc;
-    rc = fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, rle, w.hash, w.matches, w.blocks,
+    rc = fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, kind, w.hash, w.matches, w.blocks,
                                     static_cast<uint32_t*>(w.nblocks), waves, lanes, stream);
     if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "general-encoder kernel launch");
     // the workspace is per device, not per stream: calls are serialised by finishing this one
@@ -456,7 +465,8 @@ static int compress_one(int kind, const uint8_t* input, size_t input_len, uint8_
     int rc = stored      ? fdh_deflate_stored_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
              : kind == 0 ? fdh_deflate_ultrafast_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
                          : fdh_deflate_general_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1,
-                                                     kind == 2 ? FDH_MODE_LEVEL1 : FDH_MODE_RLE, nullptr);
+                                                     kind == 2 ? FDH_MODE_LEVEL1 : kind == 3 ? FDH_MODE_RLE : kind == 4 ? FDH_MODE_LEVEL2 : FDH_MODE_LEVEL3,
+                                                     nullptr);
     if (rc != FDH_SUCCESS) return rc;
     HIP_TRY(hipDeviceSynchronize());
     uint32_t n32 = 0;
@@ -490,6 +500,19 @@ int fdh_compress_to_vec(const uint8_t* input, size_t input_len, uint8_t** output
 
 int fdh_compress_to_vec_rle(const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
     return compress_one(3, input, input_len, output, output_len);
+}
+
+int fdh_compress_to_vec_with_level(const uint8_t* input, size_t input_len, uint32_t level, uint8_t** output,
+                                   size_t* output_len) {
+    switch (level) {
+        case 0: return compress_one(1, input, input_len, output, output_len);
+        case 1: return compress_one(2, input, input_len, output, output_len);
+        case 2: return compress_one(4, input, input_len, output, output_len);
+        case 3: return compress_one(5, input, input_len, output, output_len);
+        default:
+            return fail(FDH_ERR_INVALID_ARGUMENT,
+                        "compression level not provided: levels 0, 1, 2 and 3 are (4-9, the lazy parser, are not)");
+    }
 }
 
 void fdh_free(void* p) { std::free(p); }

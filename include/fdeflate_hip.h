@@ -185,14 +185,26 @@ uint64_t fdh_stored_size(uint64_t len);
  *                    src/compress/matchfinder/hashtable.rs, dynamic blocks src/compress/bitstream.rs)
  *   FDH_MODE_RLE     `compress_to_vec_rle(input)` (src/compress/mod.rs:306-310; Compressor::new_rle
  *                    :107-123 = RleParser src/compress/parse/rle.rs)
+ *   FDH_MODE_LEVEL2  `compress_to_vec_with_level(input, 2)` (src/compress/mod.rs:77-78: GreedyParser,
+ *                    skip_ahead_shift 6, HashChainMatchFinder::<true>::new(8, 16, 64)
+ *                    src/compress/matchfinder/hashchain.rs)
+ *   FDH_MODE_LEVEL3  `compress_to_vec_with_level(input, 3)` (src/compress/mod.rs:79: GreedyParser,
+ *                    skip_ahead_shift 6, HashChainMatchFinder::<false>::new(6, 16, 32), 4-byte
+ *                    match_length src/compress/matchfinder/mod.rs:51-110)
+ * Levels 4-9 (LazyParser + HybridMatchFinder, src/compress/mod.rs:80-99) are not provided.  Levels 2
+ * and 3 are pinned by tests/level_model.py, a restatement that is itself pinned against the oracle
+ * at level 1 and RLE; the oracle has no chain finder.
  * Same argument convention as fdh_deflate_ultrafast_batch; slots of at least fdh_compress_bound(len_i)
  * bytes; out_len[i] = 0xFFFFFFFF if a slot was too small or the buffer exceeds 1 GiB.  The call
- * uses a per-device workspace (one 256 KiB hash table per resident stream at level 1, at most
- * 16 GiB; 8 bytes per 4 input bytes for the back-reference records), reads in_off[0] and in_off[n]
+ * uses a per-device workspace (per resident stream one 256 KiB hash table at level 1, a 256 KiB head
+ * table and a 128 KiB link ring at levels 2 and 3, at most 16 GiB -- so fewer streams are resident at
+ * levels 2 and 3; 8 bytes per 4 input bytes for the back-reference records), reads in_off[0] and in_off[n]
  * back to size it, and returns after the kernels have finished.
  */
 #define FDH_MODE_LEVEL1 1u
 #define FDH_MODE_RLE 2u
+#define FDH_MODE_LEVEL2 3u /* src/compress/mod.rs:77-78 */
+#define FDH_MODE_LEVEL3 4u /* src/compress/mod.rs:79 */
 int fdh_deflate_general_batch(const uint8_t *in, const uint64_t *in_off, uint8_t *out,
                               const uint64_t *out_off, uint32_t *out_len, uint64_t n, uint32_t mode,
                               void *hip_stream);
@@ -318,6 +330,10 @@ int fdh_compress_to_vec(const uint8_t *input, size_t input_len, uint8_t **output
                         size_t *output_len); /* compress_to_vec = level 1, compress/mod.rs:294 */
 int fdh_compress_to_vec_rle(const uint8_t *input, size_t input_len, uint8_t **output,
                             size_t *output_len); /* compress_to_vec_rle, compress/mod.rs:306 */
+/* compress_to_vec_with_level, compress/mod.rs:299: level 0 stored, 1, 2 and 3 the general encoder;
+ * level 4 and above returns FDH_ERR_INVALID_ARGUMENT (fdh_last_error() names the levels provided). */
+int fdh_compress_to_vec_with_level(const uint8_t *input, size_t input_len, uint32_t level,
+                                   uint8_t **output, size_t *output_len);
 void fdh_free(void *p);
 
 /* ---- several GPUs of one node, one process --------------------------------

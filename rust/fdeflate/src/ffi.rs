@@ -8,6 +8,8 @@ pub const FDH_FLAG_IGNORE_ADLER32: u32 = 0x1;
 pub const FDH_OUTPUT_TOO_LARGE: u32 = 17;
 pub const FDH_MODE_LEVEL1: u32 = 1;
 pub const FDH_MODE_RLE: u32 = 2;
+pub const FDH_MODE_LEVEL2: u32 = 3;
+pub const FDH_MODE_LEVEL3: u32 = 4;
 
 #[repr(C)]
 pub struct fdh_decompressor {
@@ -84,6 +86,7 @@ extern "C" {
     pub fn fdh_compress_to_vec_stored(input: *const u8, len: usize, out: *mut *mut u8, out_len: *mut usize) -> c_int;
     pub fn fdh_compress_to_vec(input: *const u8, len: usize, out: *mut *mut u8, out_len: *mut usize) -> c_int;
     pub fn fdh_compress_to_vec_rle(input: *const u8, len: usize, out: *mut *mut u8, out_len: *mut usize) -> c_int;
+    pub fn fdh_compress_to_vec_with_level(input: *const u8, len: usize, level: u32, out: *mut *mut u8, out_len: *mut usize) -> c_int;
     pub fn fdh_free(p: *mut c_void);
 
     // several GPUs of a node from one process

@@ -2,9 +2,9 @@
 //!
 //! Same items, same signatures, same error values as the reference crate; every byte of decoding
 //! and encoding happens on the GPU behind the C ABI of `include/fdeflate_hip.h`.  What the
-//! reference has and this shim does not: `Compressor<W>` for levels 2-9 (the LZ77 match search of
-//! those levels is outside the hot path, see DESIGN.md "out of scope") and the hidden
-//! `compute_code_lengths` helper.
+//! reference has and this shim does not: compression levels 4-9 (the lazy parser and its hybrid
+//! match finder, see DESIGN.md "out of scope"; levels 0-3 are provided), the streaming
+//! `Compressor<W>` and the hidden `compute_code_lengths` helper.
 //!
 //! Source only: the build container has no Rust toolchain, so this crate has never been compiled
 //! there.  The same C entry points are exercised through ctypes by `tests/`.
@@ -204,13 +204,15 @@ pub fn compress_to_vec(input: &[u8]) -> Vec<u8> {
 }
 
 /// Compresses the given data with a specific compression level (`src/compress/mod.rs:299`).
-/// Levels 0 and 1 run on the GPU; the LZ77 searches of levels 2-9 are not part of this codec.
+/// Levels 0 to 3 run on the GPU (0 stored, 1 hash table, 2 and 3 hash chains); the lazy parser of
+/// levels 4-9 is not part of this codec and panics.
 pub fn compress_to_vec_with_level(input: &[u8], level: u8) -> Vec<u8> {
-    match level {
-        0 => compress_with(ffi::fdh_compress_to_vec_stored, input),
-        1 => compress_with(ffi::fdh_compress_to_vec, input),
-        _ => panic!("fdeflate (hip): compression level {level} is not provided by the GPU codec"),
+    if level > 3 {
+        panic!("fdeflate (hip): compression level {level} is not provided by the GPU codec (levels 0-3 are)");
     }
+    let (mut p, mut n) = (std::ptr::null_mut(), 0usize);
+    check(unsafe { ffi::fdh_compress_to_vec_with_level(input.as_ptr(), input.len(), level as u32, &mut p, &mut n) });
+    unsafe { take(p, n) }
 }
 
 /// Compresses the given data using only RLE matches (`src/compress/mod.rs:306`).
