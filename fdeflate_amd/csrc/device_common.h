@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/fdeflate_hip.h"  // FDH_FLAG_*: the one definition of every flag bit the kernels test
 
 namespace fdh {
 

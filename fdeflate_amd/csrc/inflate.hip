@@ -1,18 +1,25 @@
-// inflate.hip -- batched zlib decode kernels (gfx950).  One independent stream per wavefront.
+// inflate.hip -- batched zlib decode kernels (gfx950) and their launcher.  One independent stream per wavefront.
 //
-// fdh_launch_inflate runs, back to back on the caller's stream (each kernel finishes what it can
-// and leaves the rest PENDING in the status word):
+// fdh_launch_inflate (at the end of this file) runs one of five chains; each kernel finishes what it can, leaves the
+// rest PENDING in the status word and lists it for the kernel behind (DESIGN.md 3.1 has the numbers):
 //
-//   inflate_segments_kernel      streams that start with the ultra-fast encoder's fixed 53-byte +
-//                                5-bit prefix (reference src/compress/ultrafast.rs:82-88: zlib header
-//                                + one final dynamic block header): segment-parallel, one shared
-//                                table copy per workgroup (inflate_segments.h).
-//   inflate_canon_kernel         canonical streams the segment kernel left over: 8 wavefronts per
-//                                workgroup sharing ONE copy of the tables (built once per device from
-//                                the prefix bytes by canon_build_kernel), tile + serial decoders.
-//   inflate_general_fast_kernel  any zlib stream (stored / fixed / dynamic, multi-block), private
-//                                10-bit tables: 8 workgroups per CU; leaves exactness-guard cases.
+//   stream_order_kernel          large batches: the hand-out order of the two kernels below (four classes by compressed
+//                                length, longest first); streams without the ultra-fast prefix go straight to the
+//                                LZ-window kernel's list, which that kernel and its exact kernels take on a side stream.
+//   inflate_seg3_kernel          the landing decoder (inflate_seg3.h, inflate_seg3.hip): every stream that starts with
+//                                the ultra-fast encoder's fixed 53-byte + 5-bit prefix (reference
+//                                src/compress/ultrafast.rs:82-88), 64 segments per stream.
+//   inflate_seg2_kernel          the interval decoder (inflate_seg2.h): what the landing decoder passes on.
+//   inflate_segments_kernel      segment-parallel, one shared table copy per workgroup (inflate_segments.h).
+//   inflate_canon_kernel         canonical streams still left: 8 wavefronts per workgroup sharing ONE copy of the tables
+//                                (built once per device from the prefix bytes by canon_build_kernel), tile + serial decoders.
+//   inflate_lz_kernel            the LZ-window decoder (inflate_lz.h): any zlib stream, persistent wavefronts.
+//   inflate_general_fast_kernel  any zlib stream (stored / fixed / dynamic, multi-block), private small tables:
+//                                8 workgroups per CU; leaves exactness-guard cases.
 //   inflate_general_kernel       the same with the reference's 12-bit tables; runs what is left.
+//
+// Behind the landing decoder a large batch takes the exact kernel alone while recent calls left next to nothing
+// (TailHint); FDH_FLAG_RESUME_IN runs resume_prepare_kernel, the LZ-window kernel and the 12-bit kernel only.
 //
 // Exactness guard: results other than Ok that depend on how literals were paired by the
 // double-literal table at the very end of a truncated input, and all hard errors, are re-derived
@@ -118,11 +125,11 @@ __device__ __forceinline__ ResumePoint resume_point(const InflateBatchArgs& a, c
     ResumePoint rp;
     rp.valid = 0;
     rp.step = 0;
-    if (a.resume && a.only_pending && (st == kPendingResume || st == kPendingSerial) && !(a.flags & 0x4000u)) {
+    if (a.resume && a.only_pending && (st == kPendingResume || st == kPendingSerial) && !(a.flags & FDH_FLAG_NO_CHECKPOINTS)) {
         rp = unpack_record(load_record(&a.resume[sid]));
         if (!rp.valid && st == kPendingResume) {  // the record is lost: not "from the first byte" -- from the caller's record
             if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(&g_lost_records, 1u);
-            if ((a.flags & 0x8000u) && a.resume_out && a.resume_out != a.resume) rp = unpack_record(load_record(&a.resume_out[sid]));
+            if ((a.flags & FDH_FLAG_RESUME_IN) && a.resume_out && a.resume_out != a.resume) rp = unpack_record(load_record(&a.resume_out[sid]));
         }
     }
     return rp;
@@ -152,7 +159,7 @@ __device__ __forceinline__ StreamArgs stream_args(const InflateBatchArgs& a, uin
 // A result the tile decoder may have classified differently from the reference: anything but Ok
 // and a "robust" OutputTooLarge / InsufficientInput far away from the end of the input.
 __device__ __forceinline__ bool needs_serial_recheck(const StreamResult& r, uint32_t flags) {
-    if (flags & 8u) return false;  // FDH_FLAG_NO_RECHECK (tests: the tile decoder on its own)
+    if (flags & FDH_FLAG_NO_RECHECK) return false;  // (tests: the tile decoder on its own)
     if (r.status == ST_OK) return false;
     // A decoder that got as far as comparing the checksum read every block to its end and found the four trailer
     // bytes behind the last one: the input never ran short inside a token, which is the only place where the
@@ -175,7 +182,7 @@ struct GeneralLds {
 __device__ __forceinline__ void general_one(const InflateBatchArgs& a, GeneralLds& lds, const uint64_t sid) {
     const int lane = threadIdx.x;
     if (sid >= a.n) return;
-    bool tiles = !(a.flags & 2u);
+    bool tiles = !(a.flags & FDH_FLAG_SERIAL_ONLY);
     uint32_t st = kPending;
     if (a.only_pending) {
         st = load_word(&a.status[sid]);
@@ -197,7 +204,7 @@ __device__ __forceinline__ void general_one(const InflateBatchArgs& a, GeneralLd
     if (tiles) {
         // the span decoder lists matches in global scratch: take one of the pool's slots
         uint32_t slot = kSpanSlots;
-        if (a.span_pool && (a.flags & 0x100u) && s.in_len >= 4096) {
+        if (a.span_pool && (a.flags & FDH_FLAG_SPANS) && s.in_len >= 4096) {
             if (lane == 0) {
                 slot = (uint32_t)(sid % kSpanSlots);
                 while (atomicCAS(&a.span_pool[slot], 0u, 1u) != 0u) slot = (slot + 1) % kSpanSlots;
@@ -210,7 +217,7 @@ __device__ __forceinline__ void general_one(const InflateBatchArgs& a, GeneralLd
         // of them -- the tail of the stream, not the stream (rounds 1-3: a damaged stream cost a serial pass over
         // all of it).  A tile starts at a symbol, not necessarily at one of the reference's table steps:
         // resync_to_step_start (inflate_stream.h) deals with that.
-        inf.keep_ck = !(a.flags & 0x4000u);
+        inf.keep_ck = !(a.flags & FDH_FLAG_NO_CHECKPOINTS);
         inf.init(s);
         r = rec.valid ? inf.run_from<true>(rec) : inf.run<true, false>();
         if (slot < kSpanSlots) {
@@ -235,7 +242,7 @@ __device__ __forceinline__ void general_one(const InflateBatchArgs& a, GeneralLd
             if (whole) inf.init(s);
             retracted = !whole && r.out_len < rp.opos;  // (the first literal of a pair whose second one is cut off)
         }
-        if (whole && (a.flags & 0x8000u) && a.resume_out && a.resume_out != a.resume) {
+        if (whole && (a.flags & FDH_FLAG_RESUME_IN) && a.resume_out && a.resume_out != a.resume) {
             // ... then from the point this CALL took the stream up at, if that one knows its place among the steps
             // (the caller's record is still there: a final result overwrites it, and there is none yet)
             const ResumePoint first = unpack_record(load_record(&a.resume_out[sid]));
@@ -272,6 +279,14 @@ __device__ __forceinline__ void general_one(const InflateBatchArgs& a, GeneralLd
 // hand-out counter is word 1 of its list (word 3 of that list was the landing decoder's own).
 __device__ uint32_t* g_tail_report = nullptr;
 constexpr uint32_t kFlagTailReport = 0x20000000u, kFlagTailCounter1 = 0x40000000u;
+constexpr uint32_t kPublicFlags =
+    FDH_FLAG_IGNORE_ADLER32 | FDH_FLAG_SERIAL_ONLY | FDH_FLAG_GENERAL_ONLY | FDH_FLAG_NO_RECHECK | FDH_FLAG_FORCE_LANES | FDH_FLAG_NO_LANES |
+    FDH_FLAG_FIRST_ONLY | FDH_FLAG_NO_SEGMENTS | FDH_FLAG_SPANS | FDH_FLAG_NO_FAST_GENERAL | FDH_FLAG_NO_INTERVALS | FDH_FLAG_INTERVALS_ONLY |
+    FDH_FLAG_NO_LZ | FDH_FLAG_LZ_ONLY | FDH_FLAG_NO_CHECKPOINTS | FDH_FLAG_RESUME_IN | FDH_FLAG_NO_LANDING | FDH_FLAG_LANDING_ONLY |
+    FDH_FLAG_LANDING_COUNT_ONLY | FDH_FLAG_NO_LEAN_WRITE | FDH_FLAG_NO_OVERLAP | FDH_FLAG_TAIL_LONG | FDH_FLAG_TAIL_SHORT | FDH_FLAG_ORDER_ONCE |
+    FDH_FLAG_ORDER_TWICE;
+static_assert(((kFlagTailReport | kFlagTailCounter1) & kPublicFlags) == 0 && (kFlagTailReport & kFlagTailCounter1) == 0,
+              "the internal flag bits overlap no bit of include/fdeflate_hip.h");
 __device__ __forceinline__ void tail_report(uint32_t count, int what = 0) {  // what: 0 the landing decoder's leftovers, 2 the other list
     uint32_t* const rep = g_tail_report;
     if (rep) {
@@ -329,7 +344,7 @@ __device__ __forceinline__ void general_fast_one(const InflateBatchArgs& a, Gene
     }
     const StreamArgs s = stream_args(a, sid);
     InflaterT<kFastLitBits, false> inf(lds.tables, lds.io, reinterpret_cast<HeaderScratch*>(lds.io.mlist), lane);
-    inf.keep_ck = (a.resume != nullptr || a.resume_out != nullptr) && !(a.flags & 0x4000u);  // (what it cannot classify goes on from its last check point)
+    inf.keep_ck = (a.resume != nullptr || a.resume_out != nullptr) && !(a.flags & FDH_FLAG_NO_CHECKPOINTS);  // (what it cannot classify goes on from its last check point)
     inf.init(s);
     const ResumePoint rec = resume_point(a, sid, st);
     const StreamResult r = rec.valid ? inf.run_from<true>(rec) : inf.run<true, false>();
@@ -510,7 +525,7 @@ __device__ __forceinline__ bool lz_one(const InflateBatchArgs& a, LzLds& L, cons
         if (inf.read_trailer(stored) != RC_OK) LZ_LEAVE(bitpos - eob_bits);
         lz_flush(L, o, true, lane);
         const uint32_t adler = (o.adler_b << 16) | o.adler_a;
-        if (!(a.flags & 1u) && stored != adler) LZ_LEAVE(bitpos - eob_bits);  // WrongChecksum is the exact kernels' verdict
+        if (!(a.flags & FDH_FLAG_IGNORE_ADLER32) && stored != adler) LZ_LEAVE(bitpos - eob_bits);  // WrongChecksum is the exact kernels' verdict
         if (lane == 0) {
             a.status[sid] = ST_OK;
             a.out_len[sid] = o.O;
@@ -529,7 +544,7 @@ __device__ __forceinline__ bool lz_one(const InflateBatchArgs& a, LzLds& L, cons
 lz_leave:
     if (from.valid && o.O == O_in) {  // nothing gained: the point this call started from stands (it may know more: its step state)
         rec = resume_record(from);
-    } else if (o.O != 0 && !(a.flags & 0x4000u)) {
+    } else if (o.O != 0 && !(a.flags & FDH_FLAG_NO_CHECKPOINTS)) {
         lz_flush(L, o, true, lane);
         rec = make_uint4(hdr_bit, leave_bit, o.O, (o.adler_b << 16) | o.adler_a);
     }
@@ -627,7 +642,7 @@ __global__ __launch_bounds__(kCanonWaves* kWave, 4) void inflate_canon_kernel(In
     inf.eof_mask = lds.tables.eof[1];
     inf.eof_bits = lds.tables.eof[2];
     inf.hdr_bit = 16;  // (the block header of the prefix, for the check points)
-    inf.keep_ck = (a.resume != nullptr || a.resume_out != nullptr) && !(a.flags & 0x4000u);
+    inf.keep_ck = (a.resume != nullptr || a.resume_out != nullptr) && !(a.flags & FDH_FLAG_NO_CHECKPOINTS);
     StreamResult r = inf.run<true, true>();
     if (lane == 0) {
         if (needs_serial_recheck(r, a.flags)) {
@@ -987,70 +1002,12 @@ extern "C" int fdh_debug_s2time(uint32_t* host) {
 }
 #endif
 
-// device address of g_canon, looked up once per device by fdh_launch_canon_build (the lookup
-// synchronises, so it must stay off the launch path)
-static fdh::CanonTables* g_canon_dev[64] = {};
-static uint32_t* g_span_pool[64] = {};  // per device: scratch of the span decoder (never freed)
-static int g_cu_count[64] = {};         // per device: compute units (0 = not asked yet)
-static hipStream_t g_side_stream[64] = {};  // per device: the stream the LZ-window kernel runs on beside the canonical kernels
-static std::mutex g_dev_mutex;          // guards the per-device caches above and below
-// What the landing decoder leaves over, as the kernels report it (g_tail_report): while the reports say "next to nothing"
-// the call launches ONE kernel behind the landing decoder (the exact kernel, which takes any stream) instead of five (the
-// interval, segment and tile decoders and the two exact kernels: each launch costs ~10 us of the chain when its list is
-// empty -- 60 us of a 2.6 ms call).  The latest report decides: more than kTailFew streams left over, the long chain.
-// A hint only: every stream is decoded either way, a wrong guess costs time (the exact kernel is slow).
-struct TailHint {
-    volatile uint32_t* rep = nullptr;  // mapped host memory
-    uint32_t seen = 0;                 // rep[1] at the last look
-    uint32_t seen_others = 0;          // rep[3]
-    int streak = 0;
-    bool short_chain = false;
-    bool order_once = false;           // stream_order_kernel in one launch: the other list in no order (it has been next to empty)
-    bool tried = false;
-};
-static TailHint g_tail[64];
-constexpr uint32_t kTailFew = 16;
+// ---- host side: the per-device tables and hooks, then the chains of launches -------------------------------------
 
-// Scratch of a call (lists, check points, records): stream-ordered allocations from a pool of the library's own that
-// KEEPS what is freed (release threshold = everything).  With the device's default pool -- which hands its memory back
-// at every synchronisation -- a call that followed a hipStreamSynchronize got fresh pages, and about one such call in
-// ten then read ZEROS where the first kernel of the call had just written (seen on the record resume_prepare_kernel
-// leaves for the kernels behind it: status "taken up at a resume point", record all zero).  Until round 5 that only
-// cost time -- a stream without a record is decoded from its first byte -- and went unnoticed; with the streaming
-// object's moved buffers (stream_decompressor.cpp) it decoded garbage.  Memory that stays mapped does not do it
-// (tools/streamtime.py, 16 runs of ~130 calls each: 0 failures against 6 in 8), and a call no longer pays for mapping
-// and unmapping its scratch.
-static hipMemPool_t g_scratch_pool[64];
-static hipError_t scratch_alloc(void** p, size_t bytes, hipStream_t stream) {
-    int dev = 0;
-    hipMemPool_t pool = nullptr;
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
-        std::lock_guard<std::mutex> lock(g_dev_mutex);
-        if (!g_scratch_pool[dev]) {
-            hipMemPoolProps props = {};
-            props.allocType = hipMemAllocationTypePinned;
-            props.location.type = hipMemLocationTypeDevice;
-            props.location.id = dev;
-            hipMemPool_t q = nullptr;
-            const hipError_t ce = hipMemPoolCreate(&q, &props);
-            if (ce != hipSuccess || !q) {  // (no fall-back to the default pool: that is the pool the zeros came from)
-                (void)hipGetLastError();
-                return ce != hipSuccess ? ce : hipErrorOutOfMemory;
-            }
-            uint64_t keep = ~0ull;
-            const hipError_t se = hipMemPoolSetAttribute(q, hipMemPoolAttrReleaseThreshold, &keep);
-            if (se != hipSuccess) {
-                (void)hipGetLastError();
-                (void)hipMemPoolDestroy(q);
-                return se;
-            }
-            g_scratch_pool[dev] = q;
-        }
-        pool = g_scratch_pool[dev];
-    }
-    if (!pool) return hipErrorInvalidDevice;
-    return hipMallocFromPoolAsync(p, bytes, pool, stream);
-}
+// inflate_seg3.hip (a translation unit of its own: it builds in a fraction of the time of this one)
+int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);
+
+#include "inflate_launch.h"  // DeviceState, the grid sizes, CallScratch, SideFork, launch()
 
 // (introspection, tests / soak: resume records that read zero under a status that promised one, since the library was loaded)
 extern "C" int fdh_debug_lost_records(unsigned int* count) {
@@ -1068,13 +1025,13 @@ extern "C" int fdh_launch_canon_build(hipStream_t stream, uint32_t* host_status)
     e = hipGetSymbolAddress(reinterpret_cast<void**>(&dev), HIP_SYMBOL(fdh::g_canon));
     if (e != hipSuccess) return (int)e;
     e = hipMemcpy(host_status, &dev->status, sizeof(uint32_t), hipMemcpyDeviceToHost);
-    int ordinal = 0;
-    if (e == hipSuccess) e = hipGetDevice(&ordinal);
-    if (e == hipSuccess && ordinal >= 0 && ordinal < 64) {
+    DeviceState* ds = nullptr;
+    if (e == hipSuccess) e = current_device(&ds);
+    if (e == hipSuccess) {
         std::lock_guard<std::mutex> lock(g_dev_mutex);
-        g_canon_dev[ordinal] = dev;
+        ds->canon = dev;
         // the word pair the kernels behind the landing decoder report to (optional: without it every call takes the long chain)
-        TailHint& h = g_tail[ordinal];
+        TailHint& h = ds->tail;
         if (!h.tried) {
             h.tried = true;
             uint32_t* hp = nullptr;
@@ -1098,10 +1055,10 @@ extern "C" int fdh_launch_canon_build(hipStream_t stream, uint32_t* host_status)
 
 // (introspection: the last report's count, the number of reports, the streak of small ones, the mode)
 extern "C" int fdh_debug_tail_state(unsigned int* out4) {
-    int dev = 0;
-    if (!out4 || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    DeviceState* ds = nullptr;
+    if (!out4 || current_device(&ds) != hipSuccess) return -1;
     std::lock_guard<std::mutex> lock(g_dev_mutex);
-    const TailHint& h = g_tail[dev];
+    const TailHint& h = ds->tail;
     out4[0] = h.rep ? h.rep[0] : 0xFFFFFFFFu;
     out4[1] = h.rep ? h.rep[1] : 0xFFFFFFFFu;
     out4[2] = (unsigned int)h.streak;
@@ -1111,10 +1068,10 @@ extern "C" int fdh_debug_tail_state(unsigned int* out4) {
 
 // (introspection, tests: 1 = the short chain behind the landing decoder is in use on this device, 0 = the long one)
 extern "C" int fdh_debug_tail_mode(void) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+    DeviceState* ds = nullptr;
+    if (current_device(&ds) != hipSuccess) return -1;
     std::lock_guard<std::mutex> lock(g_dev_mutex);
-    return g_tail[dev].short_chain ? 1 : 0;
+    return ds->tail.short_chain ? 1 : 0;
 }
 
 // Statuses of a batch whose streams are taken up at resume points: PENDING_RESUME where there is one, PENDING elsewhere.
@@ -1134,12 +1091,221 @@ __global__ __launch_bounds__(256) void resume_prepare_kernel(uint32_t* status, c
     }
 }
 
-// `resume_io` (nullable, n records of 16 bytes): where a stream that ends InsufficientInput / OutputTooLarge can be
-// taken up again; with FDH_FLAG_RESUME_IN (0x8000) also where each stream is to be taken up NOW (all zero: at its
-// first byte) -- the slot then holds the output up to that point, and only the two general kernels run.
-// inflate_seg3.hip (a translation unit of its own: it builds in a fraction of the time of this one)
-int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);
+// The two exact kernels, one behind the other: the small-table one leaves what only the 12-bit one can take.
+static hipError_t launch_exact(const fdh::InflateBatchArgs& a, unsigned blocks, hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    if (!(a.flags & FDH_FLAG_NO_FAST_GENERAL)) e = launch(fdh::inflate_general_fast_kernel, blocks, fdh::kWave, stream, a);
+    if (e == hipSuccess) e = launch(fdh::inflate_general_kernel, blocks, fdh::kWave, stream, a);
+    return e;
+}
 
+// stream_order_kernel: the hand-out order of the landing / interval kernel, and the streams without the ultra-fast
+// prefix straight to the second list -- in one launch (in no order) or in two (the long ones first).
+static hipError_t launch_order(fdh::SegArgs& sa, const CallScratch& s, bool once, hipStream_t stream) {
+    if (sa.flags & FDH_FLAG_ORDER_ONCE) once = true;
+    if (sa.flags & FDH_FLAG_ORDER_TWICE) once = false;
+    for (uint32_t second = once ? 2 : 0; second < (once ? 3u : 2u); second++) {
+        const hipError_t e = launch(fdh::stream_order_kernel, (unsigned)((sa.n + 1023) / 1024), 1024, stream, sa.in, sa.in_off, (uint32_t)sa.n,
+                                    s.order(), s.order_counters(), sa.canon_hdr, sa.status, fdh::kPending, sa.list2, second);
+        if (e != hipSuccess) return e;
+    }
+    sa.order = s.order();
+    sa.order_counts = s.order_counters();
+    return hipSuccess;
+}
+
+// The landing decoder: what it does not take (short streams, a chain that did not land) is listed for the interval kernel.
+static hipError_t launch_landing(fdh::SegArgs& sa, const CallScratch& s, unsigned blocks, hipStream_t stream) {
+    sa.list = s.landing_list();
+    const hipError_t e = (hipError_t)fdh_launch_seg3(sa, blocks, stream);
+    sa.src_list = s.landing_list();
+    sa.list = s.first_list();
+    return e;
+}
+
+// Streams taken up at resume points (FDH_FLAG_RESUME_IN).  The LZ-window kernel takes every stream as far as it can
+// (from its resume point), the 12-bit kernel does the rest: its tiles know where the reference's table steps start, so
+// the serial decoder can take over at its check points whatever the data -- the small-table kernel's cannot.  Scratch:
+// a list of all streams for the persistent wavefronts of the first kernel, its items, and the records the two kernels
+// pass between them (the caller's array keeps what came in until the final result of a stream overwrites it).
+static hipError_t chain_resume_in(fdh::InflateBatchArgs a, DeviceState& ds, hipStream_t stream) {
+    const int cus = device_view(ds, false).cus;
+    CallScratch s(CallScratch::ResumeIn{}, a.n, cus, stream);
+    hipError_t e = s.alloc(ds);
+    if (e != hipSuccess) return e;
+    a.lz_counter = s.lz_counter();
+    a.list = s.first_list();  // [0] = count, [4..] = ids (its hand-out words [2], [3] are not used by this kernel)
+    a.lz_ck = s.lz_items();
+    a.resume = s.resume();
+    a.only_pending = 1;
+    e = launch(resume_prepare_kernel, (unsigned)((a.n + 255) / 256), 256, stream, a.status, a.resume_out, a.resume, s.base(), a.n);
+    if (e == hipSuccess && !(a.flags & FDH_FLAG_NO_LZ)) e = launch(fdh::inflate_lz_kernel, lz_blocks(a.n, cus), fdh::kWave, stream, a);
+    a.list = nullptr;
+    if (e == hipSuccess) e = launch(fdh::inflate_general_kernel, (unsigned)a.n, fdh::kWave, stream, a);
+    return e;
+}
+
+// No lists (FDH_FLAG_NO_SEGMENTS: `sa` null; or the scratch could not be had): every kernel scans the status words.
+// The segment kernel or, on request, the stream-per-lane kernel (it finishes the canonical streams that decode cleanly);
+// then the canon kernel and the exact kernels, a workgroup per stream.
+static hipError_t chain_no_lists(fdh::InflateBatchArgs a, const fdh::SegArgs* sa, DeviceState& ds, hipStream_t stream) {
+    const uint64_t n = a.n;
+    hipError_t e = hipSuccess;
+    bool first = false;
+    if (sa) {
+        e = launch(fdh::inflate_segments_kernel, segment_blocks(n, 0, false), fdh::kSegWaves * fdh::kWave, stream, *sa);
+        first = true;
+    } else if ((a.flags & FDH_FLAG_FORCE_LANES) || (n >= fdh::kLaneMinStreams && !(a.flags & FDH_FLAG_NO_LANES))) {
+        const fdh::CanonTables* canon = device_view(ds, false).canon;
+        if (!canon) return hipErrorNotInitialized;
+        fdh::LaneArgs la{a.in, a.in_off, a.out, a.out_off, a.out_len, a.status, a.adler, n, a.flags,
+                         canon->lit, canon->dist, canon->hdr, fdh::kCanonBits, fdh::kPending};
+        e = launch(fdh::inflate_lanes_kernel, (unsigned)((n + fdh::kLaneBlock - 1) / fdh::kLaneBlock), fdh::kLaneBlock, stream, la);
+        first = true;
+    }
+    if (e != hipSuccess) return e;
+    if (first) {
+        a.only_pending = 1;
+        if (a.flags & FDH_FLAG_FIRST_ONLY) return hipSuccess;  // debug: first kernel only (PENDING streams stay undecoded)
+    }
+    e = launch(fdh::inflate_canon_kernel, canon_blocks(n), fdh::kCanonWaves * fdh::kWave, stream, a);
+    if (e != hipSuccess) return e;
+    a.only_pending = 1;
+    return launch_exact(a, (unsigned)n, stream);
+}
+
+// One stream, with lists: [order] [landing decoder] interval kernel, segment kernel, canon kernel, LZ-window kernel,
+// the exact kernels -- each on what the one in front listed as left over.
+static hipError_t chain_one_stream(fdh::InflateBatchArgs a, fdh::SegArgs sa, const ChainPlan& p, int cus, const CallScratch& s, hipStream_t stream) {
+    const uint64_t n = a.n;
+    const uint32_t flags = a.flags;
+    hipError_t e;
+    if (p.seg2) {  // interval kernel first; what it leaves goes through the segment kernel
+        sa.ckpt = s.checkpoints();
+        sa.list2 = s.second_list();
+        if (p.ordered) {
+            e = launch_order(sa, s, false, stream);
+            if (e != hipSuccess) return e;
+        }
+        if (p.seg3) {
+            e = launch_landing(sa, s, s2_blocks(n, cus), stream);
+            if (e != hipSuccess || (flags & FDH_FLAG_LANDING_ONLY)) return e;  // (debug: the landing decoder only)
+        }
+        e = launch(fdh::inflate_seg2_kernel, s2_blocks(n, cus), fdh::kS2Waves * fdh::kWave, stream, sa);
+        if (e != hipSuccess) return e;
+        sa.src_list = s.first_list();
+        sa.list = s.second_list();
+        sa.list2 = nullptr;
+        sa.order = nullptr;
+        if (flags & FDH_FLAG_INTERVALS_ONLY) return hipSuccess;  // debug: the interval kernel only
+    }
+    e = launch(fdh::inflate_segments_kernel, segment_blocks(n, cus, true), fdh::kSegWaves * fdh::kWave, stream, sa);
+    if (e != hipSuccess) return e;
+    a.only_pending = 1;
+    if (flags & FDH_FLAG_FIRST_ONLY) return hipSuccess;  // debug: first kernel only (PENDING streams stay undecoded)
+    a.list = sa.list;
+    a.resume = s.resume();
+    e = launch(fdh::inflate_canon_kernel, canon_blocks(n), fdh::kCanonWaves * fdh::kWave, stream, a);
+    // the kernels behind walk the same list (what the canon kernel finished is no longer PENDING)
+    if (e == hipSuccess && !(flags & FDH_FLAG_NO_LZ)) {
+        a.lz_counter = s.lz_counter();  // (zeroed with the headers)
+        a.lz_ck = s.lz_items();
+        // its leftovers: the list region the kernels in front are done with
+        a.list_out = (sa.list == s.first_list()) ? s.second_list() : s.first_list();
+        e = hipMemsetAsync(a.list_out, 0, 4 * sizeof(uint32_t), stream);
+        if (e == hipSuccess) e = launch(fdh::inflate_lz_kernel, lz_blocks(n, cus), fdh::kWave, stream, a);
+        a.list = a.list_out;
+    }
+    if (e == hipSuccess && (flags & FDH_FLAG_LZ_ONLY)) return hipSuccess;  // debug: what the LZ-window kernel left stays PENDING
+    if (e == hipSuccess) e = launch_exact(a, exact_blocks(n), stream);
+    return e;
+}
+
+// The side stream's share of the two-stream chain: the LZ-window kernel on the second list, which is complete once
+// stream_order_kernel has run, and -- what it leaves depends on nothing the canonical kernels do -- its two exact kernels
+// behind it, off the chain of launches behind the landing decoder (a launch that finds its list empty still costs
+// ~10 us of that chain).  False: nothing has been started on the side stream, or it cannot be joined.
+static bool fork_side(const fdh::InflateBatchArgs& a, int cus, const CallScratch& s, SideFork& fj, hipStream_t side) {
+    if (fj.fork() != hipSuccess) return false;
+    fdh::InflateBatchArgs b = a;
+    b.only_pending = 1;
+    b.flags = a.flags | fdh::kFlagTailReport;  // (its list's count goes to the host's hint, if there is one)
+    b.list = s.second_list();
+    b.list_out = s.lz_left();
+    b.lz_counter = s.lz_counter();  // (zeroed with the headers)
+    b.lz_ck = s.lz_items();
+    b.resume = s.resume();
+    if (launch(fdh::inflate_lz_kernel, lz_blocks(a.n, cus), fdh::kWave, side, b) != hipSuccess) return false;
+    fdh::InflateBatchArgs g = a;
+    g.only_pending = 1;
+    g.resume = s.resume();
+    g.list = s.lz_left();
+    return launch_exact(g, exact_blocks(a.n), side) == hipSuccess && fj.record_join() == hipSuccess;
+}
+
+// Two streams (a large batch, split by stream_order_kernel into the streams with the ultra-fast prefix and the others:
+// two independent lists).  The LZ-window kernel takes the others on the side stream, beside the landing / interval /
+// segment / tile kernels of the canonical ones (round 4 ran the lists back to back: the mix of BASELINE config 5 paid the
+// sum).  Behind the landing decoder the short tail -- the exact kernel alone on what it listed -- or the long one:
+// interval, segment, canon kernel, the join, the exact kernels (TailHint chooses).
+static hipError_t chain_two_streams(fdh::InflateBatchArgs a, fdh::SegArgs sa, const ChainPlan& p, DeviceState& ds, const DeviceView& dv,
+                                    const CallScratch& s, hipStream_t stream) {
+    const uint64_t n = a.n;
+    const uint32_t flags = a.flags;
+    sa.ckpt = s.checkpoints();
+    sa.list2 = s.second_list();
+    hipError_t e = launch_order(sa, s, hint_order_once(ds), stream);
+    if (e != hipSuccess) return e;
+    SideFork fj(stream, dv.side);
+    if (!fork_side(a, dv.cus, s, fj, dv.side)) {  // give up cleanly
+        fj.sync_side_at_exit();
+        return hipErrorUnknown;
+    }
+    sa.list2 = nullptr;  // (nothing more goes on the other list: what the canonical kernels meet and cannot take stays on their own lists)
+    a.only_pending = 1;
+    a.resume = s.resume();
+    if (p.seg3) {
+        e = launch_landing(sa, s, s2_blocks(n, dv.cus), stream);
+        if (e != hipSuccess) return e;
+        bool report = false;
+        bool short_chain = hint_short_chain(ds, &report);
+        if (flags & FDH_FLAG_TAIL_LONG) short_chain = false;
+        if (flags & FDH_FLAG_TAIL_SHORT) short_chain = true;
+        if (short_chain) {
+            a.list = s.landing_list();
+            a.flags = flags | fdh::kFlagTailCounter1 | (report ? fdh::kFlagTailReport : 0u);
+            e = launch(fdh::inflate_general_kernel, (unsigned)std::min<uint64_t>(n, 1024), fdh::kWave, stream, a);
+            const hipError_t ej = fj.join();
+            if (e == hipSuccess) e = ej;
+            if (e != hipSuccess) fj.sync_side_at_exit();
+            return e;
+        }
+        if (report) sa.flags = flags | fdh::kFlagTailReport;
+    }
+    e = launch(fdh::inflate_seg2_kernel, s2_blocks(n, dv.cus), fdh::kS2Waves * fdh::kWave, stream, sa);
+    if (e != hipSuccess) return e;
+    // the segment kernel and the tile decoder on what the interval kernels left, then -- both lists done with their
+    // fast kernels -- the kernels that take whatever is still pending on this one (the other list's ran on the side stream)
+    sa.src_list = s.first_list();
+    sa.list = s.canon_left();
+    sa.order = nullptr;
+    e = launch(fdh::inflate_segments_kernel, segment_blocks(n, dv.cus, true), fdh::kSegWaves * fdh::kWave, stream, sa);
+    a.list = s.canon_left();
+    if (e == hipSuccess) e = launch(fdh::inflate_canon_kernel, canon_blocks(n), fdh::kCanonWaves * fdh::kWave, stream, a);
+    const hipError_t ej = fj.join();
+    if (e == hipSuccess) e = ej;
+    if (e == hipSuccess) e = launch_exact(a, exact_blocks(n), stream);
+    if (e != hipSuccess) fj.sync_side_at_exit();
+    return e;
+}
+
+// The debug and A/B flags under which a call stays on one stream.
+constexpr uint32_t kNoSideStream = FDH_FLAG_NO_LZ | FDH_FLAG_LZ_ONLY | FDH_FLAG_INTERVALS_ONLY | FDH_FLAG_LANDING_ONLY | FDH_FLAG_FIRST_ONLY | FDH_FLAG_NO_OVERLAP;
+
+// Every decode call goes through here: mask the internal bits, build the arguments, pick the chain.
+// `resume_io` (nullable, n records of 16 bytes): where a stream that ends InsufficientInput / OutputTooLarge can be
+// taken up again; with FDH_FLAG_RESUME_IN also where each stream is to be taken up NOW (all zero: at its first
+// byte) -- the slot then holds the output up to that point, and only the LZ-window kernel and the 12-bit kernel run.
 extern "C" int fdh_launch_inflate(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
                                   uint32_t* out_len, uint32_t* status, uint32_t* adler, uint64_t n, uint32_t flags,
                                   void* resume_io, hipStream_t stream) {
@@ -1147,402 +1313,38 @@ extern "C" int fdh_launch_inflate(const uint8_t* in, const uint64_t* in_off, uin
     flags &= ~(fdh::kFlagTailReport | fdh::kFlagTailCounter1);  // (internal)
     fdh::InflateBatchArgs a{in, in_off, out, out_off, out_len, status, adler, n, flags, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                             static_cast<uint4*>(resume_io)};
-    if (resume_io && (flags & 0x8000u)) {
-        // The LZ-window kernel takes every stream as far as it can (from its resume point), the 12-bit kernel does the
-        // rest: its tiles know where the reference's table steps start, so the serial decoder can take over at its
-        // check points whatever the data -- the small-table kernel's cannot.  Scratch: a list of all streams for the
-        // persistent wavefronts of the first kernel, its items, and the records the two kernels pass between them
-        // (the caller's array keeps what came in until the final result of a stream overwrites it).
-        int ordinal = 0, cus = 256;
-        if (hipGetDevice(&ordinal) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ordinal) == hipSuccess && v > 0) cus = v;
-        }
-        const unsigned lblocks = (unsigned)std::min<uint64_t>(n, (uint64_t)FDH_LZ_WAVES_PER_CU * cus);
-        const size_t list_words = ((size_t)n + 8 + 3) & ~(size_t)3;
-        const size_t lzck_bytes = (size_t)lblocks * fdh::kWave * fdh::kLzMaxPhases * sizeof(uint2);
-        uint32_t* scratch = nullptr;
-        hipError_t e = scratch_alloc(reinterpret_cast<void**>(&scratch), list_words * sizeof(uint32_t) + lzck_bytes + (size_t)n * sizeof(uint4), stream);
-        if (e != hipSuccess) return (int)e;
-        a.lz_counter = scratch + 2;
-        a.list = scratch + 4;   // [0] = count, [4..] = ids (its hand-out words [2], [3] are not used by this kernel)
-        a.lz_ck = reinterpret_cast<uint2*>(scratch + list_words);
-        a.resume = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(a.lz_ck) + lzck_bytes);
-        a.only_pending = 1;
-        hipLaunchKernelGGL(resume_prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, status, a.resume_out, a.resume,
-                           scratch, n);
-        if (!(flags & 0x1000u)) hipLaunchKernelGGL(fdh::inflate_lz_kernel, dim3(lblocks), dim3(fdh::kWave), 0, stream, a);
-        a.list = nullptr;
-        hipLaunchKernelGGL(fdh::inflate_general_kernel, dim3((unsigned)n), dim3(fdh::kWave), 0, stream, a);
-        e = hipGetLastError();
-        (void)hipFreeAsync(scratch, stream);
-        return (int)e;
-    }
-    if (resume_io) {  // (same promise for a call that starts every stream at its first byte)
-        const hipError_t e0 = hipMemsetAsync(resume_io, 0, (size_t)n * sizeof(uint4), stream);
-        if (e0 != hipSuccess) return (int)e0;
-    }
-    if (flags & 0x100u) {  // FDH_FLAG_SPANS: scratch of the span decoder, allocated once per device, zero-initialised
-        int ordinal = 0;
-        if (hipGetDevice(&ordinal) == hipSuccess && ordinal >= 0 && ordinal < 64) {
-            std::lock_guard<std::mutex> lock(g_dev_mutex);
-            if (!g_span_pool[ordinal]) {
-                const size_t bytes = ((size_t)fdh::kSpanSlots + (size_t)fdh::kSpanSlots * 2 * fdh::kSpanMaxMatches) * sizeof(uint32_t);
-                uint32_t* p = nullptr;
-                if (hipMalloc(reinterpret_cast<void**>(&p), bytes) == hipSuccess) {
-                    if (hipMemset(p, 0, fdh::kSpanSlots * sizeof(uint32_t)) == hipSuccess && hipDeviceSynchronize() == hipSuccess)
-                        g_span_pool[ordinal] = p;
-                    else (void)hipFree(p);
-                } else {
-                    (void)hipGetLastError();  // no scratch: the general kernel runs without spans
-                }
-            }
-            a.span_pool = g_span_pool[ordinal];
-        }
-    }
-    if (flags & 6u) {  // FDH_FLAG_SERIAL_ONLY (2) / debug: general kernel only, tiles allowed (4)
-        hipLaunchKernelGGL(fdh::inflate_general_kernel, dim3((unsigned)n), dim3(fdh::kWave), 0, stream, a);
-        return (int)hipGetLastError();
-    }
-    hipError_t e;
-    // Canonical streams of useful length: segment-parallel kernel first; what it cannot finish
-    // stays PENDING for the kernels below.
-    if (!(flags & 128u)) {
-        int ordinal = 0;
-        e = hipGetDevice(&ordinal);
-        if (e != hipSuccess) return (int)e;
-        fdh::CanonTables* canon = (ordinal >= 0 && ordinal < 64) ? g_canon_dev[ordinal] : nullptr;
-        if (!canon) return (int)hipErrorNotInitialized;
-        // stream-ordered scratch (no host synchronisation): two compacted lists of leftovers (what the
-        // interval kernel leaves to the segment kernel, what that one leaves to the kernels behind) and
-        // the interval kernel's checkpoints
-        uint32_t* list = nullptr;
-        int cus;
-        {
-            std::lock_guard<std::mutex> lock(g_dev_mutex);
-            if (g_cu_count[ordinal & 63] == 0) {
-                int v = 0;
-                if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, ordinal) != hipSuccess || v <= 0) v = 256;
-                g_cu_count[ordinal & 63] = v;
-            }
-            cus = g_cu_count[ordinal & 63];
-        }
-        const bool seg2 = !(flags & 0x400u);
-        // A large batch is split by stream_order_kernel into the streams with the ultra-fast prefix and the others:
-        // two independent lists.  The LZ-window kernel takes the others on a stream of its own, beside the landing /
-        // interval / segment / tile kernels of the canonical ones, and the two meet again in front of the kernels
-        // that take what is left (round 4 ran the lists back to back: the mix of BASELINE config 5 paid the sum).
-        hipStream_t side = nullptr;
-        if (seg2 && !(flags & (0x1000u | 0x2000u | 0x800u | 0x20000u | 64u | 0x100000u))) {
-            std::lock_guard<std::mutex> lock(g_dev_mutex);
-            if (!g_side_stream[ordinal & 63]) {
-                hipStream_t s2 = nullptr;
-                if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) == hipSuccess) g_side_stream[ordinal & 63] = s2;
-                else (void)hipGetLastError();
-            }
-            side = g_side_stream[ordinal & 63];
-        }
-        const bool seg3 = seg2 && !(flags & 0x10000u);  // the landing decoder in front of the interval decoder
-        const unsigned s2blocks = std::min((unsigned)((n + fdh::kS2Waves - 1) / fdh::kS2Waves), (unsigned)cus);
-        // (+ the hand-out order of the interval kernel when every wavefront gets several streams);
-        // layout: first list | 8 words: counters of stream_order_kernel (4 classes, [4] the LZ-window kernel's hand-out) | second list | order | third list | checkpoints
-        const bool ordered = seg2 && n >= 4ull * s2blocks * fdh::kS2Waves && n <= 0x7FFFFFFFull;
-        const size_t list2_at = (size_t)(n + 4) + 8;
-        const size_t list3_at = list2_at + (size_t)(n + 4) + (ordered ? (size_t)(2 * n) : 0);
-        const bool overlap = ordered && side != nullptr;
-        const size_t list4_at = list3_at + (seg3 ? (size_t)(n + 4) : 0);  // (overlap: what the canonical kernels leave)
-        const size_t list5_at = list4_at + (overlap ? (size_t)(n + 4) : 0);  // (overlap: what the LZ-window kernel leaves)
-        const size_t list_words = list5_at + (overlap ? (size_t)(n + 4) : 0);
-        const size_t ckpt_bytes = seg2 ? (size_t)s2blocks * fdh::kS2Waves * fdh::kS2CkptPerWave * sizeof(uint2) : 0;
-        const unsigned lblocks = (unsigned)std::min<uint64_t>(n, (uint64_t)FDH_LZ_WAVES_PER_CU * cus);  // LZ-window kernel: persistent wavefronts
-        const size_t lzck_bytes = (flags & 0x1000u) ? 0 : (size_t)lblocks * fdh::kWave * fdh::kLzMaxPhases * sizeof(uint2);
-        const size_t resume_bytes = (size_t)n * sizeof(uint4);  // where a kernel leaves a stream for the kernels behind it
-        const size_t words_al = (list_words + 3) & ~(size_t)3;  // (what follows the lists is 16-byte aligned)
-        if (scratch_alloc(reinterpret_cast<void**>(&list), words_al * sizeof(uint32_t) + ckpt_bytes + lzck_bytes + resume_bytes, stream) != hipSuccess) {
-            (void)hipGetLastError();
-            list = nullptr;  // fall back to the status-scan form
-        } else {
-            // the headers of the lists and the counters between them: one fill over the list words is cheaper than three
-            // small ones (a fill is a kernel of its own on the stream)
-            if (seg3 || ordered) {
-                e = hipMemsetAsync(list, 0, words_al * sizeof(uint32_t), stream);
-            } else {
-                e = hipMemsetAsync(list, 0, 4 * sizeof(uint32_t), stream);
-                if (e == hipSuccess) e = hipMemsetAsync(list + (n + 4), 0, 12 * sizeof(uint32_t), stream);  // counters + second header
-            }
-            if (e != hipSuccess) {
-                (void)hipFreeAsync(list, stream);
-                return (int)e;
-            }
-        }
-        fdh::SegArgs sa{in, in_off, out, out_off, out_len, status, adler, n, flags, canon->lit, canon->len4, canon->hdr,
-                        fdh::kCanonBits, fdh::kPending, list, nullptr, nullptr, canon->nl, canon->lit2, nullptr, nullptr};
-        if (list && seg2) {  // interval kernel first; what it leaves goes through the segment kernel
-            sa.ckpt = reinterpret_cast<uint2*>(list + words_al);
-            sa.list2 = list + list2_at;
-            if (ordered) {
-                uint32_t* order = list + list2_at + (n + 4);
-                uint32_t* counters = list + (n + 4);
-                // (the other list's long streams first takes a launch of its own for the short ones: ~12 us of the chain in
-                //  front of the landing decoder, spent in vain while that list is as good as empty -- the LZ-window kernel
-                //  reports its count like the kernel behind the landing decoder does, TailHint)
-                bool once = false;
-                if (side) {
-                    std::lock_guard<std::mutex> lock(g_dev_mutex);
-                    TailHint& h = g_tail[ordinal & 63];
-                    if (h.rep) {
-                        const uint32_t seq = h.rep[3], others = h.rep[2];
-                        if (seq != h.seen_others) {
-                            h.seen_others = seq;
-                            h.order_once = others <= kTailFew;
-                        }
-                        once = h.order_once;
-                    }
-                }
-                if (flags & 0x800000u) once = true;    // FDH_FLAG_ORDER_ONCE
-                if (flags & 0x1000000u) once = false;  // FDH_FLAG_ORDER_TWICE
-                for (uint32_t second = once ? 2 : 0; second < (once ? 3u : 2u); second++)
-                    hipLaunchKernelGGL(fdh::stream_order_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(1024), 0, stream, in, in_off, (uint32_t)n, order,
-                                       counters, canon->hdr, status, fdh::kPending, sa.list2, second);
-                e = hipGetLastError();
-                if (e != hipSuccess) {
-                    (void)hipFreeAsync(list, stream);
-                    return (int)e;
-                }
-                sa.order = order;
-                sa.order_counts = counters;
-            }
-            hipEvent_t ev_join = nullptr;
-            if (overlap) {  // the other list is complete: the LZ-window kernel starts on it now, on its own stream
-                hipEvent_t ev_fork = nullptr;
-                bool forked = hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) == hipSuccess &&
-                              hipEventCreateWithFlags(&ev_join, hipEventDisableTiming) == hipSuccess &&
-                              hipEventRecord(ev_fork, stream) == hipSuccess && hipStreamWaitEvent(side, ev_fork, 0) == hipSuccess;
-                if (forked) {
-                    fdh::InflateBatchArgs b = a;
-                    b.only_pending = 1;
-                    b.flags = flags | fdh::kFlagTailReport;  // (its list's count goes to the host's hint, if there is one)
-                    b.list = list + list2_at;
-                    b.list_out = list + list5_at;
-                    b.lz_counter = list + (n + 4) + 4;  // (a spare word of stream_order_kernel's counters, zeroed above)
-                    b.lz_ck = reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(list) + words_al * sizeof(uint32_t) + ckpt_bytes);
-                    b.resume = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(list) + words_al * sizeof(uint32_t) + ckpt_bytes + lzck_bytes);
-                    hipLaunchKernelGGL(fdh::inflate_lz_kernel, dim3(lblocks), dim3(fdh::kWave), 0, side, b);
-                    forked = hipGetLastError() == hipSuccess;
-                    // (round 6) what the LZ-window kernel leaves depends on nothing the canonical kernels do: its two
-                    // exact kernels follow it on the side stream, off the chain of launches behind the landing decoder
-                    // (a launch that finds its list empty still costs ~10 us of that chain)
-                    fdh::InflateBatchArgs g = a;
-                    g.only_pending = 1;
-                    g.resume = b.resume;
-                    g.list = list + list5_at;
-                    const unsigned gblocks5 = (unsigned)std::min<uint64_t>(n, 4096);
-                    if (forked && !(flags & 0x200u)) {
-                        hipLaunchKernelGGL(fdh::inflate_general_fast_kernel, dim3(gblocks5), dim3(fdh::kWave), 0, side, g);
-                        forked = hipGetLastError() == hipSuccess;
-                    }
-                    if (forked) {
-                        hipLaunchKernelGGL(fdh::inflate_general_kernel, dim3(gblocks5), dim3(fdh::kWave), 0, side, g);
-                        forked = hipGetLastError() == hipSuccess;
-                    }
-                    forked = forked && hipEventRecord(ev_join, side) == hipSuccess;
-                }
-                if (ev_fork) (void)hipEventDestroy(ev_fork);
-                if (!forked) {  // (nothing has been started on the other stream, or it cannot be joined: give up cleanly)
-                    if (ev_join) (void)hipEventDestroy(ev_join);
-                    (void)hipStreamSynchronize(side);
-                    (void)hipFreeAsync(list, stream);
-                    return (int)hipErrorUnknown;
-                }
-                sa.list2 = nullptr;  // (nothing more goes on the other list: what the canonical kernels meet and cannot
-                                     //  take stays on their own lists)
-            }
-            if (seg3) {  // what it does not take (short streams, a chain that did not land) is listed for the interval kernel
-                sa.list = list + list3_at;
-                e = (hipError_t)fdh_launch_seg3(sa, s2blocks, stream);
-                if (e != hipSuccess || (flags & 0x20000u)) {  // (debug: the landing decoder only)
-                    if (ev_join) {
-                        (void)hipStreamWaitEvent(stream, ev_join, 0);
-                        (void)hipEventDestroy(ev_join);
-                    }
-                    (void)hipFreeAsync(list, stream);
-                    return (int)e;
-                }
-                sa.src_list = list + list3_at;
-                sa.list = list;
-            }
-            if (seg3 && overlap) {
-                // how many streams the landing decoder has been leaving over lately (TailHint)
-                bool short_chain = false, report = false;
-                {
-                    std::lock_guard<std::mutex> lock(g_dev_mutex);
-                    TailHint& h = g_tail[ordinal & 63];
-                    if (h.rep) {
-                        report = true;
-                        const uint32_t seq = h.rep[1], left = h.rep[0];
-                        if (seq != h.seen) {  // (a caller that enqueues calls faster than they run sees few reports: the latest one decides)
-                            h.seen = seq;
-                            h.streak = left > kTailFew ? 0 : h.streak + 1;
-                            h.short_chain = left <= kTailFew;
-                        }
-                        short_chain = h.short_chain;
-                    }
-                }
-                if (flags & 0x200000u) short_chain = false;  // FDH_FLAG_TAIL_LONG
-                if (flags & 0x400000u) short_chain = true;   // FDH_FLAG_TAIL_SHORT
-                if (short_chain) {  // the exact kernel alone on what the landing decoder listed, then the join
-                    a.only_pending = 1;
-                    a.resume = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(list) + words_al * sizeof(uint32_t) + ckpt_bytes + lzck_bytes);
-                    a.list = list + list3_at;
-                    a.flags = flags | fdh::kFlagTailCounter1 | (report ? fdh::kFlagTailReport : 0u);
-                    hipLaunchKernelGGL(fdh::inflate_general_kernel, dim3((unsigned)std::min<uint64_t>(n, 1024)), dim3(fdh::kWave), 0, stream, a);
-                    e = hipGetLastError();
-                    a.flags = flags;
-                    a.list = nullptr;
-                    const hipError_t ej = hipStreamWaitEvent(stream, ev_join, 0);
-                    (void)hipEventDestroy(ev_join);
-                    if (e == hipSuccess) e = ej;
-                    if (e != hipSuccess) (void)hipStreamSynchronize(side);  // (the scratch is about to go)
-                    (void)hipFreeAsync(list, stream);
-                    return (int)e;
-                }
-                if (report) sa.flags = flags | fdh::kFlagTailReport;
-            }
-            hipLaunchKernelGGL(fdh::inflate_seg2_kernel, dim3(s2blocks), dim3(fdh::kS2Waves * fdh::kWave), 0, stream, sa);
-            e = hipGetLastError();
-            if (e != hipSuccess) {
-                if (ev_join) {
-                    (void)hipStreamWaitEvent(stream, ev_join, 0);
-                    (void)hipEventDestroy(ev_join);
-                }
-                (void)hipFreeAsync(list, stream);
-                return (int)e;
-            }
-            sa.src_list = list;
-            sa.list = overlap ? list + list4_at : list + list2_at;
-            sa.list2 = nullptr;
-            sa.order = nullptr;
-            if (flags & 0x800u) {  // debug: the interval kernel only
-                (void)hipFreeAsync(list, stream);
-                return 0;
-            }
-            if (overlap) {
-                // the segment kernel and the tile decoder on what the interval kernels left, then -- both lists done
-                // with their fast kernels -- the kernels that take whatever is still pending, list by list
-                const unsigned sblocks2 = std::min((unsigned)((n + fdh::kSegWaves - 1) / fdh::kSegWaves), (unsigned)(2 * cus));
-                hipLaunchKernelGGL(fdh::inflate_segments_kernel, dim3(sblocks2), dim3(fdh::kSegWaves * fdh::kWave), 0, stream, sa);
-                e = hipGetLastError();
-                a.only_pending = 1;
-                a.resume = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(list) + words_al * sizeof(uint32_t) + ckpt_bytes + lzck_bytes);
-                a.list = list + list4_at;
-                if (e == hipSuccess) {
-                    const unsigned cblocks = (unsigned)((n + fdh::kCanonWaves - 1) / fdh::kCanonWaves);
-                    hipLaunchKernelGGL(fdh::inflate_canon_kernel, dim3(cblocks), dim3(fdh::kCanonWaves * fdh::kWave), 0, stream, a);
-                    e = hipGetLastError();
-                }
-                const hipError_t ej = hipStreamWaitEvent(stream, ev_join, 0);
-                (void)hipEventDestroy(ev_join);
-                if (e == hipSuccess) e = ej;
-                const unsigned gblocks = (unsigned)std::min<uint64_t>(n, 4096);
-                if (e == hipSuccess) {  // (the other list's exact kernels ran on the side stream, behind the LZ-window kernel)
-                    a.list = list + list4_at;
-                    if (!(flags & 0x200u)) {
-                        hipLaunchKernelGGL(fdh::inflate_general_fast_kernel, dim3(gblocks), dim3(fdh::kWave), 0, stream, a);
-                        e = hipGetLastError();
-                    }
-                    if (e == hipSuccess) {
-                        hipLaunchKernelGGL(fdh::inflate_general_kernel, dim3(gblocks), dim3(fdh::kWave), 0, stream, a);
-                        e = hipGetLastError();
-                    }
-                }
-                a.list = nullptr;
-                if (e != hipSuccess) (void)hipStreamSynchronize(side);  // (the scratch is about to go)
-                (void)hipFreeAsync(list, stream);
-                return (int)e;
-            }
-        }
-        unsigned sblocks = (unsigned)((n + fdh::kSegWaves - 1) / fdh::kSegWaves);
-        if (list) sblocks = std::min(sblocks, (unsigned)(2 * cus));  // persistent wavefronts: two workgroups (80 KiB of LDS each) per CU
-        hipLaunchKernelGGL(fdh::inflate_segments_kernel, dim3(sblocks), dim3(fdh::kSegWaves * fdh::kWave), 0, stream, sa);
-        e = hipGetLastError();
-        if (e != hipSuccess) {
-            if (list) (void)hipFreeAsync(list, stream);
-            return (int)e;
-        }
-        a.only_pending = 1;
-        if (flags & 64u) {  // debug: first kernel only (PENDING streams stay undecoded)
-            if (list) (void)hipFreeAsync(list, stream);
-            return 0;
-        }
-        if (list) {
-            a.list = sa.list;
-            a.resume = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(list) + words_al * sizeof(uint32_t) + ckpt_bytes + lzck_bytes);
-            unsigned cblocks = (unsigned)((n + fdh::kCanonWaves - 1) / fdh::kCanonWaves);
-            hipLaunchKernelGGL(fdh::inflate_canon_kernel, dim3(cblocks), dim3(fdh::kCanonWaves * fdh::kWave), 0, stream, a);
-            e = hipGetLastError();
-            // the general kernels walk the same list (what the canon kernel finished is no longer PENDING):
-            // a grid-stride loop, so a batch that is all canonical costs two near-empty launches
-            const unsigned gblocks = (unsigned)std::min<uint64_t>(n, 4096);  // persistent workgroups (16 per CU at most)
-            if (e == hipSuccess && !(flags & 0x1000u)) {  // the LZ-window kernel: persistent wavefronts, FDH_LZ_WAVES_PER_CU per CU
-                a.lz_counter = list + (n + 4) + 4;  // (a spare word of stream_order_kernel's counters, zeroed above)
-                a.lz_ck = reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(list) + words_al * sizeof(uint32_t) + ckpt_bytes);
-
-                // its leftovers: the list region the kernels in front are done with
-                a.list_out = (sa.list == list) ? list + list2_at : list;
-                e = hipMemsetAsync(a.list_out, 0, 4 * sizeof(uint32_t), stream);
-                if (e == hipSuccess) {
-                    hipLaunchKernelGGL(fdh::inflate_lz_kernel, dim3(lblocks), dim3(fdh::kWave), 0, stream, a);
-                    e = hipGetLastError();
-                }
-                a.list = a.list_out;
-            }
-            if (e == hipSuccess && (flags & 0x2000u)) {  // debug: what the LZ-window kernel left stays PENDING
-                (void)hipFreeAsync(list, stream);
-                return 0;
-            }
-            if (e == hipSuccess && !(flags & 0x200u)) {
-                hipLaunchKernelGGL(fdh::inflate_general_fast_kernel, dim3(gblocks), dim3(fdh::kWave), 0, stream, a);
-                e = hipGetLastError();
-            }
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(fdh::inflate_general_kernel, dim3(gblocks), dim3(fdh::kWave), 0, stream, a);
-                e = hipGetLastError();
-            }
-            a.list = nullptr;
-            (void)hipFreeAsync(list, stream);
-            return (int)e;
-        }
-    }
-    // Dense batches first go through the stream-per-lane kernel; it finishes the canonical
-    // streams that decode cleanly and leaves everything else PENDING.
-    const bool lanes = (flags & 16u) || (n >= fdh::kLaneMinStreams && !(flags & 32u));
-    if (lanes && a.only_pending == 0) {
-        int ordinal = 0;
-        e = hipGetDevice(&ordinal);
-        if (e != hipSuccess) return (int)e;
-        fdh::CanonTables* canon = (ordinal >= 0 && ordinal < 64) ? g_canon_dev[ordinal] : nullptr;
-        if (!canon) return (int)hipErrorNotInitialized;
-        fdh::LaneArgs la{in, in_off, out, out_off, out_len, status, adler, n, flags,
-                         canon->lit, canon->dist, canon->hdr, fdh::kCanonBits, fdh::kPending};
-        unsigned lblocks = (unsigned)((n + fdh::kLaneBlock - 1) / fdh::kLaneBlock);
-        hipLaunchKernelGGL(fdh::inflate_lanes_kernel, dim3(lblocks), dim3(fdh::kLaneBlock), 0, stream, la);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        a.only_pending = 1;
-        if (flags & 64u) return 0;  // debug: lane kernel only (PENDING streams stay undecoded)
-    }
-    unsigned blocks = (unsigned)((n + fdh::kCanonWaves - 1) / fdh::kCanonWaves);
-    hipLaunchKernelGGL(fdh::inflate_canon_kernel, dim3(blocks), dim3(fdh::kCanonWaves * fdh::kWave), 0, stream, a);
-    e = hipGetLastError();
+    DeviceState* ds = nullptr;
+    hipError_t e = current_device(&ds);
     if (e != hipSuccess) return (int)e;
-    a.only_pending = 1;
-    if (!(flags & 0x200u)) {
-        hipLaunchKernelGGL(fdh::inflate_general_fast_kernel, dim3((unsigned)n), dim3(fdh::kWave), 0, stream, a);
-        e = hipGetLastError();
+    if (resume_io && (flags & FDH_FLAG_RESUME_IN)) return (int)chain_resume_in(a, *ds, stream);
+    if (resume_io) {  // (same promise for a call that starts every stream at its first byte)
+        e = hipMemsetAsync(resume_io, 0, (size_t)n * sizeof(uint4), stream);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL(fdh::inflate_general_kernel, dim3((unsigned)n), dim3(fdh::kWave), 0, stream, a);
-    return (int)hipGetLastError();
+    if (flags & FDH_FLAG_SPANS) a.span_pool = span_pool(*ds);
+    if (flags & (FDH_FLAG_SERIAL_ONLY | FDH_FLAG_GENERAL_ONLY))  // debug: the 12-bit kernel only (GENERAL_ONLY: tiles allowed)
+        return (int)launch(fdh::inflate_general_kernel, (unsigned)n, fdh::kWave, stream, a);
+    if (flags & FDH_FLAG_NO_SEGMENTS) return (int)chain_no_lists(a, nullptr, *ds, stream);
+    // Canonical streams of useful length: the segment-parallel kernels first; what they cannot finish stays PENDING
+    // for the kernels behind.
+    ChainPlan p;
+    p.seg2 = !(flags & FDH_FLAG_NO_INTERVALS);
+    const DeviceView dv = device_view(*ds, p.seg2 && !(flags & kNoSideStream));
+    if (!dv.canon) return (int)hipErrorNotInitialized;
+    p.seg3 = p.seg2 && !(flags & FDH_FLAG_NO_LANDING);
+    p.ordered = p.seg2 && n >= 4ull * s2_blocks(n, dv.cus) * fdh::kS2Waves && n <= 0x7FFFFFFFull;
+    p.overlap = p.ordered && dv.side != nullptr;
+    fdh::SegArgs sa{in, in_off, out, out_off, out_len, status, adler, n, flags, dv.canon->lit, dv.canon->len4, dv.canon->hdr,
+                    fdh::kCanonBits, fdh::kPending, nullptr, nullptr, nullptr, dv.canon->nl, dv.canon->lit2, nullptr, nullptr};
+    CallScratch s(n, flags, dv.cus, p, stream);
+    if (s.alloc(*ds) != hipSuccess) {  // fall back to the status-scan form
+        (void)hipGetLastError();
+        return (int)chain_no_lists(a, &sa, *ds, stream);
+    }
+    e = s.clear_headers(p.seg3 || p.ordered);
+    if (e != hipSuccess) return (int)e;
+    sa.list = s.first_list();
+    return (int)(p.overlap ? chain_two_streams(a, sa, p, *ds, dv, s, stream) : chain_one_stream(a, sa, p, dv.cus, s, stream));
 }
 
 extern "C" int fdh_launch_build_tables_debug(const uint8_t* code_lengths, uint32_t hlit, uint32_t* litlen,

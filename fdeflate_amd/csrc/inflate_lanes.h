@@ -278,7 +278,7 @@ __device__ __forceinline__ void lanes_decode(const LaneArgs& a, LaneLds& L) {
         if ((uint64_t)tb * 8 + 32 <= in_bits) {
             uint32_t stored = ((uint32_t)in[tb] << 24) | ((uint32_t)in[tb + 1] << 16) | ((uint32_t)in[tb + 2] << 8) |
                               (uint32_t)in[tb + 3];
-            if (stored == adler || (a.flags & 1u)) {
+            if (stored == adler || (a.flags & FDH_FLAG_IGNORE_ADLER32)) {
                 status = ST_OK;
                 a.out_len[sid] = opos + acc_n;
                 if (a.adler) a.adler[sid] = adler;

@@ -1115,7 +1115,7 @@ __device__ __forceinline__ void seg2_write(const SegArgs& a, const uint32_t* lit
         // src/decompress.rs:306-326: byte boundary, then the big-endian Adler-32
         const uint32_t stored = ((uint32_t)in[tb] << 24) | ((uint32_t)in[tb + 1] << 16) | ((uint32_t)in[tb + 2] << 8) |
                                 (uint32_t)in[tb + 3];
-        if (stored == adler || (a.flags & 1u)) {
+        if (stored == adler || (a.flags & FDH_FLAG_IGNORE_ADLER32)) {
             a.status[sid] = ST_OK;
             a.out_len[sid] = total;
             if (a.adler) a.adler[sid] = adler;

@@ -158,7 +158,7 @@ __device__ __forceinline__ bool seg3_plan(const SegArgs& a, const uint32_t* lit,
     // (uniform) the lean writer takes the stream: 16-B aligned slot, not within an input image of the end of the batch
     // buffer.  Known here, because the counting pass may then merge up to kS3Repeat run tokens into a chain (the
     // general writer: kS2Repeat) and mark the chains that follow a chain.
-    lean = !(a.flags & 0x80000u) && ((reinterpret_cast<uintptr_t>(a.out) + o0) & 15) == 0 && in + ilen + kS3InCap + 128 <= buf_hi;
+    lean = !(a.flags & FDH_FLAG_NO_LEAN_WRITE) && ((reinterpret_cast<uintptr_t>(a.out) + o0) & 15) == 0 && in + ilen + kS3InCap + 128 <= buf_hi;
     const int reps = lean ? kS3Repeat : kS2Repeat;
     const uint32_t pure_flag = lean ? kS3PureFlag : 0u;
     if (ours) {  // canonical prefix: lane k compares stream dword k
@@ -835,7 +835,7 @@ __device__ __forceinline__ bool seg3_write(const SegArgs& a, const uint32_t* lit
         // src/decompress.rs:306-326: byte boundary, then the big-endian Adler-32; Ok / WrongChecksum is the comparison
         // (every token was decoded and the trailer is there: see seg2_write)
         const uint32_t stored = ((uint32_t)in[tb] << 24) | ((uint32_t)in[tb + 1] << 16) | ((uint32_t)in[tb + 2] << 8) | (uint32_t)in[tb + 3];
-        a.status[sid] = (stored == adler || (a.flags & 1u)) ? (uint32_t)ST_OK : (uint32_t)ST_WRONG_CHECKSUM;
+        a.status[sid] = (stored == adler || (a.flags & FDH_FLAG_IGNORE_ADLER32)) ? (uint32_t)ST_OK : (uint32_t)ST_WRONG_CHECKSUM;
         a.out_len[sid] = total;
         if (a.adler) a.adler[sid] = adler;
     }
@@ -851,7 +851,7 @@ __device__ __forceinline__ bool seg3_decode(const SegArgs& a, Seg3Lds& L, uint2*
     bool lean = false;
     const bool planned = seg3_plan(a, L.lit, L.canon, W, ckpt, sid, plan, lean);
     // the writing pass of the interval decoder: output image in the first 5 KiB, input image in the last 3
-    if (planned && (a.flags & 0x40000u)) {  // debug (FDH_FLAG_LANDING_COUNT_ONLY): time the counting pass alone
+    if (planned && (a.flags & FDH_FLAG_LANDING_COUNT_ONLY)) {  // debug: time the counting pass alone
         if ((threadIdx.x & (kWave - 1)) == 0) seg_leave_pending(a, sid);
         return true;
     }

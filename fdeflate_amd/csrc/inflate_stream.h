@@ -1767,7 +1767,7 @@ struct InflaterT {
 #endif
         uint32_t adler = (adler_b << 16) | adler_a;
         if (rc == RC_OK) {
-            r.status = (!(flags & 1u) && stored != adler) ? (uint32_t)ST_WRONG_CHECKSUM : (uint32_t)ST_OK;
+            r.status = (!(flags & FDH_FLAG_IGNORE_ADLER32) && stored != adler) ? (uint32_t)ST_WRONG_CHECKSUM : (uint32_t)ST_OK;
         } else if (rc == RC_STUCK) {
             // src/decompress.rs:1126-1139: not done and no error -> OutputTooLarge if the slot is
             // full, InsufficientInput otherwise.
