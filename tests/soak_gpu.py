@@ -46,7 +46,7 @@ def enc_round(seed):
 def png_round(seed):
     r = np.random.default_rng(seed)
     bpp = int(r.choice([1, 2, 3, 4, 6, 8]))
-    row_bytes = bpp * int(r.integers(1, 400))
+    row_bytes = bpp * int(r.integers(1, 4300 // bpp + 1))   # up to ~4300 bytes for every bpp: both sides of the 4096-byte gate of the pipeline
     pixs, types = [], []
     for k in range(int(r.integers(1, 60))):
         rows = int(r.integers(0, 150))

@@ -742,6 +742,80 @@ def test_png_fused_encoder_slots_too_small(harness):
         _assert_encoder_slots("png rb %d bpp %d" % (rb, bpp), ln[0::2], slots, harness.encoder_guard_faults(h, ooff, ln, empty, fill), want, small, fill)
 
 
+def test_png_fused_encoder_gate_two_gib_of_filtered_bytes(harness):
+    """fdh_png_filter_deflate_ultrafast_batch takes an image only if rows < Q = 2^31 / (row_bytes + 1), rounded down (its
+    filtered offsets are 32-bit, PngSource::divide multiplies them by floor(2^32 / (row_bytes + 1))).  Rows of 4092 bytes
+    (row_bytes + 1 = 4093: a row's start falls on every phase of the encoder's 8-byte chunks), bpp 4, random filter
+    types; one batch holds a small image, one of Q - 1 rows, one of Q rows and another small one, guard slots between them.
+    Q - 1 rows: png_status 0, the stream bit for bit the oracle's filter + ultra-fast encoder in a slot of its length + 5,
+    and decoded back on the GPU it is the filtered image, its length and its Adler-32.  The pixels are zero but for three
+    stretches of noisy rows -- at the start, either side of filtered offset 2^30 and in the last MiB --, so `divide`
+    works on offsets up to 2^31 while host time and stream size stay small.  Q rows: png_status 2, out_len 0, its slot
+    and the guard slots keep their bytes."""
+    import torch
+    import fdeflate_amd as fd
+    _need(12 << 30, "two 2 GiB images, the decoded copy and the comparison")
+    t0 = time.time()
+    rb, bpp, fill = 4092, 4, 0x5A
+    q = (1 << 31) // (rb + 1)
+    assert q * (rb + 1) <= (1 << 31) < (q + 1) * (rb + 1)
+    r = np.random.default_rng(59)
+    rows = q - 1
+    pix = np.zeros((rows, rb), dtype=np.uint8)
+    mid = (1 << 30) // (rb + 1)
+    for lo, hi in ((0, 256), (mid - 128, mid + 128), (rows - 256, rows)):
+        noise = r.integers(0, 256, (hi - lo, rb), dtype=np.uint8)
+        noise[r.random(noise.shape) < 0.4] = 0
+        pix[lo:hi] = noise
+    types = r.integers(0, 5, rows, dtype=np.uint8)
+    est, filt = ob.png_filter(pix.reshape(-1), rb, bpp, types)
+    assert est == 0 and len(filt) == rows * (rb + 1) and (1 << 31) - 2 * (rb + 1) <= len(filt) < (1 << 31)
+    want_big = ob.compress_ultra_fast(filt)
+    t1 = time.time()
+    smalls = []
+    for nr in (70, 3):
+        p = r.integers(0, 256, nr * rb, dtype=np.uint8)
+        t = r.integers(0, 5, nr, dtype=np.uint8)
+        smalls.append((p, t, ob.compress_ultra_fast(ob.png_filter(p, rb, bpp, t)[1])))
+    empty = ob.compress_ultra_fast(b"")
+    # [small, guard, Q - 1 rows, guard, Q rows, guard, small]; the guards are empty images
+    nrows = [70, 0, rows, 0, q, 0, 3]
+    poff = np.cumsum([0] + [n * rb for n in nrows]).astype(np.int64)
+    toff = np.cumsum([0] + nrows).astype(np.int64)
+    d_pix = torch.zeros(int(poff[-1]), dtype=torch.uint8, device="cuda")
+    d_types = torch.zeros(int(toff[-1]), dtype=torch.uint8, device="cuda")     # (the image of Q rows: zeros, type 0)
+    for slot, (p, t) in ((0, smalls[0][:2]), (2, (pix.reshape(-1), types)), (6, smalls[1][:2])):
+        for c in range(0, p.size, 1 << 28):
+            piece = p[c:c + (1 << 28)]
+            d_pix[int(poff[slot]) + c:int(poff[slot]) + c + piece.size] = torch.from_numpy(piece.copy()).cuda()
+        d_types[int(toff[slot]):int(toff[slot]) + t.size] = torch.from_numpy(t).cuda()
+    del pix
+    g = len(empty) + 3
+    caps = [len(smalls[0][2]), g, len(want_big) + 5, g, 4096 + 5, g, len(smalls[1][2]) + 7]
+    ooff = np.zeros(8, dtype=np.int64)
+    ooff[1:] = np.cumsum(caps)
+    d_out = torch.full((int(ooff[-1]),), fill, dtype=torch.uint8, device="cuda")
+    ol, st = fd.png_filter_deflate_ultrafast_batch(d_pix, torch.from_numpy(poff).cuda(), d_types, torch.from_numpy(toff).cuda(),
+                                                   d_out, torch.from_numpy(ooff).cuda(), rb, bpp)
+    torch.cuda.synchronize()
+    t2 = time.time()
+    ln = ol.cpu().numpy().view(np.uint32)
+    h = d_out.cpu().numpy()
+    assert st.cpu().tolist() == [0, 0, 0, 0, 2, 0, 0], st.cpu().tolist()
+    assert not harness.encoder_guard_faults(h, ooff, ln, empty, fill)
+    assert int(ln[4]) == 0 and np.all(h[ooff[4]:ooff[5]] == fill), ("Q rows", int(ln[4]))
+    for i, w in ((0, smalls[0][2]), (2, want_big), (6, smalls[1][2])):
+        assert int(ln[i]) == len(w), (i, int(ln[i]), len(w))
+        assert h[ooff[i]:ooff[i] + len(w)].tobytes() == w, (i, "not bit-exact")
+        assert np.all(h[ooff[i] + len(w):ooff[i + 1]] == fill), (i, "wrote behind its stream")
+    del d_pix, d_types, d_out
+    dst, dl, ad, slots, guards_ok = harness.gpu_inflate_big([want_big], [len(filt)])
+    assert guards_ok and int(dst[0]) == 0 and int(dl[0]) == len(filt) and int(ad[0]) == zlib.adler32(filt)
+    assert slots.head_equals(0, filt)
+    print("Q = %d rows of %d bytes: oracle %.1f s, %d compressed bytes, encode call %.1f s, whole test %.1f s"
+          % (q, rb, t1 - t0, len(want_big), t2 - t1, time.time() - t0))
+
+
 # ------------------------------------------------------------------------------------------
 # 8. encoders: inputs that are too long
 # ------------------------------------------------------------------------------------------
