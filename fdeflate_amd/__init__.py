@@ -11,7 +11,8 @@ from .api import (Decompressor, DecompressionError, OutputTooLarge, STATUS_NAMES
                   stored_size, compress_to_vec, compress_to_vec_rle, compress_to_vec_with_level, compress_bound,
                   deflate_general_batch, MODE_LEVEL2, MODE_LEVEL3,
                   MODE_LEVEL1, MODE_RLE, inflate_batch_multi, init_devices, shutdown_devices, multi_uses_rccl,
-                  png_unfilter_batch, png_filter_batch, inflate_png_batch, png_filter_deflate_ultrafast_batch)
+                  png_unfilter_batch, png_filter_batch, inflate_png_batch, png_filter_deflate_ultrafast_batch,
+                  png_choose_filters_batch, png_encode_ultrafast_batch)
 
 __all__ = [
     "Decompressor", "DecompressionError", "OutputTooLarge", "STATUS_NAMES", "FLAG_IGNORE_ADLER32",
@@ -21,4 +22,5 @@ __all__ = [
     "compress_bound", "deflate_general_batch", "MODE_LEVEL1", "MODE_RLE", "MODE_LEVEL2", "MODE_LEVEL3",
     "compress_to_vec_with_level", "inflate_batch_multi", "init_devices",
     "shutdown_devices", "multi_uses_rccl", "png_unfilter_batch", "png_filter_batch", "inflate_png_batch", "png_filter_deflate_ultrafast_batch",
+    "png_choose_filters_batch", "png_encode_ultrafast_batch",
 ]

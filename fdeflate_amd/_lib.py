@@ -66,6 +66,8 @@ def lib():
     L.fdh_inflate_png_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, u32, vp]
     L.fdh_png_filter_deflate_ultrafast_batch.restype = C.c_int
     L.fdh_png_filter_deflate_ultrafast_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, vp]
+    L.fdh_png_choose_filters_batch.restype = C.c_int
+    L.fdh_png_choose_filters_batch.argtypes = [vp, vp, vp, vp, vp, u64, u32, u32, vp]
     L.fdh_init.restype = C.c_int
     L.fdh_init.argtypes = [u64]
     L.fdh_shutdown.restype = C.c_int
@@ -113,6 +115,7 @@ EXPORTED_SYMBOLS = [
     "fdh_compress_bound", "fdh_deflate_general_batch", "fdh_compress_to_vec", "fdh_compress_to_vec_rle",
     "fdh_compress_to_vec_with_level",
     "fdh_png_unfilter_batch", "fdh_png_filter_batch", "fdh_inflate_png_batch", "fdh_png_filter_deflate_ultrafast_batch",
+    "fdh_png_choose_filters_batch",
     "fdh_init", "fdh_shutdown", "fdh_multi_device_count", "fdh_multi_uses_rccl", "fdh_inflate_batch_multi",
 ]
 

@@ -391,6 +391,44 @@ def png_filter_deflate_ultrafast_batch(pix, pix_off, types, types_off, out, out_
     return out_len, png_status
 
 
+def png_choose_filters_batch(pix, pix_off, types, types_off, row_bytes, bpp, png_status=None):
+    """One filter type per row, chosen from the pixels by the PNG specification's heuristic: the type
+    whose filtered row has the smallest sum of absolute values, the lowest type number on equal sums
+    (fdh_png_choose_filters_batch).  `types` (uint8) receives them at types_off (int64 [n+1], slots of
+    exactly the row counts); returns png_status (0 ok, 2 sizes do not fit: nothing written)."""
+    import torch
+    n = pix_off.numel() - 1
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
+    with _OnDevice(pix, pix_off, types, types_off, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_choose_filters_batch(_ptr(pix), _ptr(pix_off), _ptr(types), _ptr(types_off),
+                                                          _ptr(png_status), n, row_bytes, bpp, C.c_void_p(stream)))
+    return png_status
+
+
+def png_encode_ultrafast_batch(pix, pix_off, out, out_off, row_bytes, bpp, types=None, types_off=None):
+    """Pixels in, IDAT payloads out: png_choose_filters_batch, then png_filter_deflate_ultrafast_batch with
+    the chosen types, both enqueued on torch's current stream -> (out_len, png_status, types).
+    Without `types` the buffer is allocated here and types_off is the running sum of the images' row
+    counts, computed on the device (pix_off[0] and pix_off[n] are read back to size the buffer); with
+    `types`, `types_off` must be given as well.  png_status[i] is the chooser's where that is not 0
+    (the image is then not encoded from chosen types: disregard its slot), else the encoder's."""
+    import torch
+    n = pix_off.numel() - 1
+    if row_bytes <= 0:
+        raise ValueError("row_bytes must be positive")
+    if (types is None) != (types_off is None):
+        raise ValueError("types and types_off are given together or not at all")
+    if types is None:
+        types_off = torch.zeros(n + 1, dtype=torch.int64, device=pix.device)
+        torch.cumsum((pix_off[1:] - pix_off[:-1]) // row_bytes, 0, out=types_off[1:])
+        span = int(pix_off[n] - pix_off[0]) if n else 0
+        types = torch.empty(max(1, span // row_bytes), dtype=torch.uint8, device=pix.device)
+    chosen = png_choose_filters_batch(pix, pix_off, types, types_off, row_bytes, bpp)
+    out_len, png_status = png_filter_deflate_ultrafast_batch(pix, pix_off, types, types_off, out, out_off, row_bytes, bpp)
+    return out_len, torch.where(chosen != 0, chosen, png_status), types
+
+
 def inflate_png_batch(comp, in_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0):
     """Decode n IDAT-style zlib streams and reconstruct their scanlines in one call
     (fdh_inflate_png_batch) -> (out_len, status, adler, png_status)."""

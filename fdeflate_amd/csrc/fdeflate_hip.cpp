@@ -36,6 +36,8 @@ int fdh_launch_png_unfilter(const uint8_t* filt, const uint64_t* filt_off, uint8
 int fdh_launch_png_filter(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
                           uint8_t* filt, const uint64_t* filt_off, uint32_t* status, uint64_t n, uint32_t row_bytes,
                           uint32_t bpp, hipStream_t stream);
+int fdh_launch_png_choose(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off,
+                          uint32_t* status, uint64_t n, uint32_t row_bytes, uint32_t bpp, hipStream_t stream);
 size_t fdh_deflate_general_hash_bytes(int kind);
 size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n);
 size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n);
@@ -222,6 +224,20 @@ int fdh_png_filter_batch(const uint8_t* pix, const uint64_t* pix_off, const uint
     rc = fdh_launch_png_filter(pix, pix_off, types, types_off, filt, filt_off, png_status, n, row_bytes, bpp,
                                static_cast<hipStream_t>(hip_stream));
     if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "filter kernel launch");
+    return FDH_SUCCESS;
+}
+
+int fdh_png_choose_filters_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off,
+                                 uint32_t* png_status, uint64_t n, uint32_t row_bytes, uint32_t bpp, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (row_bytes >= (1u << 25))
+        return fail(FDH_ERR_INVALID_ARGUMENT, "row_bytes must be below 2^25 (a row's filter cost is summed in 32 bits)");
+    int rc = png_args_ok(pix, pix_off, types, types_off, png_status, row_bytes, bpp);
+    if (rc != FDH_SUCCESS) return rc;
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
+    rc = fdh_launch_png_choose(pix, pix_off, types, types_off, png_status, n, row_bytes, bpp,
+                               static_cast<hipStream_t>(hip_stream));
+    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "filter-selection kernel launch");
     return FDH_SUCCESS;
 }
 

@@ -220,6 +220,8 @@ uint64_t fdh_compress_bound(uint64_t len);
  *   fdh_png_unfilter_batch  reconstruction: filt -> pix
  *   fdh_png_filter_batch    filtering with the given per-row types: pix -> filt (types_off[n+1]
  *                           into `types`, one byte per row)
+ *   fdh_png_choose_filters_batch  the per-row types for either of the two filtering calls, chosen
+ *                           from the pixels (below)
  *   fdh_inflate_png_batch   fdh_inflate_batch into `filt` (the slots must be the exact image sizes)
  *                           followed, on the same stream, by the reconstruction into `pix` of every
  *                           stream that decoded to exactly the bytes of its slot
@@ -232,6 +234,22 @@ int fdh_png_filter_batch(const uint8_t *pix, const uint64_t *pix_off, const uint
                          const uint64_t *types_off, uint8_t *filt, const uint64_t *filt_off,
                          uint32_t *png_status, uint64_t n, uint32_t row_bytes, uint32_t bpp,
                          void *hip_stream);
+/* Filter selection: which type each row is filtered with, from the pixels alone -- the heuristic of the
+ * PNG specification (12.8, libpng's default, "minimum sum of absolute differences").  For every row
+ * the five filtered versions are formed (row 0 has zeros above it), every filtered byte v is read as
+ * signed and costs v < 128 ? v : 256 - v (so 128 costs 128), the costs of the row's row_bytes bytes are
+ * summed (the type byte is not counted), and the type with the smallest sum is written to `types`, one
+ * byte per row.  On equal sums the LOWEST type number wins (None < Sub < Up < Average < Paeth); row 0 is
+ * therefore only ever 0, 1 or 3.  `types` / `types_off` are exactly what fdh_png_filter_batch and
+ * fdh_png_filter_deflate_ultrafast_batch take: choosing and encoding are two calls on one stream with no
+ * round trip between them.  No workspace, no host synchronisation.
+ * png_status[i]: 0 ok; 2 the pixel slot is not a whole number of rows, or the types slot
+ * types_off[i+1] - types_off[i] is not exactly the row count: nothing is written for that image.  (1 does
+ * not occur.)  Bytes outside the types slots are never written.  row_bytes == 0, row_bytes >= 2^25 (the
+ * sums are 32 bits wide) or a bpp outside the list: FDH_ERR_INVALID_ARGUMENT. */
+int fdh_png_choose_filters_batch(const uint8_t *pix, const uint64_t *pix_off, uint8_t *types,
+                                 const uint64_t *types_off, uint32_t *png_status, uint64_t n,
+                                 uint32_t row_bytes, uint32_t bpp, void *hip_stream);
 /* Filtering fused into the ultra-fast encoder: pixel rows in (`pix`, rows_i x row_bytes), one filter
  * type per row in `types`, out the zlib stream compress_to_vec_ultra_fast(filtered image) -- what an
  * IDAT holds.  The filtered bytes exist only in registers (no intermediate buffer).  Slots of at

@@ -106,6 +106,9 @@ extern "C" {
                                                   types_off: *const u64, out: *mut u8, out_off: *const u64,
                                                   out_len: *mut u32, png_status: *mut u32, n: u64, row_bytes: u32,
                                                   bpp: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn fdh_png_choose_filters_batch(pix: *const u8, pix_off: *const u64, types: *mut u8, types_off: *const u64,
+                                        png_status: *mut u32, n: u64, row_bytes: u32, bpp: u32,
+                                        hip_stream: *mut c_void) -> c_int;
     pub fn fdh_inflate_png_batch(input: *const u8, in_off: *const u64, filt: *mut u8, filt_off: *const u64,
                                  out_len: *mut u32, status: *mut u32, adler: *mut u32, pix: *mut u8,
                                  pix_off: *const u64, png_status: *mut u32, n: u64, flags: u32, row_bytes: u32,
