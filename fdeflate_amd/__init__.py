@@ -12,7 +12,10 @@ from .api import (Decompressor, DecompressionError, OutputTooLarge, STATUS_NAMES
                   deflate_general_batch, MODE_LEVEL2, MODE_LEVEL3,
                   MODE_LEVEL1, MODE_RLE, inflate_batch_multi, init_devices, shutdown_devices, multi_uses_rccl,
                   png_unfilter_batch, png_filter_batch, inflate_png_batch, png_filter_deflate_ultrafast_batch,
-                  png_choose_filters_batch, png_encode_ultrafast_batch)
+                  png_choose_filters_batch, png_encode_ultrafast_batch,
+                  crc32_batch, png_file_bound, png_geometry, png_frame_batch, png_encode_files_batch, png_scan_files_batch,
+                  png_info_fields, png_gather_idat_batch, png_decode_files_batch, PNG_FILE_PREFIX, PNG_FILE_SUFFIX,
+                  PNG_FLAG_IGNORE_CRC, PNG_SCAN_STATUS_NAMES, PNG_OTHER_GEOMETRY, PNG_COMP_SLOT_TOO_SMALL)
 
 __all__ = [
     "Decompressor", "DecompressionError", "OutputTooLarge", "STATUS_NAMES", "FLAG_IGNORE_ADLER32",
@@ -23,4 +26,7 @@ __all__ = [
     "compress_to_vec_with_level", "inflate_batch_multi", "init_devices",
     "shutdown_devices", "multi_uses_rccl", "png_unfilter_batch", "png_filter_batch", "inflate_png_batch", "png_filter_deflate_ultrafast_batch",
     "png_choose_filters_batch", "png_encode_ultrafast_batch",
+    "crc32_batch", "png_file_bound", "png_geometry", "png_frame_batch", "png_encode_files_batch", "png_scan_files_batch",
+    "png_info_fields", "png_gather_idat_batch", "png_decode_files_batch", "PNG_FILE_PREFIX", "PNG_FILE_SUFFIX",
+    "PNG_FLAG_IGNORE_CRC", "PNG_SCAN_STATUS_NAMES", "PNG_OTHER_GEOMETRY", "PNG_COMP_SLOT_TOO_SMALL",
 ]

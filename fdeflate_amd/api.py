@@ -446,6 +446,175 @@ def inflate_png_batch(comp, in_off, filt, filt_off, pix, pix_off, row_bytes, bpp
     return out_len, status, adler, png_status
 
 
+# ------------------------------------------------------------------------------------------
+# PNG files: CRC-32, framing, container scan, IDAT gather
+# ------------------------------------------------------------------------------------------
+
+PNG_FILE_PREFIX = 41   # signature 8 + IHDR chunk 25 + the IDAT's length and type 8
+PNG_FILE_SUFFIX = 16   # the IDAT's CRC 4 + IEND chunk 12
+PNG_FLAG_IGNORE_CRC = 1
+# info.status of png_scan_files_batch; png_status 7 / 8 of png_gather_idat_batch
+PNG_SCAN_STATUS_NAMES = ["Ok", "NoSignature", "Truncated", "BadIhdr", "Interlaced", "ChunkStructure", "CrcMismatch"]
+PNG_OTHER_GEOMETRY = 7
+PNG_COMP_SLOT_TOO_SMALL = 8
+# fdh_png_info as eight int32 words: status, width, height, depth | colour << 8 | interlace << 16, idat_bytes,
+# idat_chunks, first_idat, chunks
+PNG_INFO_WORDS = 8
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+_PNG_DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
+
+
+def png_file_bound(rows, row_bytes):
+    """A file slot that always suffices for png_encode_files_batch: ultrafast_bound(rows * (row_bytes + 1)) + 57."""
+    return int(_lib.lib().fdh_png_file_bound(int(rows), int(row_bytes)))
+
+
+def png_geometry(width, bit_depth, colour_type):
+    """(row_bytes, bpp) of the packed scanlines of a PNG image: row_bytes = ceil(width * channels * depth / 8),
+    bpp = max(1, channels * depth / 8) -- always one of 1, 2, 3, 4, 6, 8.  ValueError for a pair that is not one of
+    the specification's fifteen."""
+    if colour_type not in _PNG_DEPTHS or bit_depth not in _PNG_DEPTHS[colour_type]:
+        raise ValueError("bit depth %r / colour type %r is not one of the PNG specification's fifteen pairs" % (bit_depth, colour_type))
+    if not 0 < width < (1 << 31):
+        raise ValueError("width must be 1 .. 2^31-1")
+    bits = _PNG_CHANNELS[colour_type] * bit_depth
+    return (width * bits + 7) // 8, max(1, bits // 8)
+
+
+def crc32_batch(data, off, length=None, seed=None, crc=None, status=None):
+    """CRC-32 (PNG / zlib) of n ranges of `data` (fdh_crc32_batch): range i starts at off[i] (int64 [n+1]) and is
+    length[i] bytes long (int32, e.g. an encoder's out_len), or the whole slot without `length`; seed[i] (int32) is the
+    CRC of what came before.  -> (crc, status), int32 [n] (bit patterns of the unsigned values); status 2 and crc 0
+    where length[i] exceeds the slot or is 0xFFFFFFFF.  Enqueued on torch's current stream."""
+    import torch
+    n = off.numel() - 1
+    if crc is None:
+        crc = torch.empty(n, dtype=torch.int32, device=data.device)
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=data.device)
+    with _OnDevice(data, off, length, seed, crc, status) as stream:
+        _lib.check(_lib.lib().fdh_crc32_batch(_ptr(data), _ptr(off), _ptr(length), _ptr(seed), _ptr(crc), _ptr(status), n,
+                                             C.c_void_p(stream)))
+    return crc, status
+
+
+def png_frame_batch(file, file_off, idat_len, height, width, bit_depth, colour_type, file_len=None, png_status=None):
+    """Signature, IHDR and the IDAT's head in front of the zlib streams that lie PNG_FILE_PREFIX bytes into their file
+    slots, the IDAT's CRC and IEND behind them (fdh_png_frame_batch) -> (file_len, png_status)."""
+    import torch
+    n = file_off.numel() - 1
+    if file_len is None:
+        file_len = torch.empty(n, dtype=torch.int32, device=file.device)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
+    with _OnDevice(file, file_off, idat_len, height, file_len, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_frame_batch(_ptr(file), _ptr(file_off), _ptr(idat_len), _ptr(height), _ptr(file_len),
+                                                 _ptr(png_status), n, width, bit_depth, colour_type, C.c_void_p(stream)))
+    return file_len, png_status
+
+
+def png_encode_files_batch(pix, pix_off, file, file_off, width, bit_depth, colour_type):
+    """Pixels in, PNG files out, on torch's current stream and without a round trip: the rows' filter types chosen
+    (png_choose_filters_batch), filtering + ultra-fast encode to file_off + 41 (png_filter_deflate_ultrafast_batch), the
+    framing around the streams (png_frame_batch).  Image i is pix[pix_off[i] .. pix_off[i+1]), whole packed scanlines of
+    the given geometry; its file goes to the slot file[file_off[i] .. file_off[i+1]) -- png_file_bound(rows, row_bytes)
+    always suffices.  -> (file_len, png_status, types) -- `types` holds the chosen filter types, one per row, the
+    images' back to back --; png_status[i] is the encoder's where that is not 0, else the
+    framing's (2: the file does not fit its slot -- file_len[i] = 0).
+    The encoders take ONE offsets array, so the encoder's slot for image i reaches 41 bytes into slot i + 1 (the last one
+    ends 16 bytes in front of its slot's end): the bytes that image i + 1's own prefix is written to afterwards.  A stream
+    that does not fit its file slot can therefore leave bytes in the first 41 of the next slot; they stay there only if
+    that next image fails as well."""
+    import torch
+    row_bytes, bpp = png_geometry(width, bit_depth, colour_type)
+    n = pix_off.numel() - 1
+    dev = pix.device
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=dev)
+        return e, e.clone(), torch.empty(0, dtype=torch.uint8, device=dev)
+    height = ((pix_off[1:] - pix_off[:-1]) // row_bytes).clamp(max=0xFFFFFFFF).to(torch.int32)   # (bit pattern of the u32)
+    enc_off = file_off + PNG_FILE_PREFIX
+    enc_off[n] = torch.maximum(file_off[n] - PNG_FILE_SUFFIX, enc_off[n - 1])
+    # one type per row; the buffer is sized by what `pix` could hold at most, so nothing is read back
+    types_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum((pix_off[1:] - pix_off[:-1]) // row_bytes, 0, out=types_off[1:])
+    types = torch.empty(max(1, pix.numel() // row_bytes), dtype=torch.uint8, device=dev)
+    idat_len, enc_status, types = png_encode_ultrafast_batch(pix, pix_off, file, enc_off, row_bytes, bpp, types=types,
+                                                             types_off=types_off)
+    file_len, png_status = png_frame_batch(file, file_off, idat_len, height, width, bit_depth, colour_type)
+    return file_len, torch.where(enc_status != 0, enc_status, png_status), types
+
+
+def png_scan_files_batch(file, file_off, file_len=None, info=None, flags=0):
+    """Walks the chunks of n PNG files and verifies every chunk's CRC (fdh_png_scan_files_batch) -> info, int32
+    [n, PNG_INFO_WORDS] on the device (png_info_fields names the columns of a host copy); info[:, 0] is the status."""
+    import torch
+    n = file_off.numel() - 1
+    if info is None:
+        info = torch.empty((n, PNG_INFO_WORDS), dtype=torch.int32, device=file.device)
+    assert info.dtype == torch.int32 and info.numel() == PNG_INFO_WORDS * n
+    with _OnDevice(file, file_off, file_len, info) as stream:
+        _lib.check(_lib.lib().fdh_png_scan_files_batch(_ptr(file), _ptr(file_off), _ptr(file_len), _ptr(info), n, flags,
+                                                      C.c_void_p(stream)))
+    return info
+
+
+def png_info_fields(info):
+    """A host copy of `info` as a dict of int64 numpy arrays named like the fields of fdh_png_info."""
+    w = info.detach().cpu().numpy().reshape(-1, PNG_INFO_WORDS).view("uint32").astype("int64")
+    return {"status": w[:, 0], "width": w[:, 1], "height": w[:, 2], "bit_depth": w[:, 3] & 0xFF,
+            "colour_type": (w[:, 3] >> 8) & 0xFF, "interlace": (w[:, 3] >> 16) & 0xFF, "idat_bytes": w[:, 4],
+            "idat_chunks": w[:, 5], "first_idat": w[:, 6], "chunks": w[:, 7]}
+
+
+def png_gather_idat_batch(file, file_off, info, comp, comp_off, width, bit_depth, colour_type, comp_len=None, png_status=None):
+    """The IDAT bodies of every file one behind the other at comp_off (fdh_png_gather_idat_batch) -> (comp_len,
+    png_status): 0 ok, 3 info says the file is not sound, 7 another geometry than the call's, 8 comp slot too small."""
+    import torch
+    n = file_off.numel() - 1
+    if comp_len is None:
+        comp_len = torch.empty(n, dtype=torch.int32, device=file.device)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
+    with _OnDevice(file, file_off, info, comp, comp_off, comp_len, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_gather_idat_batch(_ptr(file), _ptr(file_off), _ptr(info), _ptr(comp), _ptr(comp_off),
+                                                       _ptr(comp_len), _ptr(png_status), n, width, bit_depth, colour_type,
+                                                       C.c_void_p(stream)))
+    return comp_len, png_status
+
+
+def png_decode_files_batch(file, file_off, width, bit_depth, colour_type, file_len=None, flags=0):
+    """PNG files in, packed scanlines out: png_scan_files_batch, ONE read-back of `info` to size the buffers (exact
+    comp / filtered / pixel slots; empty ones for files that are not sound or not of the call's geometry),
+    png_gather_idat_batch, inflate_png_batch.  `flags`: PNG_FLAG_IGNORE_CRC.
+    -> (pix, pix_off, info, status, png_status): pix uint8 with image i at pix_off[i] .. pix_off[i+1] (height_i rows of
+    row_bytes, the PNG's own packed samples: no palette expansion, no tRNS, no gamma); info as png_scan_files_batch;
+    status the zlib decoder's (of an empty stream for a file that was skipped); png_status the gather's where that is not
+    0 (3, 7), else inflate_png_batch's."""
+    import numpy as np
+    import torch
+    row_bytes, bpp = png_geometry(width, bit_depth, colour_type)
+    n = file_off.numel() - 1
+    dev = file.device
+    info = png_scan_files_batch(file, file_off, file_len, flags=flags)
+    f = png_info_fields(info)                                   # the one read-back
+    good = (f["status"] == 0) & (f["width"] == width) & (f["bit_depth"] == bit_depth) & (f["colour_type"] == colour_type)
+    sizes = np.zeros((3, n + 1), dtype=np.int64)
+    sizes[0, 1:] = np.where(good, f["idat_bytes"], 0)
+    sizes[1, 1:] = np.where(good, f["height"] * (row_bytes + 1), 0)
+    sizes[2, 1:] = np.where(good, f["height"] * row_bytes, 0)
+    offs = torch.from_numpy(np.cumsum(sizes, axis=1)).to(dev)
+    comp_off, filt_off, pix_off = offs[0], offs[1], offs[2]
+    total = offs[:, n].tolist() if n else [0, 0, 0]
+    comp = torch.empty(max(1, total[0]), dtype=torch.uint8, device=dev)
+    filt = torch.empty(max(1, total[1]), dtype=torch.uint8, device=dev)
+    pix = torch.empty(max(1, total[2]), dtype=torch.uint8, device=dev)
+    _, gathered = png_gather_idat_batch(file, file_off, info, comp, comp_off, width, bit_depth, colour_type)
+    _, status, _, png_status = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp,
+                                                 flags=0)
+    return pix[:total[2]], pix_off, info, status, torch.where(gathered != 0, gathered, png_status)
+
+
 def inflate_batch_multi(shards, flags=0, gather=True):
     """fdh_inflate_batch_multi from one process: `shards` = one tuple (comp, in_off, out, out_off) of
     tensors per GPU selected by init_devices(); returns per shard (out_len, status, adler) and, with

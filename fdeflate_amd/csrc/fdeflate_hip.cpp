@@ -38,6 +38,16 @@ int fdh_launch_png_filter(const uint8_t* pix, const uint64_t* pix_off, const uin
                           uint32_t bpp, hipStream_t stream);
 int fdh_launch_png_choose(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off,
                           uint32_t* status, uint64_t n, uint32_t row_bytes, uint32_t bpp, hipStream_t stream);
+int fdh_launch_crc32(const uint8_t* data, const uint64_t* off, const uint32_t* len, const uint32_t* seed, uint32_t* crc,
+                     uint32_t* status, uint64_t n, hipStream_t stream);
+int fdh_launch_png_frame(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height,
+                         uint32_t* file_len, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
+                         uint32_t colour_type, hipStream_t stream);
+int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, void* info, uint64_t n,
+                        int verify_crc, hipStream_t stream);
+int fdh_launch_png_gather(const uint8_t* file, const uint64_t* file_off, const void* info, uint8_t* comp,
+                          const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n, uint32_t width,
+                          uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
 size_t fdh_deflate_general_hash_bytes(int kind);
 size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n);
 size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n);
@@ -272,6 +282,80 @@ int fdh_inflate_png_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* fi
     rc = fdh_launch_png_unfilter(filt, filt_off, pix, pix_off, png_status, status, out_len, n, row_bytes, bpp,
                                  static_cast<hipStream_t>(hip_stream));
     if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "unfilter kernel launch");
+    return FDH_SUCCESS;
+}
+
+// ---- PNG files: CRC-32, framing, container scan, IDAT gather (png_file.hip) ----
+int fdh_crc32_batch(const uint8_t* data, const uint64_t* off, const uint32_t* len, const uint32_t* seed, uint32_t* crc,
+                    uint32_t* status, uint64_t n, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (!off || !crc || !status) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many ranges in one call (max 2^31-1)");
+    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    int rc = fdh_launch_crc32(data, off, len, seed, crc, status, n, static_cast<hipStream_t>(hip_stream));
+    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "CRC-32 kernel launch");
+    return FDH_SUCCESS;
+}
+
+uint64_t fdh_png_file_bound(uint64_t rows, uint64_t row_bytes) {
+    return fdh_ultrafast_bound(rows * (row_bytes + 1)) + FDH_PNG_FILE_PREFIX + FDH_PNG_FILE_SUFFIX;
+}
+
+// the fifteen depth / colour-type pairs of the PNG specification (11.2.2, table 11.1)
+static bool png_pair_ok(uint32_t depth, uint32_t colour) {
+    const bool low = depth == 1 || depth == 2 || depth == 4;
+    if (colour == 0) return low || depth == 8 || depth == 16;
+    if (colour == 3) return low || depth == 8;
+    return (colour == 2 || colour == 4 || colour == 6) && (depth == 8 || depth == 16);
+}
+
+static int png_geometry_ok(uint32_t width, uint32_t bit_depth, uint32_t colour_type) {
+    if (width == 0 || width > 0x7FFFFFFFu) return fail(FDH_ERR_INVALID_ARGUMENT, "width must be 1 .. 2^31-1");
+    if (!png_pair_ok(bit_depth, colour_type))
+        return fail(FDH_ERR_INVALID_ARGUMENT, "bit depth / colour type is not one of the PNG specification's fifteen pairs");
+    return FDH_SUCCESS;
+}
+
+int fdh_png_frame_batch(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height,
+                        uint32_t* file_len, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
+                        uint32_t colour_type, void* hip_stream) {
+    int rc = png_geometry_ok(width, bit_depth, colour_type);
+    if (rc != FDH_SUCCESS) return rc;
+    if (n == 0) return FDH_SUCCESS;
+    if (!file || !file_off || !idat_len || !height || !file_len || !png_status) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
+    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    rc = fdh_launch_png_frame(file, file_off, idat_len, height, file_len, png_status, n, width, bit_depth, colour_type,
+                              static_cast<hipStream_t>(hip_stream));
+    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "PNG framing kernel launch");
+    return FDH_SUCCESS;
+}
+
+int fdh_png_scan_files_batch(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, fdh_png_info* info,
+                             uint64_t n, uint32_t flags, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (!file || !file_off || !info) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
+    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    int rc = fdh_launch_png_scan(file, file_off, file_len, info, n, (flags & FDH_PNG_FLAG_IGNORE_CRC) ? 0 : 1,
+                                 static_cast<hipStream_t>(hip_stream));
+    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "PNG scan kernel launch");
+    return FDH_SUCCESS;
+}
+
+int fdh_png_gather_idat_batch(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint8_t* comp,
+                              const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n,
+                              uint32_t width, uint32_t bit_depth, uint32_t colour_type, void* hip_stream) {
+    int rc = png_geometry_ok(width, bit_depth, colour_type);
+    if (rc != FDH_SUCCESS) return rc;
+    if (n == 0) return FDH_SUCCESS;
+    if (!file || !file_off || !info || !comp || !comp_off || !comp_len || !png_status)
+        return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
+    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    rc = fdh_launch_png_gather(file, file_off, info, comp, comp_off, comp_len, png_status, n, width, bit_depth,
+                               colour_type, static_cast<hipStream_t>(hip_stream));
+    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "IDAT gather kernel launch");
     return FDH_SUCCESS;
 }
 

@@ -267,6 +267,93 @@ int fdh_inflate_png_batch(const uint8_t *in, const uint64_t *in_off, uint8_t *fi
                           uint32_t *png_status, uint64_t n, uint32_t flags, uint32_t row_bytes,
                           uint32_t bpp, void *hip_stream);
 
+/* ---- PNG files: CRC-32, the framing around an IDAT stream, the container scan ----------------
+ * Not in the fdeflate crate either (image-rs/image-png frames and parses the container); the format is the
+ * PNG specification's (5.2 signature, 5.3 chunk layout, 5.5 and annex D CRC, 11.2.2 IHDR, 5.6 ordering).
+ * With these the encoders' output becomes files, and files become the decoder's input, with no host work
+ * in between: nothing here allocates, synchronises or reads anything back. */
+
+/*
+ * fdh_crc32_batch -- CRC-32 as in PNG / zlib (polynomial 0xEDB88320, reflected, preset and result
+ * complemented) of `n` byte ranges: crc[i] = crc32(range i, seed[i]) in zlib's sense.
+ *   data, off[n+1]  range i = data[off[i] .. off[i] + L_i), L_i = len ? len[i] : off[i+1] - off[i]; any alignment
+ *   len[n]          nullable; the device-resident out_len an encoder wrote, so that its output is summed
+ *                   with no round trip to the host
+ *   seed[n]         nullable (= 0); the CRC of the bytes that came before (a chunk's type and its body can be
+ *                   two ranges)
+ *   status[n]       0 ok; 2 len[i] exceeds the slot off[i+1] - off[i], len[i] == 0xFFFFFFFF (the encoders'
+ *                   "slot too small"), or the slot is 4 GiB or more: crc[i] = 0
+ * A range of no bytes returns its seed.  Parallel inside a range as well as across ranges: a batch of
+ * fewer than 4096 ranges gives each several wavefronts (one 256 MiB range is an ordinary input), and the
+ * 64 lanes of a wavefront always share its bytes.  No byte of `data` is written.
+ */
+int fdh_crc32_batch(const uint8_t *data, const uint64_t *off, const uint32_t *len,
+                    const uint32_t *seed, uint32_t *crc, uint32_t *status, uint64_t n,
+                    void *hip_stream);
+
+/*
+ * fdh_png_frame_batch -- makes PNG files of zlib streams that are already in place: one IDAT chunk each.
+ * Precondition: the stream of image i lies at file[file_off[i] + FDH_PNG_FILE_PREFIX ..), idat_len[i] bytes
+ * long -- put there by any of the encoders above, called with the offsets shifted by FDH_PNG_FILE_PREFIX
+ * (with idat_len their out_len).  Nothing is copied.  The call writes the 41 bytes in front (signature 8,
+ * IHDR chunk 25 -- width, height[i], bit_depth, colour_type, 0, 0, 0 and its CRC --, the IDAT's length and
+ * type 8) and the 16 bytes behind (the IDAT's CRC over "IDAT" and the stream 4, IEND chunk 12), and sets
+ * file_len[i] = idat_len[i] + 57.
+ * png_status[i]: 0 ok; 2 -- nothing written, file_len[i] = 0 -- when idat_len[i] is 0 or 0xFFFFFFFF (the
+ * image was skipped or overflowed its slot upstream) or above 2^31-1, idat_len[i] + 57 exceeds the slot
+ * file_off[i+1] - file_off[i], or height[i] is 0 or above 2^31-1.  width 0 or above 2^31-1, or a depth /
+ * colour-type pair that is not one of the specification's fifteen: FDH_ERR_INVALID_ARGUMENT.
+ * Bytes outside a slot are never written; those of the slot behind file_len[i] are not specified.
+ * fdh_png_file_bound(rows, row_bytes) = fdh_ultrafast_bound(rows * (row_bytes + 1)) + 57: a slot that
+ * always suffices for the ultra-fast encoder's file.
+ */
+#define FDH_PNG_FILE_PREFIX 41u
+#define FDH_PNG_FILE_SUFFIX 16u
+uint64_t fdh_png_file_bound(uint64_t rows, uint64_t row_bytes);
+int fdh_png_frame_batch(uint8_t *file, const uint64_t *file_off, const uint32_t *idat_len,
+                        const uint32_t *height, uint32_t *file_len, uint32_t *png_status,
+                        uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type,
+                        void *hip_stream);
+
+/*
+ * fdh_png_scan_files_batch -- walks the chunks of `n` PNG files (one lane per file) and then verifies the
+ * CRC of EVERY chunk, ancillary ones included, with the kernel of fdh_crc32_batch (one wavefront per
+ * file, sixteen for a batch of fewer than 4096).  File i = file[file_off[i] .. + file_len[i]); file_len
+ * nullable (= the whole slot; a length above the slot counts as the slot).  Bytes behind IEND are ignored.
+ * info[i].status is the first structural finding in file order, and 6 only if there is none:
+ *   0 ok
+ *   1 no PNG signature
+ *   2 truncated: a chunk runs past the end of the file, or there is no IEND
+ *   3 bad IHDR: not the first chunk, length not 13, a zero dimension (or one above 2^31-1), an illegal
+ *     depth / colour pair, compression or filter method not 0 (or an interlace method above 1)
+ *   4 interlace method 1 (Adam7 is not provided)
+ *   5 chunk structure: no IDAT, IDAT chunks not consecutive, a PLTE after IDAT, an unknown critical chunk
+ *   6 CRC mismatch in some chunk
+ * The walk ends at the first finding; the counts then hold what came before it.  first_idat is the offset
+ * of the first IDAT chunk (its length field) in the file, chunks counts IHDR .. IEND.
+ * FDH_PNG_FLAG_IGNORE_CRC skips the CRC pass (as FDH_FLAG_IGNORE_ADLER32 skips that check).
+ *
+ * fdh_png_gather_idat_batch -- copies the IDAT bodies of file i, in order, to comp[comp_off[i] ..) as one
+ * zlib stream (what fdh_inflate_png_batch takes) and sets comp_len[i] = info[i].idat_bytes; 16 bytes per
+ * lane and step wherever the destination's alignment allows.
+ * png_status[i]: 0 ok; 3 info[i].status != 0 (skipped, as above); 7 the file's width, depth or colour type
+ * is not the call's; 8 the slot comp_off[i+1] - comp_off[i] is too small.  Where it is not 0, comp_len[i] = 0
+ * and nothing is written.  Geometry arguments as for fdh_png_frame_batch.
+ */
+#define FDH_PNG_FLAG_IGNORE_CRC 0x1u
+typedef struct fdh_png_info {
+  uint32_t status, width, height;
+  uint8_t bit_depth, colour_type, interlace, pad;
+  uint32_t idat_bytes, idat_chunks, first_idat, chunks;
+} fdh_png_info; /* 32 bytes */
+int fdh_png_scan_files_batch(const uint8_t *file, const uint64_t *file_off,
+                             const uint32_t *file_len, fdh_png_info *info, uint64_t n,
+                             uint32_t flags, void *hip_stream);
+int fdh_png_gather_idat_batch(const uint8_t *file, const uint64_t *file_off,
+                              const fdh_png_info *info, uint8_t *comp, const uint64_t *comp_off,
+                              uint32_t *comp_len, uint32_t *png_status, uint64_t n, uint32_t width,
+                              uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
+
 /* ---- streaming decoder: `Decompressor` (src/decompress.rs:96-156, 179-342) ----------------
  * A host-side object with exactly `Decompressor::read`'s contract on HOST buffers; every bit of
  * decoding is done by fdh_inflate_batch_resumable on the device (the object keeps a device-resident

@@ -26,6 +26,27 @@ pub struct fdh_resume_point {
     pub adler32: u32,
 }
 
+/// `fdh_png_info`: what `fdh_png_scan_files_batch` found in one PNG file (32 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct fdh_png_info {
+    pub status: u32,
+    pub width: u32,
+    pub height: u32,
+    pub bit_depth: u8,
+    pub colour_type: u8,
+    pub interlace: u8,
+    pub pad: u8,
+    pub idat_bytes: u32,
+    pub idat_chunks: u32,
+    pub first_idat: u32,
+    pub chunks: u32,
+}
+
+pub const FDH_PNG_FILE_PREFIX: u32 = 41;
+pub const FDH_PNG_FILE_SUFFIX: u32 = 16;
+pub const FDH_PNG_FLAG_IGNORE_CRC: u32 = 1;
+
 /// `fdh_shard_t`: the device-resident shard of one GPU for `fdh_inflate_batch_multi`.
 #[repr(C)]
 pub struct fdh_shard_t {
@@ -113,6 +134,18 @@ extern "C" {
                                  out_len: *mut u32, status: *mut u32, adler: *mut u32, pix: *mut u8,
                                  pix_off: *const u64, png_status: *mut u32, n: u64, flags: u32, row_bytes: u32,
                                  bpp: u32, hip_stream: *mut c_void) -> c_int;
+    // PNG files: CRC-32 of byte ranges, the framing around an IDAT stream in place, container scan, IDAT gather
+    pub fn fdh_crc32_batch(data: *const u8, off: *const u64, len: *const u32, seed: *const u32, crc: *mut u32,
+                           status: *mut u32, n: u64, hip_stream: *mut c_void) -> c_int;
+    pub fn fdh_png_file_bound(rows: u64, row_bytes: u64) -> u64;
+    pub fn fdh_png_frame_batch(file: *mut u8, file_off: *const u64, idat_len: *const u32, height: *const u32,
+                               file_len: *mut u32, png_status: *mut u32, n: u64, width: u32, bit_depth: u32,
+                               colour_type: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn fdh_png_scan_files_batch(file: *const u8, file_off: *const u64, file_len: *const u32,
+                                    info: *mut fdh_png_info, n: u64, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn fdh_png_gather_idat_batch(file: *const u8, file_off: *const u64, info: *const fdh_png_info, comp: *mut u8,
+                                     comp_off: *const u64, comp_len: *mut u32, png_status: *mut u32, n: u64,
+                                     width: u32, bit_depth: u32, colour_type: u32, hip_stream: *mut c_void) -> c_int;
 
     pub fn fdh_last_error() -> *const c_char;
     pub fn fdh_device_count() -> c_int;

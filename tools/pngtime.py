@@ -116,3 +116,84 @@ for t in range(5):
 print("rows per chosen type (None, Sub, Up, Average, Paeth): %s" % hist)
 for k, v in total.items():
     print("compressed bytes, %-7s %14d  (%.4f of the pixels, %.4f of chosen)" % (k + ":", v, v / (n * rows * rb), v / total["chosen"]))
+
+# ---- PNG files: CRC-32 of the encoder's output, the framing, the container scan and the IDAT gather ----
+# Interleaved rounds again.  Beside the CRC: a device copy of the encoder's buffer, as this box's memory bandwidth.
+import os
+
+width, depth, colour = rb // bpp, 8, 2
+assert fd.png_geometry(width, depth, colour) == (rb, bpp)
+choose()
+ol, st = encode_chosen(); torch.cuda.synchronize()
+assert int(st.abs().sum()) == 0
+stream_bytes = int(ol.to(torch.int64).sum())
+
+
+def interleaved(variants, rounds=9, calls=5):
+    for _, f in variants:
+        f(); f(); torch.cuda.synchronize()
+    ts = {name: [] for name, _ in variants}
+    for _ in range(rounds):
+        for name, f in variants:
+            ts[name].append(once(f, calls))
+    return ts
+
+
+def show(name, t, nbytes=None):
+    t = sorted(t)
+    rate = "" if nbytes is None else ", %.0f GB/s" % (nbytes / t[len(t) // 2] / 1e6)
+    print("%-44s median %.3f ms, min %.3f, max %.3f over %d rounds%s" % (name, t[len(t) // 2], t[0], t[-1], len(t), rate))
+
+
+big_n = 256 << 20
+big = torch.randint(0, 256, (big_n + 16,), dtype=torch.uint8, device=dev)
+big_off = torch.tensor([0, big_n], dtype=torch.int64, device=dev)
+enc_copy = torch.empty_like(enc)
+ts = interleaved((("device copy of the encoder's buffer", lambda: enc_copy.copy_(enc)),), rounds=5, calls=3)
+show("device copy, %.2f GB read + as much written" % (enc.numel() / 1e9), ts["device copy of the encoder's buffer"], 2 * enc.numel())
+del enc_copy
+for copies in ("1", "8", "32"):
+    os.environ["FDH_CRC_COPIES"] = copies
+    ts = interleaved((("streams", lambda: fd.crc32_batch(enc, o_off, ol)), ("big", lambda: fd.crc32_batch(big, big_off))))
+    show("crc32 of %d streams (%.2f GB), %s table copies" % (n, stream_bytes / 1e9, copies), ts["streams"], stream_bytes)
+    show("crc32 of one 256 MiB range, %s table copies" % copies, ts["big"], big_n)
+os.environ.pop("FDH_CRC_COPIES")
+
+slot = (fd.png_file_bound(rows, rb) + 15) & ~15
+files = torch.empty(n * slot + 64, dtype=torch.uint8, device=dev)
+f_off0 = torch.arange(n + 1, dtype=torch.int64, device=dev) * slot        # the stream starts at +41: not aligned
+f_off7 = f_off0 + 7                                                        # the stream starts at +48: 16-byte aligned
+enc2 = torch.empty(n * bound + 64, dtype=torch.uint8, device=dev)
+o_off41 = o_off + 41
+height = torch.full((n,), rows, dtype=torch.int32, device=dev)
+file_len, st, _ = fd.png_encode_files_batch(pixels, p_off, files, f_off0, width, depth, colour); torch.cuda.synchronize()
+assert int(st.abs().sum()) == 0 and bool((file_len == ol + 57).all())
+variants = (
+    ("pixels -> streams (choose + encode)", choose_and_encode),
+    ("pixels -> files, file_off % 16 == 0", lambda: fd.png_encode_files_batch(pixels, p_off, files, f_off0, width, depth, colour)),
+    ("pixels -> files, file_off % 16 == 7", lambda: fd.png_encode_files_batch(pixels, p_off, files, f_off7, width, depth, colour)),
+    ("framing alone (prefix, IDAT CRC, suffix)", lambda: fd.png_frame_batch(files, f_off0, ol, height, width, depth, colour)),
+    ("encoder, streams at aligned addresses", lambda: fd.png_filter_deflate_ultrafast_batch(pixels, p_off, chosen, t_off, enc2, o_off, rb, bpp)),
+    ("encoder, streams at aligned + 41", lambda: fd.png_filter_deflate_ultrafast_batch(pixels, p_off, chosen, t_off, enc2, o_off41, rb, bpp)),
+)
+ts = interleaved(variants)
+for name, _ in variants:
+    show(name, ts[name])
+
+file_len, st, _ = fd.png_encode_files_batch(pixels, p_off, files, f_off0, width, depth, colour)
+info = fd.png_scan_files_batch(files, f_off0, file_len); torch.cuda.synchronize()
+assert int(info[:, 0].abs().sum()) == 0
+comp_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+torch.cumsum(info[:, 4].to(torch.int64), 0, out=comp_off[1:])
+comp = torch.empty(int(comp_off[n]), dtype=torch.uint8, device=dev)
+pix2 = torch.empty_like(pixels)
+variants = (
+    ("scan of %d files, CRCs verified" % n, lambda: fd.png_scan_files_batch(files, f_off0, file_len, info=info)),
+    ("scan, FDH_PNG_FLAG_IGNORE_CRC", lambda: fd.png_scan_files_batch(files, f_off0, file_len, info=info, flags=fd.PNG_FLAG_IGNORE_CRC)),
+    ("gather of the IDAT bodies", lambda: fd.png_gather_idat_batch(files, f_off0, info, comp, comp_off, width, depth, colour)),
+    ("inflate_png_batch of the gathered streams", lambda: fd.inflate_png_batch(comp, comp_off, filt, r_off, pix2, p_off, rb, bpp)),
+)
+ts = interleaved(variants)
+for name, _ in variants:
+    show(name, ts[name], stream_bytes if "scan of" in name or "gather" in name else None)
+print("files -> pixels give the source back: %s" % bool(torch.equal(pix2, pixels)))
