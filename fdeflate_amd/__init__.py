@@ -15,7 +15,9 @@ from .api import (Decompressor, DecompressionError, OutputTooLarge, STATUS_NAMES
                   png_choose_filters_batch, png_encode_ultrafast_batch,
                   crc32_batch, png_file_bound, png_geometry, png_frame_batch, png_encode_files_batch, png_scan_files_batch,
                   png_info_fields, png_gather_idat_batch, png_decode_files_batch, PNG_FILE_PREFIX, PNG_FILE_SUFFIX,
-                  PNG_FLAG_IGNORE_CRC, PNG_SCAN_STATUS_NAMES, PNG_OTHER_GEOMETRY, PNG_COMP_SLOT_TOO_SMALL)
+                  PNG_FLAG_IGNORE_CRC, PNG_SCAN_STATUS_NAMES, PNG_OTHER_GEOMETRY, PNG_COMP_SLOT_TOO_SMALL,
+                  PNG_INDEX_OUTSIDE_PALETTE, PNG_BAD_PLTE, PNG_BAD_TRNS, png_colour_batch, png_expand_batch,
+                  png_decode_files_rgba_batch)
 
 __all__ = [
     "Decompressor", "DecompressionError", "OutputTooLarge", "STATUS_NAMES", "FLAG_IGNORE_ADLER32",
@@ -29,4 +31,6 @@ __all__ = [
     "crc32_batch", "png_file_bound", "png_geometry", "png_frame_batch", "png_encode_files_batch", "png_scan_files_batch",
     "png_info_fields", "png_gather_idat_batch", "png_decode_files_batch", "PNG_FILE_PREFIX", "PNG_FILE_SUFFIX",
     "PNG_FLAG_IGNORE_CRC", "PNG_SCAN_STATUS_NAMES", "PNG_OTHER_GEOMETRY", "PNG_COMP_SLOT_TOO_SMALL",
+    "PNG_INDEX_OUTSIDE_PALETTE", "PNG_BAD_PLTE", "PNG_BAD_TRNS", "png_colour_batch", "png_expand_batch",
+    "png_decode_files_rgba_batch",
 ]

@@ -457,6 +457,10 @@ PNG_FLAG_IGNORE_CRC = 1
 PNG_SCAN_STATUS_NAMES = ["Ok", "NoSignature", "Truncated", "BadIhdr", "Interlaced", "ChunkStructure", "CrcMismatch"]
 PNG_OTHER_GEOMETRY = 7
 PNG_COMP_SLOT_TOO_SMALL = 8
+# png_status 9 of png_expand_batch, 10 / 11 of png_colour_batch
+PNG_INDEX_OUTSIDE_PALETTE = 9
+PNG_BAD_PLTE = 10
+PNG_BAD_TRNS = 11
 # fdh_png_info as eight int32 words: status, width, height, depth | colour << 8 | interlace << 16, idat_bytes,
 # idat_chunks, first_idat, chunks
 PNG_INFO_WORDS = 8
@@ -583,14 +587,11 @@ def png_gather_idat_batch(file, file_off, info, comp, comp_off, width, bit_depth
     return comp_len, png_status
 
 
-def png_decode_files_batch(file, file_off, width, bit_depth, colour_type, file_len=None, flags=0):
-    """PNG files in, packed scanlines out: png_scan_files_batch, ONE read-back of `info` to size the buffers (exact
-    comp / filtered / pixel slots; empty ones for files that are not sound or not of the call's geometry),
-    png_gather_idat_batch, inflate_png_batch.  `flags`: PNG_FLAG_IGNORE_CRC.
-    -> (pix, pix_off, info, status, png_status): pix uint8 with image i at pix_off[i] .. pix_off[i+1] (height_i rows of
-    row_bytes, the PNG's own packed samples: no palette expansion, no tRNS, no gamma); info as png_scan_files_batch;
-    status the zlib decoder's (of an empty stream for a file that was skipped); png_status the gather's where that is not
-    0 (3, 7), else inflate_png_batch's."""
+def _png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len, flags, rgba):
+    """What png_decode_files_batch and png_decode_files_rgba_batch share: the scan, the ONE read-back of `info` that sizes
+    every buffer (with `rgba` the RGBA slots as well), gather, with `rgba` png_colour_batch, then inflate_png_batch.
+    -> (pix, pix_off, info, status, png_status, rgba_off, pal, colour, total pixel bytes, total RGBA bytes); png_status is
+    the first that is not 0 in that order."""
     import numpy as np
     import torch
     row_bytes, bpp = png_geometry(width, bit_depth, colour_type)
@@ -599,20 +600,98 @@ def png_decode_files_batch(file, file_off, width, bit_depth, colour_type, file_l
     info = png_scan_files_batch(file, file_off, file_len, flags=flags)
     f = png_info_fields(info)                                   # the one read-back
     good = (f["status"] == 0) & (f["width"] == width) & (f["bit_depth"] == bit_depth) & (f["colour_type"] == colour_type)
-    sizes = np.zeros((3, n + 1), dtype=np.int64)
+    sizes = np.zeros((4, n + 1), dtype=np.int64)
     sizes[0, 1:] = np.where(good, f["idat_bytes"], 0)
     sizes[1, 1:] = np.where(good, f["height"] * (row_bytes + 1), 0)
     sizes[2, 1:] = np.where(good, f["height"] * row_bytes, 0)
+    if rgba:
+        sizes[3, 1:] = np.where(good, f["height"] * (width * 4), 0)
     offs = torch.from_numpy(np.cumsum(sizes, axis=1)).to(dev)
     comp_off, filt_off, pix_off = offs[0], offs[1], offs[2]
-    total = offs[:, n].tolist() if n else [0, 0, 0]
+    total = offs[:, n].tolist() if n else [0, 0, 0, 0]
     comp = torch.empty(max(1, total[0]), dtype=torch.uint8, device=dev)
     filt = torch.empty(max(1, total[1]), dtype=torch.uint8, device=dev)
     pix = torch.empty(max(1, total[2]), dtype=torch.uint8, device=dev)
-    _, gathered = png_gather_idat_batch(file, file_off, info, comp, comp_off, width, bit_depth, colour_type)
-    _, status, _, png_status = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp,
-                                                 flags=0)
-    return pix[:total[2]], pix_off, info, status, torch.where(gathered != 0, gathered, png_status)
+    _, png_status = png_gather_idat_batch(file, file_off, info, comp, comp_off, width, bit_depth, colour_type)
+    pal = colour = None
+    if rgba:
+        pal, colour, coloured = png_colour_batch(file, file_off, info, width, bit_depth, colour_type)
+        png_status = torch.where(png_status != 0, png_status, coloured)
+    _, status, _, unfiltered = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0)
+    png_status = torch.where(png_status != 0, png_status, unfiltered)
+    return pix, pix_off, info, status, png_status, offs[3], pal, colour, total[2], total[3]
+
+
+def png_decode_files_batch(file, file_off, width, bit_depth, colour_type, file_len=None, flags=0):
+    """PNG files in, packed scanlines out: png_scan_files_batch, ONE read-back of `info` to size the buffers (exact
+    comp / filtered / pixel slots; empty ones for files that are not sound or not of the call's geometry),
+    png_gather_idat_batch, inflate_png_batch.  `flags`: PNG_FLAG_IGNORE_CRC.
+    -> (pix, pix_off, info, status, png_status): pix uint8 with image i at pix_off[i] .. pix_off[i+1] (height_i rows of
+    row_bytes, the PNG's own packed samples: palette indices, bit-packed and big-endian samples as they are, no tRNS --
+    png_decode_files_rgba_batch goes on to [H, W, 4] uint8 pictures; neither applies gamma); info as png_scan_files_batch;
+    status the zlib decoder's (of an empty stream for a file that was skipped); png_status the gather's where that is not
+    0 (3, 7), else inflate_png_batch's."""
+    pix, pix_off, info, status, png_status, _, _, _, total, _ = _png_files_to_pixels(file, file_off, width, bit_depth, colour_type,
+                                                                                    file_len, flags, False)
+    return pix[:total], pix_off, info, status, png_status
+
+
+def png_colour_batch(file, file_off, info, width, bit_depth, colour_type, pal=None, colour=None, png_status=None):
+    """PLTE and tRNS of n scanned files (fdh_png_colour_batch) -> (pal, colour, png_status): pal int32 [n, 256], the
+    words R | G << 8 | B << 16 | A << 24 (None unless colour_type is 3), colour int32 [n, 4] (PLTE entry count, bit 0 =
+    a colour key is present, key R or grey | G << 16, key B); png_status 0 ok, 3 / 7 as the gather's,
+    PNG_BAD_PLTE (10), PNG_BAD_TRNS (11)."""
+    import torch
+    n = file_off.numel() - 1
+    dev = file.device
+    if pal is None and colour_type == 3:
+        pal = torch.empty((n, 256), dtype=torch.int32, device=dev)
+    if colour is None:
+        colour = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=dev)
+    with _OnDevice(file, file_off, info, pal, colour, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_colour_batch(_ptr(file), _ptr(file_off), _ptr(info), _ptr(pal), _ptr(colour),
+                                                  _ptr(png_status), n, width, bit_depth, colour_type, C.c_void_p(stream)))
+    return pal, colour, png_status
+
+
+def png_expand_batch(pix, pix_off, rgba, rgba_off, width, bit_depth, colour_type, pal=None, colour=None, upstream=None,
+                     png_status=None):
+    """Packed scanlines to RGBA8 (fdh_png_expand_batch): image i, whole rows at pix_off[i] .. pix_off[i+1], goes to the
+    slot rgba[rgba_off[i] .. rgba_off[i+1]) of exactly rows * width * 4 bytes.  pal / colour as png_colour_batch writes
+    them (pal is needed for colour type 3; without colour there is no key and every palette index counts as inside);
+    upstream (int32 [n]): where not 0 the image is skipped and its png_status is that value.  -> png_status: 0 ok, 2 the
+    slots do not fit (nothing written), PNG_INDEX_OUTSIDE_PALETTE (9: such pixels are (0, 0, 0, 255))."""
+    import torch
+    n = pix_off.numel() - 1
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
+    with _OnDevice(pix, pix_off, rgba, rgba_off, pal, colour, upstream, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_expand_batch(_ptr(pix), _ptr(pix_off), _ptr(rgba), _ptr(rgba_off), _ptr(pal),
+                                                  _ptr(colour), _ptr(upstream), _ptr(png_status), n, width, bit_depth,
+                                                  colour_type, C.c_void_p(stream)))
+    return png_status
+
+
+def png_decode_files_rgba_batch(file, file_off, width, bit_depth, colour_type, file_len=None, flags=0):
+    """PNG files in, RGBA8 pictures out, on torch's current stream: png_decode_files_batch's steps (the same single
+    read-back, which also sizes the RGBA slots: height * width * 4 bytes, empty for files that are skipped) with
+    png_colour_batch behind the gather and png_expand_batch at the end.  -> (rgba, rgba_off, info, status, png_status):
+    rgba[rgba_off[i]:rgba_off[i+1]].view(h, width, 4) is picture i -- samples scaled to eight bits, palette and tRNS
+    applied (PNG specification; no gamma) --; info and status as png_decode_files_batch; png_status the first that is
+    not 0 of gather, colour, inflate_png_batch and expand (3, 7; 10, 11; 1 .. 3; 9)."""
+    import torch
+    pix, pix_off, info, status, png_status, rgba_off, pal, colour, _, total = _png_files_to_pixels(
+        file, file_off, width, bit_depth, colour_type, file_len, flags, True)
+    rgba = torch.empty(max(1, total), dtype=torch.uint8, device=file.device)
+    n = file_off.numel() - 1
+    if n:
+        upstream = torch.where(png_status != 0, png_status, status)   # (a zlib status reaches expand as "not 0")
+        expanded = png_expand_batch(pix, pix_off, rgba, rgba_off, width, bit_depth, colour_type, pal=pal, colour=colour,
+                                    upstream=upstream)
+        png_status = torch.where(png_status != 0, png_status, expanded)
+    return rgba[:total], rgba_off, info, status, png_status
 
 
 def inflate_batch_multi(shards, flags=0, gather=True):

@@ -48,6 +48,12 @@ int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uin
 int fdh_launch_png_gather(const uint8_t* file, const uint64_t* file_off, const void* info, uint8_t* comp,
                           const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n, uint32_t width,
                           uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+int fdh_launch_png_colour(const uint8_t* file, const uint64_t* file_off, const void* info, uint32_t* pal, uint32_t* colour,
+                          uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type,
+                          hipStream_t stream);
+int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
+                          const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n,
+                          uint32_t width, uint64_t row_bytes, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
 size_t fdh_deflate_general_hash_bytes(int kind);
 size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n);
 size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n);
@@ -356,6 +362,41 @@ int fdh_png_gather_idat_batch(const uint8_t* file, const uint64_t* file_off, con
     rc = fdh_launch_png_gather(file, file_off, info, comp, comp_off, comp_len, png_status, n, width, bit_depth,
                                colour_type, static_cast<hipStream_t>(hip_stream));
     if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "IDAT gather kernel launch");
+    return FDH_SUCCESS;
+}
+
+// ---- PNG decode to RGBA8: PLTE / tRNS (png_file.hip), expansion (png_expand.hip) ----
+int fdh_png_colour_batch(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint32_t* pal,
+                         uint32_t* colour, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
+                         uint32_t colour_type, void* hip_stream) {
+    int rc = png_geometry_ok(width, bit_depth, colour_type);
+    if (rc != FDH_SUCCESS) return rc;
+    if (n == 0) return FDH_SUCCESS;
+    if (!file || !file_off || !info || !colour || !png_status || (colour_type == 3 && !pal))
+        return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
+    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    rc = fdh_launch_png_colour(file, file_off, info, pal, colour, png_status, n, width, bit_depth, colour_type,
+                               static_cast<hipStream_t>(hip_stream));
+    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "PLTE / tRNS kernel launch");
+    return FDH_SUCCESS;
+}
+
+int fdh_png_expand_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
+                         const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* png_status,
+                         uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type, void* hip_stream) {
+    int rc = png_geometry_ok(width, bit_depth, colour_type);
+    if (rc != FDH_SUCCESS) return rc;
+    if (n == 0) return FDH_SUCCESS;
+    if (!pix || !pix_off || !rgba || !rgba_off || !png_status || (colour_type == 3 && !pal))
+        return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
+    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    const uint32_t channels = colour_type == 2 ? 3 : colour_type == 4 ? 2 : colour_type == 6 ? 4 : 1;
+    const uint64_t row_bytes = ((uint64_t)width * channels * bit_depth + 7) / 8;
+    rc = fdh_launch_png_expand(pix, pix_off, rgba, rgba_off, pal, colour, upstream, png_status, n, width, row_bytes,
+                               bit_depth, colour_type, static_cast<hipStream_t>(hip_stream));
+    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "RGBA expansion kernel launch");
     return FDH_SUCCESS;
 }
 

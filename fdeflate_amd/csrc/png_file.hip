@@ -520,6 +520,91 @@ __global__ __launch_bounds__(THREADS) void png_gather_idat_kernel(GatherArgs a) 
     }
 }
 
+// ---- fdh_png_colour_batch ----
+struct ColourArgs {
+    const uint8_t* file;
+    const uint64_t* file_off;
+    const PngInfo* info;
+    uint32_t* pal;     // nullable unless colour_type == 3: 256 words per file
+    uint32_t* colour;  // 4 words per file
+    uint32_t* png_status;
+    uint64_t n;
+    uint32_t width, bit_depth, colour_type;
+};
+
+constexpr uint32_t kTRNS = 0x74524E53u;
+
+// One file per wavefront.  The chunks between IHDR and the first IDAT are walked by all lanes alike (the addresses are
+// the same in every lane: scalar loads); the first finding in file order is the status.  Then every lane builds four
+// of the 256 palette words.  The scan has been over these chunks: their lengths fit the file and their CRCs are right.
+__global__ __launch_bounds__(kWave) void png_colour_kernel(ColourArgs a) {
+    const uint64_t i = blockIdx.x;
+    const uint32_t lane = threadIdx.x;
+    const PngInfo r = a.info[i];
+    const uint64_t slot = a.file_off[i + 1] - a.file_off[i];
+    const uint8_t* f = a.file + a.file_off[i];
+    const uint32_t ct = a.colour_type;
+    uint32_t st = 0;
+    if (r.status != 0) st = 3;
+    else if (r.width != a.width || r.bit_depth != a.bit_depth || r.colour_type != ct) st = 7;
+    else if (r.first_idat > slot) st = 3;  // (an info record that does not describe the file)
+    const uint32_t end = uni(r.first_idat);
+    uint64_t pos = 8;
+    bool have_plte = false, have_trns = false;
+    uint32_t plte_at = 0, count = 0, trns_at = 0, trns_len = 0;
+    while (st == 0 && pos < end) {
+        if (pos + 12 > end) {
+            st = 3;
+            break;
+        }
+        const uint32_t len = uni(get_be32(f + pos)), type = uni(get_be32(f + pos + 4));
+        if (pos + 12 + len > end) {
+            st = 3;
+            break;
+        }
+        if (type == kPLTE && ct == 3) {
+            if (have_plte || len == 0 || len % 3 != 0 || len > 768) st = 10;
+            have_plte = true;
+            plte_at = (uint32_t)pos + 8;
+            count = len / 3;
+        } else if (type == kTRNS && (ct == 0 || ct == 2 || ct == 3)) {
+            if (have_trns || (ct == 0 && len != 2) || (ct == 2 && len != 6) || (ct == 3 && (!have_plte || len > count))) st = 11;
+            have_trns = true;
+            trns_at = (uint32_t)pos + 8;
+            trns_len = len;
+        }
+        pos += 12ull + len;
+    }
+    if (st == 0 && ct == 3 && !have_plte) st = 10;
+    if (lane == 0) a.png_status[i] = st;
+    if (st != 0) return;
+    if (lane == 0) {
+        const uint8_t* t = f + trns_at;
+        const bool key = have_trns && ct != 3;
+        uint32_t k[3] = {0, 0, 0};
+        for (uint32_t c = 0; key && c < trns_len / 2; c++) k[c] = (uint32_t)t[2 * c] << 8 | t[2 * c + 1];
+        uint32_t* w = a.colour + 4 * i;
+        w[0] = count;
+        w[1] = key ? 1u : 0u;
+        w[2] = k[0] | k[1] << 16;
+        w[3] = k[2];
+    }
+    if (ct != 3) return;
+    uint32_t e[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        const uint32_t idx = 4 * lane + j;
+        uint32_t v = 0xFF000000u;
+        if (idx < count) {
+            const uint8_t* p = f + plte_at + 3 * idx;
+            v = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (idx < trns_len ? (uint32_t)f[trns_at + idx] : 255u) << 24;
+        }
+        e[j] = v;
+    }
+    const Bytes16 v{e[0], e[1], e[2], e[3]};
+    *reinterpret_cast<Bytes16*>(a.pal + 256 * i + 4 * lane) = v;
+}
+
 }  // namespace fdh
 
 // ---- launchers ----
@@ -584,6 +669,14 @@ extern "C" int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off
     if (e != hipSuccess || !verify_crc) return (int)e;
     if (n >= kFillWaves) hipLaunchKernelGGL((fdh::png_verify_crc_kernel<64>), dim3((unsigned)n), dim3(64), 0, stream, a);
     else hipLaunchKernelGGL((fdh::png_verify_crc_kernel<1024>), dim3((unsigned)n), dim3(1024), 0, stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int fdh_launch_png_colour(const uint8_t* file, const uint64_t* file_off, const void* info, uint32_t* pal,
+                                     uint32_t* colour, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
+                                     uint32_t colour_type, hipStream_t stream) {
+    fdh::ColourArgs a{file, file_off, static_cast<const fdh::PngInfo*>(info), pal, colour, png_status, n, width, bit_depth, colour_type};
+    hipLaunchKernelGGL(fdh::png_colour_kernel, dim3((unsigned)n), dim3(fdh::kWave), 0, stream, a);
     return (int)hipGetLastError();
 }
 

@@ -354,6 +354,60 @@ int fdh_png_gather_idat_batch(const uint8_t *file, const uint64_t *file_off,
                               uint32_t *comp_len, uint32_t *png_status, uint64_t n, uint32_t width,
                               uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
 
+/* ---- PNG decode to RGBA8: PLTE and tRNS, sample expansion --------------------------------------
+ * image-png's Transformations::EXPAND | STRIP_16 | ALPHA, not the fdeflate crate's ground: the packed
+ * scanlines that fdh_inflate_png_batch leaves become [rows, width, 4] uint8 pictures, R, G, B, A.  Samples
+ * are unpacked as the PNG specification says (7.2: most significant bits first, 16-bit samples big-endian;
+ * padding bits behind a row's last pixel are ignored) and brought to eight bits by to8(s) = s >> 8 at depth
+ * 16, s at depth 8, s * 255, s * 85, s * 17 at depths 1, 2, 4.  No gamma.
+ *   colour type 0  R = G = B = to8(g); A = 0 if a key is present and the RAW sample equals key & (2^depth - 1),
+ *                  else 255
+ *   colour type 2  to8 of each sample; A = 0 if a key is present and all three raw samples equal the key's
+ *                  three values (each masked to the depth; all 16 bits at depth 16), else 255
+ *   colour type 3  PLTE entry idx; A = tRNS byte idx where the chunk has one, else 255
+ *   colour type 4  R = G = B = to8(g), A = to8(a)
+ *   colour type 6  to8 of each sample
+ * A palette index at or above the number of PLTE entries gives (0, 0, 0, 255) and status 9.
+ *
+ * fdh_png_colour_batch -- reads PLTE and tRNS of file i out of the chunks between IHDR and info[i].first_idat
+ * (the scan has verified their CRCs; one wavefront per file).  info as fdh_png_scan_files_batch wrote it; width,
+ * bit_depth, colour_type as for fdh_png_gather_idat_batch.
+ *   pal[256 n]    per file 256 words R | G << 8 | B << 16 | A << 24: entries behind the PLTE's count are
+ *                 0xFF000000, A is 255 where tRNS is shorter.  Nullable unless colour_type is 3 (then not written).
+ *   colour[4 n]   word 0 the PLTE entry count (0 for other colour types); word 1 bit 0: a key is present;
+ *                 word 2 the key's R or grey | G << 16, word 3 its B (the 16-bit values of the chunk)
+ * png_status[i] -- the first finding in file order:
+ *   0  ok
+ *   3  info[i].status != 0 (or info does not describe the file)
+ *   7  the file's width, depth or colour type is not the call's
+ *   10 PLTE (colour type 3 only): none in front of IDAT; a length of 0, not a multiple of 3, above 768; a second one
+ *   11 tRNS: its length is not 2 (colour type 0) or 6 (colour type 2); for colour type 3 more bytes than PLTE has
+ *      entries, or in front of PLTE; a second tRNS (colour types 0, 2, 3)
+ * A tRNS in a file of colour type 4 or 6 is ignored (as libpng does), and so is a PLTE in a file of another
+ * colour type than 3.  Where png_status[i] != 0, pal and colour of file i are not specified.
+ *
+ * fdh_png_expand_batch -- image i = pix[pix_off[i] .. pix_off[i+1]), whole packed rows of the geometry's
+ * row_bytes at any alignment, to the slot rgba[rgba_off[i] .. rgba_off[i+1]) of exactly rows * width * 4 bytes.
+ *   pal       as above; nullable unless colour_type is 3
+ *   colour    as above; null: no key anywhere, and every palette index counts as inside the palette
+ *   upstream  nullable; where upstream[i] != 0 the image is skipped and png_status[i] = upstream[i] (earlier
+ *             failures pass through without a read-back)
+ * png_status[i]:
+ *   0 ok (an empty pixel slot with an empty output slot as well: nothing is written)
+ *   2 the pixel slot is not whole rows, or the output slot is not exactly the image's size: nothing is written
+ *   9 a palette index at or above the PLTE's count; the image is written in full
+ * An illegal depth / colour pair or width: FDH_ERR_INVALID_ARGUMENT.  No byte outside a slot is written and no
+ * byte outside pix[pix_off[0] .. pix_off[n]) is read.  FDH_PNG_EXPAND_WAVES (environment) sets the number of
+ * wavefronts per image.
+ */
+int fdh_png_colour_batch(const uint8_t *file, const uint64_t *file_off, const fdh_png_info *info,
+                         uint32_t *pal, uint32_t *colour, uint32_t *png_status, uint64_t n,
+                         uint32_t width, uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
+int fdh_png_expand_batch(const uint8_t *pix, const uint64_t *pix_off, uint8_t *rgba,
+                         const uint64_t *rgba_off, const uint32_t *pal, const uint32_t *colour,
+                         const uint32_t *upstream, uint32_t *png_status, uint64_t n, uint32_t width,
+                         uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
+
 /* ---- streaming decoder: `Decompressor` (src/decompress.rs:96-156, 179-342) ----------------
  * A host-side object with exactly `Decompressor::read`'s contract on HOST buffers; every bit of
  * decoding is done by fdh_inflate_batch_resumable on the device (the object keeps a device-resident
