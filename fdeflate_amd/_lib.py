@@ -82,6 +82,10 @@ def lib():
     L.fdh_png_colour_batch.argtypes = [vp, vp, vp, vp, vp, vp, u64, u32, u32, u32, vp]
     L.fdh_png_expand_batch.restype = C.c_int
     L.fdh_png_expand_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, u32, vp]
+    L.fdh_png_adam7_size.restype = u64
+    L.fdh_png_adam7_size.argtypes = [u32, u32, u32, u32]
+    L.fdh_png_unfilter_interlaced_batch.restype = C.c_int
+    L.fdh_png_unfilter_interlaced_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, u32, u32, vp]
     L.fdh_init.restype = C.c_int
     L.fdh_init.argtypes = [u64]
     L.fdh_shutdown.restype = C.c_int
@@ -131,7 +135,7 @@ EXPORTED_SYMBOLS = [
     "fdh_png_unfilter_batch", "fdh_png_filter_batch", "fdh_inflate_png_batch", "fdh_png_filter_deflate_ultrafast_batch",
     "fdh_png_choose_filters_batch",
     "fdh_crc32_batch", "fdh_png_file_bound", "fdh_png_frame_batch", "fdh_png_scan_files_batch", "fdh_png_gather_idat_batch",
-    "fdh_png_colour_batch", "fdh_png_expand_batch",
+    "fdh_png_colour_batch", "fdh_png_expand_batch", "fdh_png_adam7_size", "fdh_png_unfilter_interlaced_batch",
     "fdh_init", "fdh_shutdown", "fdh_multi_device_count", "fdh_multi_uses_rccl", "fdh_inflate_batch_multi",
 ]
 

@@ -453,6 +453,7 @@ def inflate_png_batch(comp, in_off, filt, filt_off, pix, pix_off, row_bytes, bpp
 PNG_FILE_PREFIX = 41   # signature 8 + IHDR chunk 25 + the IDAT's length and type 8
 PNG_FILE_SUFFIX = 16   # the IDAT's CRC 4 + IEND chunk 12
 PNG_FLAG_IGNORE_CRC = 1
+PNG_FLAG_ADAM7 = 2     # the scan accepts interlace method 1; the decode pipelines take such files to pixels
 # info.status of png_scan_files_batch; png_status 7 / 8 of png_gather_idat_batch
 PNG_SCAN_STATUS_NAMES = ["Ok", "NoSignature", "Truncated", "BadIhdr", "Interlaced", "ChunkStructure", "CrcMismatch"]
 PNG_OTHER_GEOMETRY = 7
@@ -587,9 +588,55 @@ def png_gather_idat_batch(file, file_off, info, comp, comp_off, width, bit_depth
     return comp_len, png_status
 
 
+# Adam7 (PNG specification 8.2): first column and row of pass p = 0 .. 6, column and row steps
+_ADAM7_X0, _ADAM7_Y0 = (0, 4, 0, 2, 0, 1, 0), (0, 0, 4, 0, 2, 0, 1)
+_ADAM7_DX, _ADAM7_DY = (8, 8, 4, 4, 2, 2, 1), (8, 8, 8, 4, 4, 2, 2)
+
+
+def png_adam7_size(width, height, bit_depth, colour_type):
+    """The number of bytes the IDAT stream of an Adam7-interlaced width x height image decodes to
+    (fdh_png_adam7_size's arithmetic, on the host, no device call): over the seven passes, ph * (1 + ceil(pw * bits / 8))
+    with pw = ceil((width - x0) / dx), ph = ceil((height - y0) / dy), nothing for a pass with pw = 0 or ph = 0.  0 for
+    an illegal depth / colour pair or a zero dimension.  `height` may be a numpy array (-> int64 array)."""
+    import numpy as np
+    h = np.asarray(height, dtype=np.int64)
+    total = np.zeros_like(h)
+    if colour_type in _PNG_DEPTHS and bit_depth in _PNG_DEPTHS[colour_type] and width > 0:
+        bits = _PNG_CHANNELS[colour_type] * bit_depth
+        for x0, y0, dx, dy in zip(_ADAM7_X0, _ADAM7_Y0, _ADAM7_DX, _ADAM7_DY):
+            pw = max(0, (width - x0 + dx - 1) // dx)
+            ph = np.maximum(0, (h - y0 + dy - 1) // dy)
+            if pw:
+                total = total + ph * (1 + (pw * bits + 7) // 8)
+        total = np.where(h > 0, total, 0)
+    return total if total.ndim else int(total)
+
+
+def png_unfilter_interlaced_batch(filt, filt_off, pix, pix_off, width, bit_depth, colour_type, method=None, upstream=None,
+                                  upstream_len=None, png_status=None):
+    """Decoded IDAT streams to packed scanlines, Adam7-interlaced images and progressive ones in one batch
+    (fdh_png_unfilter_interlaced_batch): image i, filt[filt_off[i] .. filt_off[i+1]) -- png_adam7_size(...) bytes, or
+    height * (row_bytes + 1) where method[i] is 0 --, goes to pix[pix_off[i] .. pix_off[i+1]), height_i rows of row_bytes
+    as png_unfilter_batch leaves them.  method: uint8 [n], 0 progressive, 1 Adam7 (None: all Adam7); upstream /
+    upstream_len: the decoder's status and out_len (int32 [n]).  `filt` is reconstructed in place: its contents
+    afterwards are not specified.  -> png_status: 0 ok, 1 a filter type above 4, 2 sizes do not fit, 3 upstream != 0."""
+    import torch
+    n = filt_off.numel() - 1
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=filt.device)
+    assert method is None or (method.dtype == torch.uint8 and method.numel() == n and method.is_contiguous())
+    with _OnDevice(filt, filt_off, pix, pix_off, method, upstream, upstream_len, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_unfilter_interlaced_batch(_ptr(filt), _ptr(filt_off), _ptr(pix), _ptr(pix_off), _ptr(method),
+                                                               _ptr(upstream), _ptr(upstream_len), _ptr(png_status), n, width,
+                                                               bit_depth, colour_type, C.c_void_p(stream)))
+    return png_status
+
+
 def _png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len, flags, rgba):
     """What png_decode_files_batch and png_decode_files_rgba_batch share: the scan, the ONE read-back of `info` that sizes
-    every buffer (with `rgba` the RGBA slots as well), gather, with `rgba` png_colour_batch, then inflate_png_batch.
+    every buffer (with `rgba` the RGBA slots as well), gather, with `rgba` png_colour_batch, then inflate_png_batch -- or,
+    with PNG_FLAG_ADAM7 and at least one good interlaced file in the batch, inflate_batch and
+    png_unfilter_interlaced_batch.
     -> (pix, pix_off, info, status, png_status, rgba_off, pal, colour, total pixel bytes, total RGBA bytes); png_status is
     the first that is not 0 in that order."""
     import numpy as np
@@ -603,6 +650,9 @@ def _png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len
     sizes = np.zeros((4, n + 1), dtype=np.int64)
     sizes[0, 1:] = np.where(good, f["idat_bytes"], 0)
     sizes[1, 1:] = np.where(good, f["height"] * (row_bytes + 1), 0)
+    adam7 = good & (f["interlace"] == 1)        # (only the scan with PNG_FLAG_ADAM7 leaves such a file at status 0)
+    if adam7.any():
+        sizes[1, 1:] = np.where(adam7, png_adam7_size(width, f["height"], bit_depth, colour_type), sizes[1, 1:])
     sizes[2, 1:] = np.where(good, f["height"] * row_bytes, 0)
     if rgba:
         sizes[3, 1:] = np.where(good, f["height"] * (width * 4), 0)
@@ -617,7 +667,13 @@ def _png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len
     if rgba:
         pal, colour, coloured = png_colour_batch(file, file_off, info, width, bit_depth, colour_type)
         png_status = torch.where(png_status != 0, png_status, coloured)
-    _, status, _, unfiltered = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0)
+    if adam7.any():
+        method = info.view(torch.uint8).view(-1, 4 * PNG_INFO_WORDS)[:, 14].contiguous()    # info.interlace, on the device
+        out_len, status, _ = inflate_batch(comp, comp_off, filt, filt_off, flags=0)
+        unfiltered = png_unfilter_interlaced_batch(filt, filt_off, pix, pix_off, width, bit_depth, colour_type, method=method,
+                                                   upstream=status, upstream_len=out_len)
+    else:
+        _, status, _, unfiltered = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0)
     png_status = torch.where(png_status != 0, png_status, unfiltered)
     return pix, pix_off, info, status, png_status, offs[3], pal, colour, total[2], total[3]
 
@@ -625,7 +681,10 @@ def _png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len
 def png_decode_files_batch(file, file_off, width, bit_depth, colour_type, file_len=None, flags=0):
     """PNG files in, packed scanlines out: png_scan_files_batch, ONE read-back of `info` to size the buffers (exact
     comp / filtered / pixel slots; empty ones for files that are not sound or not of the call's geometry),
-    png_gather_idat_batch, inflate_png_batch.  `flags`: PNG_FLAG_IGNORE_CRC.
+    png_gather_idat_batch, inflate_png_batch.  `flags`: PNG_FLAG_IGNORE_CRC, PNG_FLAG_ADAM7 -- with the latter
+    Adam7-interlaced files are decoded too (a batch that holds one goes through inflate_batch and
+    png_unfilter_interlaced_batch; one that holds none takes the same calls as without the flag); without it such a
+    file is info.status 4 / png_status 3 with empty slots.
     -> (pix, pix_off, info, status, png_status): pix uint8 with image i at pix_off[i] .. pix_off[i+1] (height_i rows of
     row_bytes, the PNG's own packed samples: palette indices, bit-packed and big-endian samples as they are, no tRNS --
     png_decode_files_rgba_batch goes on to [H, W, 4] uint8 pictures; neither applies gamma); info as png_scan_files_batch;
@@ -677,7 +736,8 @@ def png_expand_batch(pix, pix_off, rgba, rgba_off, width, bit_depth, colour_type
 def png_decode_files_rgba_batch(file, file_off, width, bit_depth, colour_type, file_len=None, flags=0):
     """PNG files in, RGBA8 pictures out, on torch's current stream: png_decode_files_batch's steps (the same single
     read-back, which also sizes the RGBA slots: height * width * 4 bytes, empty for files that are skipped) with
-    png_colour_batch behind the gather and png_expand_batch at the end.  -> (rgba, rgba_off, info, status, png_status):
+    png_colour_batch behind the gather and png_expand_batch at the end; `flags` as there (PNG_FLAG_ADAM7 included).
+    -> (rgba, rgba_off, info, status, png_status):
     rgba[rgba_off[i]:rgba_off[i+1]].view(h, width, 4) is picture i -- samples scaled to eight bits, palette and tRNS
     applied (PNG specification; no gamma) --; info and status as png_decode_files_batch; png_status the first that is
     not 0 of gather, colour, inflate_png_batch and expand (3, 7; 10, 11; 1 .. 3; 9)."""

@@ -44,7 +44,7 @@ int fdh_launch_png_frame(uint8_t* file, const uint64_t* file_off, const uint32_t
                          uint32_t* file_len, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
                          uint32_t colour_type, hipStream_t stream);
 int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, void* info, uint64_t n,
-                        int verify_crc, hipStream_t stream);
+                        int verify_crc, int adam7, hipStream_t stream);
 int fdh_launch_png_gather(const uint8_t* file, const uint64_t* file_off, const void* info, uint8_t* comp,
                           const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n, uint32_t width,
                           uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
@@ -54,6 +54,9 @@ int fdh_launch_png_colour(const uint8_t* file, const uint64_t* file_off, const v
 int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
                           const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n,
                           uint32_t width, uint64_t row_bytes, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+int fdh_launch_png_adam7(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, const uint8_t* method,
+                         const uint32_t* upstream, const uint32_t* upstream_len, uint32_t* status, uint64_t n, uint32_t width,
+                         uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
 size_t fdh_deflate_general_hash_bytes(int kind);
 size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n);
 size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n);
@@ -344,7 +347,7 @@ int fdh_png_scan_files_batch(const uint8_t* file, const uint64_t* file_off, cons
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
     if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
     int rc = fdh_launch_png_scan(file, file_off, file_len, info, n, (flags & FDH_PNG_FLAG_IGNORE_CRC) ? 0 : 1,
-                                 static_cast<hipStream_t>(hip_stream));
+                                 (flags & FDH_PNG_FLAG_ADAM7) ? 1 : 0, static_cast<hipStream_t>(hip_stream));
     if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "PNG scan kernel launch");
     return FDH_SUCCESS;
 }
@@ -397,6 +400,37 @@ int fdh_png_expand_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* r
     rc = fdh_launch_png_expand(pix, pix_off, rgba, rgba_off, pal, colour, upstream, png_status, n, width, row_bytes,
                                bit_depth, colour_type, static_cast<hipStream_t>(hip_stream));
     if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "RGBA expansion kernel launch");
+    return FDH_SUCCESS;
+}
+
+// ---- PNG decode: Adam7 interlaced images (png_adam7.hip) ----
+uint64_t fdh_png_adam7_size(uint32_t width, uint32_t height, uint32_t bit_depth, uint32_t colour_type) {
+    if (width == 0 || height == 0 || !png_pair_ok(bit_depth, colour_type)) return 0;
+    static const uint32_t x0[7] = {0, 4, 0, 2, 0, 1, 0}, y0[7] = {0, 0, 4, 0, 2, 0, 1};
+    static const uint32_t dx[7] = {8, 8, 4, 4, 2, 2, 1}, dy[7] = {8, 8, 8, 4, 4, 2, 2};
+    const uint64_t bits = (colour_type == 2 ? 3 : colour_type == 4 ? 2 : colour_type == 6 ? 4 : 1) * (uint64_t)bit_depth;
+    uint64_t total = 0;
+    for (int p = 0; p < 7; p++) {
+        const uint64_t pw = width > x0[p] ? ((uint64_t)width - x0[p] + dx[p] - 1) / dx[p] : 0;
+        const uint64_t ph = height > y0[p] ? ((uint64_t)height - y0[p] + dy[p] - 1) / dy[p] : 0;
+        if (pw && ph) total += ph * (1 + (pw * bits + 7) / 8);
+    }
+    return total;
+}
+
+int fdh_png_unfilter_interlaced_batch(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off,
+                                      const uint8_t* method, const uint32_t* upstream, const uint32_t* upstream_len,
+                                      uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
+                                      uint32_t colour_type, void* hip_stream) {
+    int rc = png_geometry_ok(width, bit_depth, colour_type);
+    if (rc != FDH_SUCCESS) return rc;
+    if (n == 0) return FDH_SUCCESS;
+    if (!filt || !filt_off || !pix || !pix_off || !png_status) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
+    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    rc = fdh_launch_png_adam7(filt, filt_off, pix, pix_off, method, upstream, upstream_len, png_status, n, width, bit_depth,
+                              colour_type, static_cast<hipStream_t>(hip_stream));
+    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "Adam7 reconstruction / placement kernel launch");
     return FDH_SUCCESS;
 }
 

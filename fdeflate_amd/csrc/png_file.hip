@@ -330,6 +330,7 @@ struct ScanArgs {
     const uint32_t* file_len;  // nullable
     PngInfo* info;
     uint64_t n;
+    bool adam7;  // FDH_PNG_FLAG_ADAM7: interlace method 1 is no finding
 };
 
 __device__ __forceinline__ bool png_pair_ok(uint32_t depth, uint32_t colour) {
@@ -382,7 +383,7 @@ __global__ __launch_bounds__(64) void png_scan_kernel(ScanArgs a) {
             if (r.width == 0 || r.height == 0 || (r.width | r.height) >> 31 || !png_pair_ok(d[8], d[9]) || d[10] != 0 ||
                 d[11] != 0 || d[12] > 1)
                 st = 3;
-            else if (d[12] == 1)
+            else if (d[12] == 1 && !a.adam7)
                 st = 4;
         } else if (type == kIDAT) {
             if (idat_over) st = 5;
@@ -662,8 +663,8 @@ extern "C" int fdh_launch_png_frame(uint8_t* file, const uint64_t* file_off, con
 }
 
 extern "C" int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, void* info,
-                                   uint64_t n, int verify_crc, hipStream_t stream) {
-    fdh::ScanArgs a{file, file_off, file_len, static_cast<fdh::PngInfo*>(info), n};
+                                   uint64_t n, int verify_crc, int adam7, hipStream_t stream) {
+    fdh::ScanArgs a{file, file_off, file_len, static_cast<fdh::PngInfo*>(info), n, adam7 != 0};
     hipLaunchKernelGGL(fdh::png_scan_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !verify_crc) return (int)e;

@@ -326,12 +326,16 @@ int fdh_png_frame_batch(uint8_t *file, const uint64_t *file_off, const uint32_t 
  *   2 truncated: a chunk runs past the end of the file, or there is no IEND
  *   3 bad IHDR: not the first chunk, length not 13, a zero dimension (or one above 2^31-1), an illegal
  *     depth / colour pair, compression or filter method not 0 (or an interlace method above 1)
- *   4 interlace method 1 (Adam7 is not provided)
+ *   4 interlace method 1, unless FDH_PNG_FLAG_ADAM7 is set
  *   5 chunk structure: no IDAT, IDAT chunks not consecutive, a PLTE after IDAT, an unknown critical chunk
  *   6 CRC mismatch in some chunk
  * The walk ends at the first finding; the counts then hold what came before it.  first_idat is the offset
  * of the first IDAT chunk (its length field) in the file, chunks counts IHDR .. IEND.
  * FDH_PNG_FLAG_IGNORE_CRC skips the CRC pass (as FDH_FLAG_IGNORE_ADLER32 skips that check).
+ * FDH_PNG_FLAG_ADAM7: an IHDR with interlace method 1 is no finding -- the walk goes on to IEND, every count is
+ * filled in, the CRC pass runs, and info.interlace is 1 (fdh_png_unfilter_interlaced_batch below takes such a
+ * file's decoded IDAT stream to pixels).  Without the flag such a file is status 4 and the walk ends at IHDR; a
+ * method above 1 is status 3 either way.
  *
  * fdh_png_gather_idat_batch -- copies the IDAT bodies of file i, in order, to comp[comp_off[i] ..) as one
  * zlib stream (what fdh_inflate_png_batch takes) and sets comp_len[i] = info[i].idat_bytes; 16 bytes per
@@ -339,8 +343,11 @@ int fdh_png_frame_batch(uint8_t *file, const uint64_t *file_off, const uint32_t 
  * png_status[i]: 0 ok; 3 info[i].status != 0 (skipped, as above); 7 the file's width, depth or colour type
  * is not the call's; 8 the slot comp_off[i+1] - comp_off[i] is too small.  Where it is not 0, comp_len[i] = 0
  * and nothing is written.  Geometry arguments as for fdh_png_frame_batch.
+ * Neither the gather nor fdh_png_colour_batch looks at info.interlace: the chunks around the pixels are the same
+ * in both layouts, and both calls serve interlaced files as they are.
  */
 #define FDH_PNG_FLAG_IGNORE_CRC 0x1u
+#define FDH_PNG_FLAG_ADAM7 0x2u
 typedef struct fdh_png_info {
   uint32_t status, width, height;
   uint8_t bit_depth, colour_type, interlace, pad;
@@ -407,6 +414,51 @@ int fdh_png_expand_batch(const uint8_t *pix, const uint64_t *pix_off, uint8_t *r
                          const uint64_t *rgba_off, const uint32_t *pal, const uint32_t *colour,
                          const uint32_t *upstream, uint32_t *png_status, uint64_t n, uint32_t width,
                          uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
+
+/* ---- PNG decode: Adam7 interlaced images ---------------------------------------------------------
+ * image-png's interlace handling, not the fdeflate crate's ground.  PNG specification 8.2: the IDAT stream of a
+ * file with interlace method 1 holds seven reduced images ("passes") one behind the other, pass p = 0 .. 6 with
+ *   x0 = 0, 4, 0, 2, 0, 1, 0    y0 = 0, 0, 4, 0, 2, 0, 1    dx = 8, 8, 4, 4, 2, 2, 1    dy = 8, 8, 8, 4, 4, 2, 2
+ * pw = ceil((width - x0) / dx) pixels wide and ph = ceil((height - y0) / dy) rows high (0 where negative).  A pass
+ * with pw = 0 or ph = 0 has no bytes at all; any other is ph rows of 1 + ceil(pw * bits / 8) bytes, filtered as an
+ * image of its own: the row above its first row is zeros, and the pixel size of the filters is the full image's,
+ * max(1, channels * depth / 8).  Pixel j of row r of pass p is pixel (x0 + j dx, y0 + r dy) of the picture; at
+ * depths 1, 2 and 4 pixels are bit fields, most significant first, in both layouts.
+ *
+ * fdh_png_adam7_size -- the number of bytes the IDAT stream of an interlaced width x height image decodes to
+ * (the sum over the passes); 0 for an illegal depth / colour pair or a zero dimension.  Host arithmetic, no device.
+ * It can equal the progressive size height * (1 + row_bytes) (1 x 9 grey-8: 18 both ways), so the size never tells
+ * the two layouts apart.
+ *
+ * fdh_png_unfilter_interlaced_batch -- image i = filt[filt_off[i] .. filt_off[i+1]), what the zlib decoder left,
+ * goes to packed scanlines in pix[pix_off[i] .. pix_off[i+1]): the layout fdh_png_unfilter_batch produces and
+ * fdh_png_expand_batch reads (height_i = slot / row_bytes rows of row_bytes, samples as PNG packs them, padding
+ * bits of a row zero: those of an Adam7 image's pass rows are dropped, whatever they hold; a progressive image
+ * keeps its own as they come, as with fdh_png_unfilter_batch).  width, bit_depth, colour_type as for
+ * fdh_png_expand_batch.
+ *   method        a byte per image: 0 progressive, 1 Adam7; null = all Adam7.  A progressive image is the same
+ *                 machinery with one pass (x0 = y0 = 0, dx = dy = 1) and gives exactly fdh_png_unfilter_batch's
+ *                 bytes, so a batch may mix both kinds (info[i].interlace, byte 14 of a record, is such a byte).
+ *   upstream, upstream_len   nullable: the decoder's status and out_len (the gate of fdh_inflate_png_batch)
+ * `filt` is NOT const: the images are reconstructed in place, and the contents of the filt slots afterwards are
+ * not specified.
+ * png_status[i]:
+ *   0 ok (two empty slots: nothing is written)
+ *   1 a filter type above 4 in some pass row; the contents of the pix slot are not specified
+ *   2 the pix slot is not whole rows; or the filt slot is not exactly fdh_png_adam7_size (method 1) or
+ *     height * (row_bytes + 1) (method 0); or upstream_len[i] is not the filt slot's size; or a method byte
+ *     above 1: nothing is written
+ *   3 upstream[i] is not 0: nothing is written
+ * No byte outside a pix slot is written, no byte outside filt[filt_off[0] .. filt_off[n]) is read.  No workspace,
+ * no host synchronisation, any alignment.  An illegal pair or width: FDH_ERR_INVALID_ARGUMENT.
+ * FDH_PNG_ADAM7_WAVES (environment) sets the number of placement wavefronts per image.
+ */
+uint64_t fdh_png_adam7_size(uint32_t width, uint32_t height, uint32_t bit_depth, uint32_t colour_type);
+int fdh_png_unfilter_interlaced_batch(uint8_t *filt, const uint64_t *filt_off, uint8_t *pix,
+                                      const uint64_t *pix_off, const uint8_t *method,
+                                      const uint32_t *upstream, const uint32_t *upstream_len,
+                                      uint32_t *png_status, uint64_t n, uint32_t width,
+                                      uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
 
 /* ---- streaming decoder: `Decompressor` (src/decompress.rs:96-156, 179-342) ----------------
  * A host-side object with exactly `Decompressor::read`'s contract on HOST buffers; every bit of
