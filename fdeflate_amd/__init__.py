@@ -17,7 +17,9 @@ from .api import (Decompressor, DecompressionError, OutputTooLarge, STATUS_NAMES
                   png_info_fields, png_gather_idat_batch, png_decode_files_batch, PNG_FILE_PREFIX, PNG_FILE_SUFFIX,
                   PNG_FLAG_IGNORE_CRC, PNG_SCAN_STATUS_NAMES, PNG_OTHER_GEOMETRY, PNG_COMP_SLOT_TOO_SMALL,
                   PNG_INDEX_OUTSIDE_PALETTE, PNG_BAD_PLTE, PNG_BAD_TRNS, png_colour_batch, png_expand_batch,
-                  png_decode_files_rgba_batch, PNG_FLAG_ADAM7, png_adam7_size, png_unfilter_interlaced_batch)
+                  png_decode_files_rgba_batch, PNG_FLAG_ADAM7, png_adam7_size, png_unfilter_interlaced_batch,
+                  PNG_OK, PNG_BAD_FILTER_TYPE, PNG_BAD_SIZES, PNG_SKIPPED, PNG_SCAN_NO_SIGNATURE, PNG_SCAN_TRUNCATED,
+                  PNG_SCAN_BAD_IHDR, PNG_SCAN_INTERLACED, PNG_SCAN_CHUNK_STRUCTURE, PNG_SCAN_CRC_MISMATCH)
 
 __all__ = [
     "Decompressor", "DecompressionError", "OutputTooLarge", "STATUS_NAMES", "FLAG_IGNORE_ADLER32",
@@ -33,4 +35,6 @@ __all__ = [
     "PNG_FLAG_IGNORE_CRC", "PNG_SCAN_STATUS_NAMES", "PNG_OTHER_GEOMETRY", "PNG_COMP_SLOT_TOO_SMALL",
     "PNG_INDEX_OUTSIDE_PALETTE", "PNG_BAD_PLTE", "PNG_BAD_TRNS", "png_colour_batch", "png_expand_batch",
     "png_decode_files_rgba_batch", "PNG_FLAG_ADAM7", "png_adam7_size", "png_unfilter_interlaced_batch",
+    "PNG_OK", "PNG_BAD_FILTER_TYPE", "PNG_BAD_SIZES", "PNG_SKIPPED", "PNG_SCAN_NO_SIGNATURE", "PNG_SCAN_TRUNCATED",
+    "PNG_SCAN_BAD_IHDR", "PNG_SCAN_INTERLACED", "PNG_SCAN_CHUNK_STRUCTURE", "PNG_SCAN_CRC_MISMATCH",
 ]

@@ -454,7 +454,19 @@ PNG_FILE_PREFIX = 41   # signature 8 + IHDR chunk 25 + the IDAT's length and typ
 PNG_FILE_SUFFIX = 16   # the IDAT's CRC 4 + IEND chunk 12
 PNG_FLAG_IGNORE_CRC = 1
 PNG_FLAG_ADAM7 = 2     # the scan accepts interlace method 1; the decode pipelines take such files to pixels
+# The per-image status values, named as include/fdeflate_hip.h names them (FDH_PNG_STATUS_*).
+# png_status of the row calls (reconstruction, filtering, selection, the fused encoder, framing, Adam7):
+PNG_OK = 0
+PNG_BAD_FILTER_TYPE = 1
+PNG_BAD_SIZES = 2
+PNG_SKIPPED = 3
 # info.status of png_scan_files_batch; png_status 7 / 8 of png_gather_idat_batch
+PNG_SCAN_NO_SIGNATURE = 1
+PNG_SCAN_TRUNCATED = 2
+PNG_SCAN_BAD_IHDR = 3
+PNG_SCAN_INTERLACED = 4
+PNG_SCAN_CHUNK_STRUCTURE = 5
+PNG_SCAN_CRC_MISMATCH = 6
 PNG_SCAN_STATUS_NAMES = ["Ok", "NoSignature", "Truncated", "BadIhdr", "Interlaced", "ChunkStructure", "CrcMismatch"]
 PNG_OTHER_GEOMETRY = 7
 PNG_COMP_SLOT_TOO_SMALL = 8

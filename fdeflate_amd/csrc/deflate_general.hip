@@ -30,6 +30,7 @@
 // lanes 0 and 1 -- the rest (compaction, code assignment, header) on the whole wavefront.
 #include "device_common.h"
 #include "bit_ring.h"
+#include "launch.h"
 
 namespace fdh {
 

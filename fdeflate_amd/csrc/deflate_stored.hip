@@ -9,6 +9,7 @@
 // known up front (output byte of input byte i = 2 + 5 (i / 65535 + 1) + i), so the block payloads
 // are copied 8 bytes per lane (both sides unaligned) and the checksum is accumulated on the way.
 #include "device_common.h"
+#include "launch.h"
 
 namespace fdh {
 

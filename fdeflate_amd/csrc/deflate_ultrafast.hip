@@ -19,6 +19,8 @@
 // (ultrafast.rs:16-29), so bit-exactness only depends on the symbol sequence and the codes.
 #include "device_common.h"
 #include "bit_ring.h"
+#include "launch.h"
+#include "png_common.h"
 
 namespace fdh {
 
@@ -132,7 +134,7 @@ struct DeflateBatchArgs {
     // is the filtered image -- a type byte + row_bytes filtered bytes per row -- computed on the fly
     const uint8_t* types;       // one filter type per row
     const uint64_t* types_off;
-    uint32_t* png_status;       // 0 ok, 1 a filter type > 4, 2 sizes do not fit
+    uint32_t* png_status;       // kPngOk, kPngBadFilterType, kPngBadSizes
     uint32_t row_bytes, bpp;
 };
 
@@ -319,7 +321,7 @@ void deflate_ultrafast_kernel_t(DeflateBatchArgs a) {
     if (PNG) {  // the encoder's input: rows x (1 + row_bytes) filtered bytes
         const uint64_t plen = len, nrows = plen / a.row_bytes;
         const uint64_t tlen = a.types_off[sid + 1] - a.types_off[sid];
-        uint32_t st = (nrows * a.row_bytes != plen || tlen != nrows || nrows >= (1ull << 31) / (a.row_bytes + 1ull)) ? 2u : 0u;
+        uint32_t st = (nrows * a.row_bytes != plen || tlen != nrows || nrows >= (1ull << 31) / (a.row_bytes + 1ull)) ? kPngBadSizes : kPngOk;
         png.pix = in;
         png.types = a.types + a.types_off[sid];
         png.rb = a.row_bytes;
@@ -328,7 +330,7 @@ void deflate_ultrafast_kernel_t(DeflateBatchArgs a) {
         png.rows = st ? 0u : (uint32_t)nrows;
         bool bad_type = false;
         for (uint32_t r = (uint32_t)lane; r < png.rows; r += kWave) bad_type = bad_type || png.types[r] > 4;
-        if (__any(bad_type)) st = 1;
+        if (__any(bad_type)) st = kPngBadFilterType;
         if (lane == 0) a.png_status[sid] = st;
         if (st) {
             if (lane == 0) a.out_len[sid] = 0;

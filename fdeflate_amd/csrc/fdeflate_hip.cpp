@@ -1,68 +1,16 @@
 // fdeflate_hip.cpp -- host side of the C ABI declared in include/fdeflate_hip.h.
 // Thin: argument checks, kernel launches, and H2D/D2H staging for the single-buffer
 // conveniences.  There is deliberately no CPU decode/encode path in this library.
-#include "../../include/fdeflate_hip.h"
-
-#include <hip/hip_runtime.h>
+#include "launch.h"
+#include "png_common.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
-
-extern "C" {
-int fdh_launch_inflate(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                       uint32_t* out_len, uint32_t* status, uint32_t* adler, uint64_t n, uint32_t flags,
-                       void* resume_io, hipStream_t stream);
-int fdh_launch_canon_build(hipStream_t stream, uint32_t* host_status);
-int fdh_launch_build_tables_debug(const uint8_t* code_lengths, uint32_t hlit, uint32_t* litlen, uint32_t* dist,
-                                  uint32_t* build_status, hipStream_t stream);
-int fdh_launch_deflate_stored(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                              uint32_t* out_len, uint64_t n, hipStream_t stream);
-int fdh_launch_png_filter_deflate_ultrafast(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types,
-                                            const uint64_t* types_off, uint8_t* out, const uint64_t* out_off,
-                                            uint32_t* out_len, uint32_t* png_status, uint64_t n, uint32_t row_bytes,
-                                            uint32_t bpp, hipStream_t stream);
-int fdh_launch_deflate_ultrafast(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                                 uint32_t* out_len, uint64_t n, hipStream_t stream);
-int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                               uint32_t* out_len, uint64_t n, int kind, void* hash, void* matches, void* blocks,
-                               uint32_t* nblocks, unsigned waves, unsigned lanes, hipStream_t stream);
-int fdh_launch_png_unfilter(const uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off,
-                            uint32_t* status, const uint32_t* gate, const uint32_t* gate_len, uint64_t n,
-                            uint32_t row_bytes, uint32_t bpp, hipStream_t stream);
-int fdh_launch_png_filter(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
-                          uint8_t* filt, const uint64_t* filt_off, uint32_t* status, uint64_t n, uint32_t row_bytes,
-                          uint32_t bpp, hipStream_t stream);
-int fdh_launch_png_choose(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off,
-                          uint32_t* status, uint64_t n, uint32_t row_bytes, uint32_t bpp, hipStream_t stream);
-int fdh_launch_crc32(const uint8_t* data, const uint64_t* off, const uint32_t* len, const uint32_t* seed, uint32_t* crc,
-                     uint32_t* status, uint64_t n, hipStream_t stream);
-int fdh_launch_png_frame(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height,
-                         uint32_t* file_len, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
-                         uint32_t colour_type, hipStream_t stream);
-int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, void* info, uint64_t n,
-                        int verify_crc, int adam7, hipStream_t stream);
-int fdh_launch_png_gather(const uint8_t* file, const uint64_t* file_off, const void* info, uint8_t* comp,
-                          const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n, uint32_t width,
-                          uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
-int fdh_launch_png_colour(const uint8_t* file, const uint64_t* file_off, const void* info, uint32_t* pal, uint32_t* colour,
-                          uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type,
-                          hipStream_t stream);
-int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
-                          const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n,
-                          uint32_t width, uint64_t row_bytes, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
-int fdh_launch_png_adam7(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, const uint8_t* method,
-                         const uint32_t* upstream, const uint32_t* upstream_len, uint32_t* status, uint64_t n, uint32_t width,
-                         uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
-size_t fdh_deflate_general_hash_bytes(int kind);
-size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n);
-size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n);
-size_t fdh_deflate_general_match_record_bytes(void);
-size_t fdh_deflate_general_block_record_bytes(void);
-}
 
 namespace {
 
@@ -84,11 +32,25 @@ int hip_fail(hipError_t e, const char* what) {
         if (e_ != hipSuccess) return hip_fail(e_, #expr); \
     } while (0)
 
-bool have_device() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return false;
-    return n > 0;
+bool have_device() { return fdh_device_count() > 0; }
+
+int no_device() { return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback"); }
+
+// What the batch entry points check once they know there is work, in this order: the pointers the call cannot do
+// without (`null_msg` names them), the batch size (`noun`: what the call counts), a device.  A pointer that is required
+// only under a condition is listed as `condition ? pointer : one that is required anyway`.
+int batch_ok(std::initializer_list<const void*> required, const char* null_msg, uint64_t n, const char* noun) {
+    for (const void* p : required)
+        if (!p) return fail(FDH_ERR_INVALID_ARGUMENT, null_msg);
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, std::string("too many ") + noun + " in one call (max 2^31-1)");
+    if (!have_device()) return no_device();
+    return FDH_SUCCESS;
 }
+
+// ... and how they end: a launcher's return value as the call's
+int launched(const char* what, int rc) { return rc != 0 ? hip_fail(static_cast<hipError_t>(rc), what) : FDH_SUCCESS; }
+
+hipStream_t stream_of(void* hip_stream) { return static_cast<hipStream_t>(hip_stream); }
 
 // The shared decode tables of the ultra-fast prefix are built on the device once per device.
 std::mutex g_canon_mutex;
@@ -101,8 +63,7 @@ int ensure_canon_tables(hipStream_t stream) {
     std::lock_guard<std::mutex> lock(g_canon_mutex);
     if (g_canon_ready[dev]) return FDH_SUCCESS;
     uint32_t st = 0xFFFFFFFFu;
-    int rc = fdh_launch_canon_build(stream, &st);
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "canonical table build");
+    if (int rc = launched("canonical table build", fdh_launch_canon_build(stream, &st))) return rc;
     if (st != 0) return fail(FDH_ERR_HIP, "canonical table build returned status " + std::to_string(st));
     g_canon_ready[dev] = true;
     return FDH_SUCCESS;
@@ -154,96 +115,72 @@ uint64_t fdh_stored_size(uint64_t len) {
 int fdh_deflate_stored_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
                              uint32_t* out_len, uint64_t n, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many buffers in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    int rc = fdh_launch_deflate_stored(in, in_off, out, out_off, out_len, n, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "stored-encoder kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({in_off, out_off, out_len}, "null metadata pointer", n, "buffers")) return rc;
+    return launched("stored-encoder kernel launch", fdh_launch_deflate_stored(in, in_off, out, out_off, out_len, n, stream_of(hip_stream)));
 }
 
 int fdh_inflate_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
                       uint32_t* out_len, uint32_t* status, uint32_t* adler, uint64_t n, uint32_t flags,
                       void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    if (!in_off || !out_off || !out_len || !status) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    int rc = ensure_canon_tables(static_cast<hipStream_t>(hip_stream));
-    if (rc != FDH_SUCCESS) return rc;
-    rc = fdh_launch_inflate(in, in_off, out, out_off, out_len, status, adler, n, flags & ~FDH_FLAG_RESUME_IN, nullptr,
-                            static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "inflate kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({in_off, out_off, out_len, status}, "null metadata pointer", n, "streams")) return rc;
+    if (int rc = ensure_canon_tables(stream_of(hip_stream))) return rc;
+    return launched("inflate kernel launch", fdh_launch_inflate(in, in_off, out, out_off, out_len, status, adler, n,
+                    flags & ~FDH_FLAG_RESUME_IN, nullptr, stream_of(hip_stream)));
 }
 
 int fdh_inflate_batch_resumable(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
                                 uint32_t* out_len, uint32_t* status, uint32_t* adler, uint64_t n, uint32_t flags,
                                 fdh_resume_point* resume, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    if (!in_off || !out_off || !out_len || !status || !resume) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    int rc = ensure_canon_tables(static_cast<hipStream_t>(hip_stream));
-    if (rc != FDH_SUCCESS) return rc;
-    rc = fdh_launch_inflate(in, in_off, out, out_off, out_len, status, adler, n, flags, resume, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "inflate kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({in_off, out_off, out_len, status, resume}, "null metadata pointer", n, "streams")) return rc;
+    if (int rc = ensure_canon_tables(stream_of(hip_stream))) return rc;
+    return launched("inflate kernel launch", fdh_launch_inflate(in, in_off, out, out_off, out_len, status, adler, n, flags, resume,
+                    stream_of(hip_stream)));
 }
 
 int fdh_deflate_ultrafast_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
                                 uint32_t* out_len, uint64_t n, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many buffers in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    int rc = fdh_launch_deflate_ultrafast(in, in_off, out, out_off, out_len, n, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "deflate kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({in_off, out_off, out_len}, "null metadata pointer", n, "buffers")) return rc;
+    return launched("deflate kernel launch", fdh_launch_deflate_ultrafast(in, in_off, out, out_off, out_len, n, stream_of(hip_stream)));
 }
 
 int fdh_debug_build_tables(const uint8_t* code_lengths320, uint32_t hlit, uint32_t* litlen4096, uint32_t* dist512,
                            uint32_t* build_status, void* hip_stream) {
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    int rc = fdh_launch_build_tables_debug(code_lengths320, hlit, litlen4096, dist512, build_status,
-                                           static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "table-build kernel launch");
-    return FDH_SUCCESS;
+    if (!have_device()) return no_device();
+    return launched("table-build kernel launch", fdh_launch_build_tables_debug(code_lengths320, hlit, litlen4096, dist512, build_status,
+                    stream_of(hip_stream)));
 }
 
 // ---- PNG scanline filters (the steps either side of the codec in the PNG pipeline) ----
+// (the row calls check their geometry between the pointers and the device, and the first three have no limit on n)
 static int png_args_ok(const void* a, const void* b, const void* c, const void* d, const void* st, uint32_t row_bytes,
                        uint32_t bpp) {
     if (!a || !b || !c || !d || !st) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
     if (row_bytes == 0) return fail(FDH_ERR_INVALID_ARGUMENT, "row_bytes must be positive");
     if (!(bpp == 1 || bpp == 2 || bpp == 3 || bpp == 4 || bpp == 6 || bpp == 8))
         return fail(FDH_ERR_INVALID_ARGUMENT, "bpp must be 1, 2, 3, 4, 6 or 8 (PNG's whole-byte pixel sizes)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    if (!have_device()) return no_device();
     return FDH_SUCCESS;
 }
 
 int fdh_png_unfilter_batch(const uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off,
                            uint32_t* png_status, uint64_t n, uint32_t row_bytes, uint32_t bpp, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    int rc = png_args_ok(filt, filt_off, pix, pix_off, png_status, row_bytes, bpp);
-    if (rc != FDH_SUCCESS) return rc;
-    rc = fdh_launch_png_unfilter(filt, filt_off, pix, pix_off, png_status, nullptr, nullptr, n, row_bytes, bpp,
-                                 static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "unfilter kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = png_args_ok(filt, filt_off, pix, pix_off, png_status, row_bytes, bpp)) return rc;
+    return launched("unfilter kernel launch", fdh_launch_png_unfilter(filt, filt_off, pix, pix_off, png_status, nullptr, nullptr, n,
+                    row_bytes, bpp, stream_of(hip_stream)));
 }
 
 int fdh_png_filter_batch(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
                          uint8_t* filt, const uint64_t* filt_off, uint32_t* png_status, uint64_t n, uint32_t row_bytes,
                          uint32_t bpp, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    int rc = png_args_ok(pix, pix_off, filt, filt_off, png_status, row_bytes, bpp);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_args_ok(pix, pix_off, filt, filt_off, png_status, row_bytes, bpp)) return rc;
     if (!types || !types_off) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
-    rc = fdh_launch_png_filter(pix, pix_off, types, types_off, filt, filt_off, png_status, n, row_bytes, bpp,
-                               static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "filter kernel launch");
-    return FDH_SUCCESS;
+    return launched("filter kernel launch", fdh_launch_png_filter(pix, pix_off, types, types_off, filt, filt_off, png_status, n, row_bytes,
+                    bpp, stream_of(hip_stream)));
 }
 
 int fdh_png_choose_filters_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off,
@@ -251,13 +188,10 @@ int fdh_png_choose_filters_batch(const uint8_t* pix, const uint64_t* pix_off, ui
     if (n == 0) return FDH_SUCCESS;
     if (row_bytes >= (1u << 25))
         return fail(FDH_ERR_INVALID_ARGUMENT, "row_bytes must be below 2^25 (a row's filter cost is summed in 32 bits)");
-    int rc = png_args_ok(pix, pix_off, types, types_off, png_status, row_bytes, bpp);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_args_ok(pix, pix_off, types, types_off, png_status, row_bytes, bpp)) return rc;
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
-    rc = fdh_launch_png_choose(pix, pix_off, types, types_off, png_status, n, row_bytes, bpp,
-                               static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "filter-selection kernel launch");
-    return FDH_SUCCESS;
+    return launched("filter-selection kernel launch", fdh_launch_png_choose(pix, pix_off, types, types_off, png_status, n, row_bytes, bpp,
+                    stream_of(hip_stream)));
 }
 
 int fdh_png_filter_deflate_ultrafast_batch(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types,
@@ -265,14 +199,11 @@ int fdh_png_filter_deflate_ultrafast_batch(const uint8_t* pix, const uint64_t* p
                                            uint32_t* out_len, uint32_t* png_status, uint64_t n, uint32_t row_bytes,
                                            uint32_t bpp, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    int rc = png_args_ok(pix, pix_off, out, out_off, png_status, row_bytes, bpp);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_args_ok(pix, pix_off, out, out_off, png_status, row_bytes, bpp)) return rc;
     if (!types || !types_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many buffers in one call (max 2^31-1)");
-    rc = fdh_launch_png_filter_deflate_ultrafast(pix, pix_off, types, types_off, out, out_off, out_len, png_status, n,
-                                                 row_bytes, bpp, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "filter + deflate kernel launch");
-    return FDH_SUCCESS;
+    return launched("filter + deflate kernel launch", fdh_launch_png_filter_deflate_ultrafast(pix, pix_off, types, types_off, out, out_off,
+                    out_len, png_status, n, row_bytes, bpp, stream_of(hip_stream)));
 }
 
 int fdh_inflate_png_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* filt, const uint64_t* filt_off,
@@ -280,47 +211,32 @@ int fdh_inflate_png_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* fi
                           uint32_t* png_status, uint64_t n, uint32_t flags, uint32_t row_bytes, uint32_t bpp,
                           void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    int rc = png_args_ok(filt, filt_off, pix, pix_off, png_status, row_bytes, bpp);
-    if (rc != FDH_SUCCESS) return rc;
-    rc = fdh_inflate_batch(in, in_off, filt, filt_off, out_len, status, adler, n, flags, hip_stream);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_args_ok(filt, filt_off, pix, pix_off, png_status, row_bytes, bpp)) return rc;
+    if (int rc = fdh_inflate_batch(in, in_off, filt, filt_off, out_len, status, adler, n, flags, hip_stream)) return rc;
     // same stream: the scanlines are reconstructed as soon as the decode kernels have finished, only
-    // for the streams that decoded (status 0) -- the rest gets png_status 3 -- and that decoded to
+    // for the streams that decoded (status 0) -- the rest gets FDH_PNG_STATUS_SKIPPED -- and that decoded to
     // exactly the bytes of their slot: a stream that ends early would leave stale bytes behind it
-    // (png_status 2; the png crate treats short IDAT data as an error as well)
-    rc = fdh_launch_png_unfilter(filt, filt_off, pix, pix_off, png_status, status, out_len, n, row_bytes, bpp,
-                                 static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "unfilter kernel launch");
-    return FDH_SUCCESS;
+    // (FDH_PNG_STATUS_BAD_SIZES; the png crate treats short IDAT data as an error as well)
+    return launched("unfilter kernel launch", fdh_launch_png_unfilter(filt, filt_off, pix, pix_off, png_status, status, out_len, n,
+                    row_bytes, bpp, stream_of(hip_stream)));
 }
 
 // ---- PNG files: CRC-32, framing, container scan, IDAT gather (png_file.hip) ----
 int fdh_crc32_batch(const uint8_t* data, const uint64_t* off, const uint32_t* len, const uint32_t* seed, uint32_t* crc,
                     uint32_t* status, uint64_t n, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    if (!off || !crc || !status) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many ranges in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    int rc = fdh_launch_crc32(data, off, len, seed, crc, status, n, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "CRC-32 kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({off, crc, status}, "null metadata pointer", n, "ranges")) return rc;
+    return launched("CRC-32 kernel launch", fdh_launch_crc32(data, off, len, seed, crc, status, n, stream_of(hip_stream)));
 }
 
 uint64_t fdh_png_file_bound(uint64_t rows, uint64_t row_bytes) {
     return fdh_ultrafast_bound(rows * (row_bytes + 1)) + FDH_PNG_FILE_PREFIX + FDH_PNG_FILE_SUFFIX;
 }
 
-// the fifteen depth / colour-type pairs of the PNG specification (11.2.2, table 11.1)
-static bool png_pair_ok(uint32_t depth, uint32_t colour) {
-    const bool low = depth == 1 || depth == 2 || depth == 4;
-    if (colour == 0) return low || depth == 8 || depth == 16;
-    if (colour == 3) return low || depth == 8;
-    return (colour == 2 || colour == 4 || colour == 6) && (depth == 8 || depth == 16);
-}
-
+// (the calls that take a geometry refuse a bad one before anything else, an empty batch included)
 static int png_geometry_ok(uint32_t width, uint32_t bit_depth, uint32_t colour_type) {
     if (width == 0 || width > 0x7FFFFFFFu) return fail(FDH_ERR_INVALID_ARGUMENT, "width must be 1 .. 2^31-1");
-    if (!png_pair_ok(bit_depth, colour_type))
+    if (!fdh::png_pair_ok(bit_depth, colour_type))
         return fail(FDH_ERR_INVALID_ARGUMENT, "bit depth / colour type is not one of the PNG specification's fifteen pairs");
     return FDH_SUCCESS;
 }
@@ -328,110 +244,68 @@ static int png_geometry_ok(uint32_t width, uint32_t bit_depth, uint32_t colour_t
 int fdh_png_frame_batch(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height,
                         uint32_t* file_len, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
                         uint32_t colour_type, void* hip_stream) {
-    int rc = png_geometry_ok(width, bit_depth, colour_type);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_geometry_ok(width, bit_depth, colour_type)) return rc;
     if (n == 0) return FDH_SUCCESS;
-    if (!file || !file_off || !idat_len || !height || !file_len || !png_status) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    rc = fdh_launch_png_frame(file, file_off, idat_len, height, file_len, png_status, n, width, bit_depth, colour_type,
-                              static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "PNG framing kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({file, file_off, idat_len, height, file_len, png_status}, "null pointer", n, "files")) return rc;
+    return launched("PNG framing kernel launch", fdh_launch_png_frame(file, file_off, idat_len, height, file_len, png_status, n, width,
+                    bit_depth, colour_type, stream_of(hip_stream)));
 }
 
 int fdh_png_scan_files_batch(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, fdh_png_info* info,
                              uint64_t n, uint32_t flags, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
-    if (!file || !file_off || !info) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    int rc = fdh_launch_png_scan(file, file_off, file_len, info, n, (flags & FDH_PNG_FLAG_IGNORE_CRC) ? 0 : 1,
-                                 (flags & FDH_PNG_FLAG_ADAM7) ? 1 : 0, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "PNG scan kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({file, file_off, info}, "null pointer", n, "files")) return rc;
+    return launched("PNG scan kernel launch", fdh_launch_png_scan(file, file_off, file_len, info, n,
+                    (flags & FDH_PNG_FLAG_IGNORE_CRC) ? 0 : 1, (flags & FDH_PNG_FLAG_ADAM7) ? 1 : 0, stream_of(hip_stream)));
 }
 
 int fdh_png_gather_idat_batch(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint8_t* comp,
                               const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n,
                               uint32_t width, uint32_t bit_depth, uint32_t colour_type, void* hip_stream) {
-    int rc = png_geometry_ok(width, bit_depth, colour_type);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_geometry_ok(width, bit_depth, colour_type)) return rc;
     if (n == 0) return FDH_SUCCESS;
-    if (!file || !file_off || !info || !comp || !comp_off || !comp_len || !png_status)
-        return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    rc = fdh_launch_png_gather(file, file_off, info, comp, comp_off, comp_len, png_status, n, width, bit_depth,
-                               colour_type, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "IDAT gather kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({file, file_off, info, comp, comp_off, comp_len, png_status}, "null pointer", n, "files")) return rc;
+    return launched("IDAT gather kernel launch", fdh_launch_png_gather(file, file_off, info, comp, comp_off, comp_len, png_status, n, width,
+                    bit_depth, colour_type, stream_of(hip_stream)));
 }
 
 // ---- PNG decode to RGBA8: PLTE / tRNS (png_file.hip), expansion (png_expand.hip) ----
 int fdh_png_colour_batch(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint32_t* pal,
                          uint32_t* colour, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
                          uint32_t colour_type, void* hip_stream) {
-    int rc = png_geometry_ok(width, bit_depth, colour_type);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_geometry_ok(width, bit_depth, colour_type)) return rc;
     if (n == 0) return FDH_SUCCESS;
-    if (!file || !file_off || !info || !colour || !png_status || (colour_type == 3 && !pal))
-        return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many files in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    rc = fdh_launch_png_colour(file, file_off, info, pal, colour, png_status, n, width, bit_depth, colour_type,
-                               static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "PLTE / tRNS kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({file, file_off, info, colour, png_status, colour_type == 3 ? pal : png_status}, "null pointer", n, "files")) return rc;
+    return launched("PLTE / tRNS kernel launch", fdh_launch_png_colour(file, file_off, info, pal, colour, png_status, n, width, bit_depth,
+                    colour_type, stream_of(hip_stream)));
 }
 
 int fdh_png_expand_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
                          const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* png_status,
                          uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type, void* hip_stream) {
-    int rc = png_geometry_ok(width, bit_depth, colour_type);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_geometry_ok(width, bit_depth, colour_type)) return rc;
     if (n == 0) return FDH_SUCCESS;
-    if (!pix || !pix_off || !rgba || !rgba_off || !png_status || (colour_type == 3 && !pal))
-        return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    const uint32_t channels = colour_type == 2 ? 3 : colour_type == 4 ? 2 : colour_type == 6 ? 4 : 1;
-    const uint64_t row_bytes = ((uint64_t)width * channels * bit_depth + 7) / 8;
-    rc = fdh_launch_png_expand(pix, pix_off, rgba, rgba_off, pal, colour, upstream, png_status, n, width, row_bytes,
-                               bit_depth, colour_type, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "RGBA expansion kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({pix, pix_off, rgba, rgba_off, png_status, colour_type == 3 ? pal : png_status}, "null pointer", n, "images")) return rc;
+    const uint64_t row_bytes = fdh::png_row_bytes(width, fdh::png_pixel_bits(bit_depth, colour_type));
+    return launched("RGBA expansion kernel launch", fdh_launch_png_expand(pix, pix_off, rgba, rgba_off, pal, colour, upstream, png_status,
+                    n, width, row_bytes, bit_depth, colour_type, stream_of(hip_stream)));
 }
 
 // ---- PNG decode: Adam7 interlaced images (png_adam7.hip) ----
 uint64_t fdh_png_adam7_size(uint32_t width, uint32_t height, uint32_t bit_depth, uint32_t colour_type) {
-    if (width == 0 || height == 0 || !png_pair_ok(bit_depth, colour_type)) return 0;
-    static const uint32_t x0[7] = {0, 4, 0, 2, 0, 1, 0}, y0[7] = {0, 0, 4, 0, 2, 0, 1};
-    static const uint32_t dx[7] = {8, 8, 4, 4, 2, 2, 1}, dy[7] = {8, 8, 8, 4, 4, 2, 2};
-    const uint64_t bits = (colour_type == 2 ? 3 : colour_type == 4 ? 2 : colour_type == 6 ? 4 : 1) * (uint64_t)bit_depth;
-    uint64_t total = 0;
-    for (int p = 0; p < 7; p++) {
-        const uint64_t pw = width > x0[p] ? ((uint64_t)width - x0[p] + dx[p] - 1) / dx[p] : 0;
-        const uint64_t ph = height > y0[p] ? ((uint64_t)height - y0[p] + dy[p] - 1) / dy[p] : 0;
-        if (pw && ph) total += ph * (1 + (pw * bits + 7) / 8);
-    }
-    return total;
+    if (width == 0 || height == 0 || !fdh::png_pair_ok(bit_depth, colour_type)) return 0;
+    return fdh::png_adam7_size(width, height, fdh::png_pixel_bits(bit_depth, colour_type), 1);
 }
 
 int fdh_png_unfilter_interlaced_batch(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off,
                                       const uint8_t* method, const uint32_t* upstream, const uint32_t* upstream_len,
                                       uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
                                       uint32_t colour_type, void* hip_stream) {
-    int rc = png_geometry_ok(width, bit_depth, colour_type);
-    if (rc != FDH_SUCCESS) return rc;
+    if (int rc = png_geometry_ok(width, bit_depth, colour_type)) return rc;
     if (n == 0) return FDH_SUCCESS;
-    if (!filt || !filt_off || !pix || !pix_off || !png_status) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer");
-    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    rc = fdh_launch_png_adam7(filt, filt_off, pix, pix_off, method, upstream, upstream_len, png_status, n, width, bit_depth,
-                              colour_type, static_cast<hipStream_t>(hip_stream));
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "Adam7 reconstruction / placement kernel launch");
-    return FDH_SUCCESS;
+    if (int rc = batch_ok({filt, filt_off, pix, pix_off, png_status}, "null pointer", n, "images")) return rc;
+    return launched("Adam7 reconstruction / placement kernel launch", fdh_launch_png_adam7(filt, filt_off, pix, pix_off, method, upstream,
+                    upstream_len, png_status, n, width, bit_depth, colour_type, stream_of(hip_stream)));
 }
 
 // ---- general encoder (levels 1-3 / RLE): per-device workspace, grown on demand, never shrunk ----
@@ -473,8 +347,8 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
     if (mode != FDH_MODE_LEVEL1 && mode != FDH_MODE_RLE && mode != FDH_MODE_LEVEL2 && mode != FDH_MODE_LEVEL3)
         return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    if (!have_device()) return no_device();
+    hipStream_t stream = stream_of(hip_stream);
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return fail(FDH_ERR_INVALID_ARGUMENT, "device ordinal out of range");
@@ -539,9 +413,9 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
                   "hipMalloc(block records)");
     if (rc == FDH_SUCCESS) rc = grow(&w.nblocks, &w.nblock_bytes, (size_t)n * 4, "hipMalloc(block counts)");
     if (rc != FDH_SUCCESS) return rc;
-    rc = fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, kind, w.hash, w.matches, w.blocks,
-                                    static_cast<uint32_t*>(w.nblocks), waves, lanes, stream);
-    if (rc != 0) return hip_fail(static_cast<hipError_t>(rc), "general-encoder kernel launch");
+    rc = launched("general-encoder kernel launch", fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, kind, w.hash, w.matches,
+                                                                          w.blocks, static_cast<uint32_t*>(w.nblocks), waves, lanes, stream));
+    if (rc != FDH_SUCCESS) return rc;
     // the workspace is per device, not per stream: calls are serialised by finishing this one
     HIP_TRY(hipStreamSynchronize(stream));
     return FDH_SUCCESS;
@@ -592,7 +466,7 @@ static int inflate_growing(const uint8_t* input, size_t input_len, size_t maxlen
     if (!output || !output_len || !stream_status) return fail(FDH_ERR_INVALID_ARGUMENT, "null result pointer");
     *output = nullptr;
     *output_len = 0;
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    if (!have_device()) return no_device();
     if (input_len >= (1ull << 31)) return fail(FDH_ERR_INVALID_ARGUMENT, "stream too large (>= 2 GiB)");
     if (maxlen > 0xFFFFFFF0ull) maxlen = 0xFFFFFFF0ull;
     DevBuf d_in;
@@ -626,7 +500,7 @@ static int compress_one(int kind, const uint8_t* input, size_t input_len, uint8_
     const bool stored = kind == 1;
     if (!output || !output_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null result pointer");
     if (input_len >= 0xFFFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "buffer too large (>= 4 GiB)");
-    if (!have_device()) return fail(FDH_ERR_NO_DEVICE, "no HIP device: fdeflate_hip has no CPU fallback");
+    if (!have_device()) return no_device();
     size_t cap = (size_t)(stored ? fdh_stored_size(input_len) : (kind == 0 ? fdh_ultrafast_bound(input_len) : fdh_compress_bound(input_len)));
     DevBuf d_in, d_out, d_meta;
     HIP_TRY(d_in.alloc(input_len));

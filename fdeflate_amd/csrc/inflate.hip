@@ -1004,10 +1004,8 @@ extern "C" int fdh_debug_s2time(uint32_t* host) {
 
 // ---- host side: the per-device tables and hooks, then the chains of launches -------------------------------------
 
-// inflate_seg3.hip (a translation unit of its own: it builds in a fraction of the time of this one)
-int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);
-
-#include "inflate_launch.h"  // DeviceState, the grid sizes, CallScratch, SideFork, launch()
+#include "launch.h"  // (fdh_launch_seg3: inflate_seg3.hip is a translation unit of its own, it builds in a fraction of the time of this one)
+#include "inflate_launch.h" // DeviceState, the grid sizes, CallScratch, SideFork, launch()
 
 // (introspection, tests / soak: resume records that read zero under a status that promised one, since the library was loaded)
 extern "C" int fdh_debug_lost_records(unsigned int* count) {

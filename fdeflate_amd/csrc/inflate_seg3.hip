@@ -1,5 +1,6 @@
 // inflate_seg3.hip -- the landing decoder's kernel (inflate_seg3.h) and its launch.
 #include "inflate_seg3.h"
+#include "launch.h"
 
 namespace fdh {
 

@@ -1,0 +1,91 @@
+// launch.h -- the boundary between the host side of the ABI (fdeflate_hip.cpp, stream_decompressor.cpp, multi_gpu.cpp)
+// and the files that hold the kernels: every launcher is declared here, once, and both its callers and the file that
+// defines it include this header, so a definition that disagrees with its declaration does not compile.  Not part of
+// the public header.  A launcher returns 0 or a hipError_t (-1: an argument no kernel was built for).  Behind the
+// declarations: what the launchers themselves share.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+
+#include "../../include/fdeflate_hip.h"
+
+namespace fdh { struct SegArgs; }
+int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);  // inflate_seg3.hip, for inflate.hip
+
+extern "C" {
+void fdh_set_last_error(const char* msg);  // fdeflate_hip.cpp: fdh_last_error's text, for the other host files
+// inflate.hip
+int fdh_launch_inflate(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                       uint32_t* status, uint32_t* adler, uint64_t n, uint32_t flags, void* resume_io, hipStream_t stream);
+int fdh_launch_canon_build(hipStream_t stream, uint32_t* host_status);
+int fdh_launch_build_tables_debug(const uint8_t* code_lengths, uint32_t hlit, uint32_t* litlen, uint32_t* dist, uint32_t* build_status,
+                                  hipStream_t stream);
+// deflate_stored.hip
+int fdh_launch_deflate_stored(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                              uint64_t n, hipStream_t stream);
+int fdh_launch_copy_lines(void* dst, const void* src, size_t bytes, hipStream_t stream);
+// deflate_ultrafast.hip
+int fdh_launch_deflate_ultrafast(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                                 uint64_t n, hipStream_t stream);
+int fdh_launch_png_filter_deflate_ultrafast(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
+                                            uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint32_t* png_status, uint64_t n,
+                                            uint32_t row_bytes, uint32_t bpp, hipStream_t stream);
+// deflate_general.hip
+int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                               uint64_t n, int kind, void* hash, void* matches, void* blocks, uint32_t* nblocks, unsigned waves,
+                               unsigned lanes, hipStream_t stream);
+size_t fdh_deflate_general_hash_bytes(int kind);
+size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n);
+size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n);
+size_t fdh_deflate_general_match_record_bytes(void);
+size_t fdh_deflate_general_block_record_bytes(void);
+// png_filter.hip
+int fdh_launch_png_unfilter(const uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, uint32_t* status,
+                            const uint32_t* gate, const uint32_t* gate_len, uint64_t n, uint32_t row_bytes, uint32_t bpp,
+                            hipStream_t stream);
+int fdh_launch_png_filter(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off, uint8_t* filt,
+                          const uint64_t* filt_off, uint32_t* status, uint64_t n, uint32_t row_bytes, uint32_t bpp, hipStream_t stream);
+// png_choose.hip
+int fdh_launch_png_choose(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off, uint32_t* status,
+                          uint64_t n, uint32_t row_bytes, uint32_t bpp, hipStream_t stream);
+// png_file.hip
+int fdh_launch_crc32(const uint8_t* data, const uint64_t* off, const uint32_t* len, const uint32_t* seed, uint32_t* crc, uint32_t* status,
+                     uint64_t n, hipStream_t stream);
+int fdh_launch_png_frame(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height, uint32_t* file_len,
+                         uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, fdh_png_info* info, uint64_t n,
+                        int verify_crc, int adam7, hipStream_t stream);
+int fdh_launch_png_gather(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint8_t* comp, const uint64_t* comp_off,
+                          uint32_t* comp_len, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type,
+                          hipStream_t stream);
+int fdh_launch_png_colour(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint32_t* pal, uint32_t* colour,
+                          uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+// png_expand.hip
+int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off, const uint32_t* pal,
+                          const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n, uint32_t width,
+                          uint64_t row_bytes, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+// png_adam7.hip
+int fdh_launch_png_adam7(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, const uint8_t* method,
+                         const uint32_t* upstream, const uint32_t* upstream_len, uint32_t* status, uint64_t n, uint32_t width,
+                         uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+}
+
+namespace fdh {
+
+// an environment variable as an integer (the launchers' overrides for tests and A/B runs); `fallback` where it is not set
+inline int env_int(const char* name, int fallback) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : fallback;
+}
+
+// Wavefronts per image for the kernels that hand an image's bands b, b + Y, .. to wavefront b of Y: Y is chosen so that
+// a small batch of tall images still fills the device; the environment variable `name` (1 .. 65535) sets it.
+inline uint32_t png_waves_per_image(uint64_t n, const char* name) {
+    const int forced = env_int(name, 0);
+    if (forced >= 1 && forced <= 65535) return (uint32_t)forced;
+    return (uint32_t)std::min<uint64_t>(4096, (32768 + n - 1) / n);
+}
+
+}  // namespace fdh

@@ -11,17 +11,14 @@
 //
 // (The Python layer has the one-process-per-GPU form of the same thing: fdeflate_amd/distributed.py
 // over torch.distributed, which is what bench.py uses.)
-#include "../../include/fdeflate_hip.h"
+#include "launch.h"
 
 #include <dlfcn.h>
-#include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <mutex>
 #include <string>
 #include <vector>
-
-extern "C" void fdh_set_last_error(const char* msg);
 
 namespace {
 

@@ -25,10 +25,9 @@
 // bytes are then gathered in the largest unit that divides both the pixel and the 16 bytes (1, 2, 4 or 8 bytes: one
 // byte for RGB8), pixels narrower than a byte bit field by bit field.  One instance per pixel size in bits.
 #include "device_common.h"
+#include "launch.h"
+#include "png_common.h"
 #include "png_rows.h"
-
-#include <algorithm>
-#include <cstdlib>
 
 namespace fdh {
 
@@ -47,23 +46,6 @@ struct Adam7Args {
     uint32_t bits;       // per pixel
 };
 
-// The pass tables (PNG specification 8.2), pass p in nibble p: first column and row, log2 of the column and row steps.
-constexpr uint32_t kAdam7X0 = 0x0102040u, kAdam7Y0 = 0x1020400u, kAdam7LogDx = 0x0112233u, kAdam7LogDy = 0x1122333u;
-__device__ __forceinline__ constexpr uint32_t adam7_nib(uint32_t table, uint32_t p) { return (table >> (4 * p)) & 15u; }
-
-// Width and height of pass p of a width x height image (method 0: one pass, the image itself); 0 x 0 if it is empty.
-__device__ __forceinline__ void adam7_pass_dims(uint32_t method, uint32_t p, uint64_t width, uint64_t height, uint64_t& pw, uint64_t& ph) {
-    if (method == 0) {
-        pw = p == 0 ? width : 0;
-        ph = p == 0 ? height : 0;
-    } else {
-        const uint32_t x0 = adam7_nib(kAdam7X0, p), y0 = adam7_nib(kAdam7Y0, p), lx = adam7_nib(kAdam7LogDx, p), ly = adam7_nib(kAdam7LogDy, p);
-        pw = width > x0 ? (width - x0 + (1u << lx) - 1) >> lx : 0;
-        ph = height > y0 ? (height - y0 + (1u << ly) - 1) >> ly : 0;
-    }
-    if (pw == 0 || ph == 0) pw = ph = 0;
-}
-
 // What both kernels know of image i: its slots, its height, its method and its status before any filter type is seen.
 struct Adam7Image {
     uint64_t f0, d0, height;
@@ -77,27 +59,21 @@ __device__ __forceinline__ Adam7Image adam7_image(const Adam7Args& a, uint64_t i
     g.d0 = a.pix_off[i];
     g.method = a.method ? a.method[i] : 1u;
     g.height = (d1 - g.d0) / a.row_bytes;
-    g.status = 0;
-    if (a.upstream && a.upstream[i] != 0) g.status = 3;
-    else if (a.upstream_len && (uint64_t)a.upstream_len[i] != f1 - g.f0) g.status = 2;
-    else if (g.method > 1 || g.height * a.row_bytes != d1 - g.d0) g.status = 2;
-    else {
+    g.status = kPngOk;
+    if (a.upstream && a.upstream[i] != 0) g.status = kPngSkipped;
+    else if (a.upstream_len && (uint64_t)a.upstream_len[i] != f1 - g.f0) g.status = kPngBadSizes;
+    else if (g.method > 1 || g.height * a.row_bytes != d1 - g.d0) g.status = kPngBadSizes;
+    else {  // png_adam7_size(a.width, g.height, a.bits, g.method), written out: as a call all fifteen kernels compile to other code
         uint64_t total = 0;
 #pragma unroll
         for (uint32_t p = 0; p < 7; p++) {
             uint64_t pw, ph;
             adam7_pass_dims(g.method, p, a.width, g.height, pw, ph);
-            total += ph * (1 + (pw * a.bits + 7) / 8);  // (an empty pass: 0 rows)
+            total += ph * (1 + png_row_bytes(pw, a.bits));  // (an empty pass: 0 rows)
         }
-        if (total != f1 - g.f0) g.status = 2;
+        if (total != f1 - g.f0) g.status = kPngBadSizes;
     }
     return g;
-}
-
-// lane j gets lane j - 1's value (lane 0: 0).  The same shift as png_from_lane_below in png_filter.hip, which is not
-// among the helpers that moved to png_rows.h and stays where it is.
-__device__ __forceinline__ uint32_t adam7_from_lane_below(uint32_t x) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
 }
 
 template <int BPP>
@@ -105,7 +81,7 @@ __global__ __launch_bounds__(kWave) void png_adam7_recon_kernel(Adam7Args a) {
     const uint64_t i = blockIdx.x;
     const uint32_t lane = threadIdx.x;
     const Adam7Image g = adam7_image(a, i);
-    if (g.status != 0) {
+    if (g.status != kPngOk) {
         if (lane == 0) a.status[i] = g.status;
         return;
     }
@@ -130,7 +106,7 @@ __global__ __launch_bounds__(kWave) void png_adam7_recon_kernel(Adam7Args a) {
             for (uint32_t p = 0; p < 7; p++) {
                 uint64_t pw, ph;
                 adam7_pass_dims(g.method, p, a.width, g.height, pw, ph);
-                const uint64_t stride = 1 + (pw * a.bits + 7) / 8;
+                const uint64_t stride = 1 + png_row_bytes(pw, a.bits);
                 if (R >= before && R < before + ph) {
                     at = base + (R - before) * stride + 1;
                     len = stride - 1;
@@ -158,7 +134,7 @@ __global__ __launch_bounds__(kWave) void png_adam7_recon_kernel(Adam7Args a) {
             const uint32_t c = s - lane - 1;  // (wraps for the lanes that have not started)
             const bool on = mine && c < nchunks;
             const uint4 f = fnext;
-            uint4 u = make_uint4(adam7_from_lane_below(last.x), adam7_from_lane_below(last.y), adam7_from_lane_below(last.z), adam7_from_lane_below(last.w));
+            uint4 u = make_uint4(png_from_lane_below(last.x), png_from_lane_below(last.y), png_from_lane_below(last.z), png_from_lane_below(last.w));
             if (from_memory) u = unext;
             if (first) u = make_uint4(0, 0, 0, 0);
             if (mine && c + 1 < nchunks) {
@@ -177,7 +153,7 @@ __global__ __launch_bounds__(kWave) void png_adam7_recon_kernel(Adam7Args a) {
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
     }
-    if (lane == 0) a.status[i] = bad ? 1u : 0u;
+    if (lane == 0) a.status[i] = bad ? kPngBadFilterType : kPngOk;
 }
 
 // The pass rows an even picture row y draws on, by the column's class: odd x; x % 4 == 2; x % 8 == 4; x % 8 == 0.
@@ -189,7 +165,7 @@ struct Adam7RowSources {
 // BITS >= 8: U bytes of a pixel at a time.  BITS < 8: bit fields.
 template <int BITS>
 struct Adam7Place {
-    static constexpr int B = BITS >= 8 ? BITS / 8 : 1;                                  // bytes per pixel
+    static constexpr int B = (int)png_bpp(BITS);                                        // bytes per pixel
     static constexpr int U = B % 8 == 0 ? 8 : B % 4 == 0 ? 4 : B % 2 == 0 ? 2 : 1;      // bytes per load
     static constexpr int PPB = BITS >= 8 ? 1 : 8 / BITS;                                // pixels per byte
 
@@ -274,9 +250,9 @@ __global__ __launch_bounds__(kWave) void png_adam7_place_kernel(Adam7Args a) {
     __shared__ uint64_t s_base[7], s_stride[7];  // of pass p: where its first type byte lies in the filt slot; 1 + row bytes
     const uint64_t i = blockIdx.x;
     const uint32_t lane = threadIdx.x;
-    if (uni(a.status[i]) >= 2) return;  // (the reconstruction kernel's verdict: 2 and 3 write nothing)
+    if (uni(a.status[i]) > kPngBadFilterType) return;  // (kPngBadSizes, kPngSkipped: refused by the reconstruction kernel, nothing is written)
     const Adam7Image g = adam7_image(a, i);
-    if (g.status != 0) return;
+    if (g.status != kPngOk) return;
     const uint64_t rb = a.row_bytes, rows = g.height;
     const uint64_t bands = (rows + kPlaceBand - 1) / kPlaceBand;
     if (blockIdx.y >= bands) return;
@@ -286,7 +262,7 @@ __global__ __launch_bounds__(kWave) void png_adam7_place_kernel(Adam7Args a) {
             uint64_t pw, ph;
             adam7_pass_dims(g.method, p, a.width, rows, pw, ph);
             s_base[p] = base;
-            s_stride[p] = 1 + (pw * a.bits + 7) / 8;
+            s_stride[p] = 1 + png_row_bytes(pw, a.bits);
             base += ph * s_stride[p];
         }
     }
@@ -351,32 +327,27 @@ extern "C" int fdh_launch_png_adam7(uint8_t* filt, const uint64_t* filt_off, uin
                                     uint32_t* status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type,
                                     hipStream_t stream) {
     if (n == 0) return 0;
-    const uint32_t channels = colour_type == 2 ? 3 : colour_type == 4 ? 2 : colour_type == 6 ? 4 : 1;
-    const uint32_t bits = channels * bit_depth;
-    const uint64_t row_bytes = ((uint64_t)width * bits + 7) / 8;
-    uint32_t waves = (uint32_t)std::min<uint64_t>(4096, (32768 + n - 1) / n);
-    if (const char* v = getenv("FDH_PNG_ADAM7_WAVES")) {
-        const int w = atoi(v);
-        if (w >= 1 && w <= 65535) waves = (uint32_t)w;
-    }
+    const uint32_t bits = fdh::png_pixel_bits(bit_depth, colour_type);
+    const uint64_t row_bytes = fdh::png_row_bytes(width, bits);
+    const uint32_t waves = fdh::png_waves_per_image(n, "FDH_PNG_ADAM7_WAVES");
     fdh::Adam7Args a{filt, filt_off, pix, pix_off, method, upstream, upstream_len, status, n, row_bytes, width, bits};
     const dim3 block(fdh::kWave), grid((unsigned)n), grid2((unsigned)n, waves);
-#define FDH_ADAM7_CASE(BITS, BPP)                                                               \
+#define FDH_ADAM7_CASE(BITS)                                                                    \
     case BITS:                                                                                  \
-        hipLaunchKernelGGL((fdh::png_adam7_recon_kernel<BPP>), grid, block, 0, stream, a);      \
+        hipLaunchKernelGGL((fdh::png_adam7_recon_kernel<(int)fdh::png_bpp(BITS)>), grid, block, 0, stream, a); \
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return (int)e;                   \
         hipLaunchKernelGGL((fdh::png_adam7_place_kernel<BITS>), grid2, block, 0, stream, a);    \
         break;
     switch (bits) {
-        FDH_ADAM7_CASE(1, 1)
-        FDH_ADAM7_CASE(2, 1)
-        FDH_ADAM7_CASE(4, 1)
-        FDH_ADAM7_CASE(8, 1)
-        FDH_ADAM7_CASE(16, 2)
-        FDH_ADAM7_CASE(24, 3)
-        FDH_ADAM7_CASE(32, 4)
-        FDH_ADAM7_CASE(48, 6)
-        FDH_ADAM7_CASE(64, 8)
+        FDH_ADAM7_CASE(1)
+        FDH_ADAM7_CASE(2)
+        FDH_ADAM7_CASE(4)
+        FDH_ADAM7_CASE(8)
+        FDH_ADAM7_CASE(16)
+        FDH_ADAM7_CASE(24)
+        FDH_ADAM7_CASE(32)
+        FDH_ADAM7_CASE(48)
+        FDH_ADAM7_CASE(64)
         default: return -1;
     }
 #undef FDH_ADAM7_CASE

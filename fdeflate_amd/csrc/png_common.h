@@ -1,0 +1,96 @@
+// png_common.h -- what every part of the PNG layer agrees on, once, for host and device code: the legal depth / colour
+// pairs, the sizes that follow from a geometry, the Adam7 pass tables with the size of an interlaced stream, and the
+// per-image status values.  Nothing here touches the device: the header compiles in a plain C++ program as well.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/fdeflate_hip.h"  // FDH_PNG_STATUS_*: the public names of the status values
+
+#if defined(__HIPCC__)
+#define FDH_PNG_FN __host__ __device__ __forceinline__ constexpr
+#else
+#define FDH_PNG_FN inline constexpr
+#endif
+
+namespace fdh {
+
+// ---- per-image status values (include/fdeflate_hip.h describes them call by call) ----
+// the row calls: a filter type above 4; slots that do not fit the geometry (or each other); refused by an earlier step
+constexpr uint32_t kPngOk = 0, kPngBadFilterType = 1, kPngBadSizes = 2, kPngSkipped = 3;
+// info.status of the container scan: the first finding in file order
+constexpr uint32_t kPngScanNoSignature = 1, kPngScanTruncated = 2, kPngScanBadIhdr = 3, kPngScanInterlaced = 4;
+constexpr uint32_t kPngScanChunkStructure = 5, kPngScanCrcMismatch = 6;
+// the decode steps behind the scan: the file's geometry is not the call's; the gather's destination; OR-ed into kPngOk by the expansion
+constexpr uint32_t kPngOtherGeometry = 7, kPngCompSlotTooSmall = 8, kPngIndexOutsidePalette = 9, kPngBadPlte = 10, kPngBadTrns = 11;
+
+static_assert(kPngOk == FDH_PNG_STATUS_OK && kPngBadFilterType == FDH_PNG_STATUS_BAD_FILTER_TYPE && kPngBadSizes == FDH_PNG_STATUS_BAD_SIZES &&
+              kPngSkipped == FDH_PNG_STATUS_SKIPPED && kPngScanNoSignature == FDH_PNG_STATUS_SCAN_NO_SIGNATURE &&
+              kPngScanTruncated == FDH_PNG_STATUS_SCAN_TRUNCATED && kPngScanBadIhdr == FDH_PNG_STATUS_SCAN_BAD_IHDR &&
+              kPngScanInterlaced == FDH_PNG_STATUS_SCAN_INTERLACED && kPngScanChunkStructure == FDH_PNG_STATUS_SCAN_CHUNK_STRUCTURE &&
+              kPngScanCrcMismatch == FDH_PNG_STATUS_SCAN_CRC_MISMATCH && kPngOtherGeometry == FDH_PNG_STATUS_OTHER_GEOMETRY &&
+              kPngCompSlotTooSmall == FDH_PNG_STATUS_COMP_SLOT_TOO_SMALL && kPngIndexOutsidePalette == FDH_PNG_STATUS_INDEX_OUTSIDE_PALETTE &&
+              kPngBadPlte == FDH_PNG_STATUS_BAD_PLTE && kPngBadTrns == FDH_PNG_STATUS_BAD_TRNS, "the public header names the same values");
+
+// ---- geometry ----
+// the fifteen depth / colour-type pairs of the PNG specification (11.2.2, table 11.1)
+FDH_PNG_FN bool png_pair_ok(uint32_t depth, uint32_t colour) {
+    switch (colour) {
+        case 0: return depth == 1 || depth == 2 || depth == 4 || depth == 8 || depth == 16;
+        case 3: return depth == 1 || depth == 2 || depth == 4 || depth == 8;
+        case 2:
+        case 4:
+        case 6: return depth == 8 || depth == 16;
+        default: return false;
+    }
+}
+FDH_PNG_FN uint32_t png_channels(uint32_t colour) { return colour == 2 ? 3 : colour == 4 ? 2 : colour == 6 ? 4 : 1; }
+FDH_PNG_FN uint32_t png_pixel_bits(uint32_t depth, uint32_t colour) { return png_channels(colour) * depth; }
+// bytes of a packed row of `width` pixels of `bits` bits (the last byte padded)
+FDH_PNG_FN uint64_t png_row_bytes(uint64_t width, uint64_t bits) { return (width * bits + 7) / 8; }
+// the pixel size of the filters: whole bytes, 1 for the narrower pixels (PNG specification 9.2)
+FDH_PNG_FN uint32_t png_bpp(uint32_t bits) { return bits >= 8 ? bits / 8 : 1; }
+
+// ---- Adam7 (PNG specification 8.2) ----
+// The pass tables, pass p in nibble p: first column and row, log2 of the column and row steps.
+constexpr uint32_t kAdam7X0 = 0x0102040u, kAdam7Y0 = 0x1020400u, kAdam7LogDx = 0x0112233u, kAdam7LogDy = 0x1122333u;
+FDH_PNG_FN uint32_t adam7_nib(uint32_t table, uint32_t p) { return (table >> (4 * p)) & 15u; }
+
+// Width and height of pass p of a width x height image (method 0: one pass, the image itself); 0 x 0 if it is empty.
+FDH_PNG_FN void adam7_pass_dims(uint32_t method, uint32_t p, uint64_t width, uint64_t height, uint64_t& pw, uint64_t& ph) {
+    if (method == 0) {
+        pw = p == 0 ? width : 0;
+        ph = p == 0 ? height : 0;
+    } else {
+        const uint32_t x0 = adam7_nib(kAdam7X0, p), y0 = adam7_nib(kAdam7Y0, p), lx = adam7_nib(kAdam7LogDx, p), ly = adam7_nib(kAdam7LogDy, p);
+        pw = width > x0 ? (width - x0 + (1u << lx) - 1) >> lx : 0;
+        ph = height > y0 ? (height - y0 + (1u << ly) - 1) >> ly : 0;
+    }
+    if (pw == 0 || ph == 0) pw = ph = 0;
+}
+
+// The bytes the IDAT stream of a width x height image of `bits` bits per pixel decodes to: every row of every pass
+// with its type byte (method 1), or height * (1 + row bytes) (method 0).  An empty pass has no bytes.  adam7_image
+// (png_adam7.hip) checks every slot against this sum, written out there from the same adam7_pass_dims and png_row_bytes.
+FDH_PNG_FN uint64_t png_adam7_size(uint32_t width, uint64_t height, uint32_t bits, uint32_t method) {
+    uint64_t total = 0;
+    for (uint32_t p = 0; p < 7; p++) {
+        uint64_t pw = 0, ph = 0;
+        adam7_pass_dims(method, p, width, height, pw, ph);
+        total += ph * (1 + png_row_bytes(pw, bits));
+    }
+    return total;
+}
+
+// ---- values that follow from the specification ----
+static_assert(png_pair_ok(1, 0) && png_pair_ok(2, 0) && png_pair_ok(4, 0) && png_pair_ok(8, 0) && png_pair_ok(16, 0) &&
+              png_pair_ok(8, 2) && png_pair_ok(16, 2) && png_pair_ok(1, 3) && png_pair_ok(2, 3) && png_pair_ok(4, 3) &&
+              png_pair_ok(8, 3) && png_pair_ok(8, 4) && png_pair_ok(16, 4) && png_pair_ok(8, 6) && png_pair_ok(16, 6),
+              "the fifteen pairs");
+static_assert(!png_pair_ok(16, 3) && !png_pair_ok(8, 1) && !png_pair_ok(4, 2) && !png_pair_ok(0, 0) && !png_pair_ok(8, 7), "and no others");
+static_assert(png_bpp(1) == 1 && png_bpp(24) == 3 && png_bpp(64) == 8, "filter pixel sizes");
+static_assert(png_row_bytes(1, 1) == 1 && png_row_bytes(9, 1) == 2 && png_row_bytes(341, 24) == 1023 &&
+              png_row_bytes(0x7FFFFFFFull, 64) == 0x3FFFFFFF8ull, "row bytes, in 64 bits");
+static_assert(png_adam7_size(8, 8, 8, 1) == 2 + 2 + 3 + 6 + 10 + 20 + 36, "8 x 8 grey-8, interlaced: 79 bytes");
+static_assert(png_adam7_size(8, 8, 8, 0) == 8 * 9 && png_adam7_size(1, 9, 8, 1) == 18 && png_adam7_size(1, 1, 1, 1) == 2, "one pass; empty passes");
+
+}  // namespace fdh

@@ -14,12 +14,11 @@
 // of fewer than 64 quads share a step (64 / quads rows to a step).
 //
 // Palette: 256 words R | G << 8 | B << 16 | A << 24 per image (fdh_png_colour_batch writes them, 0xFF000000 behind the
-// PLTE's count), copied to the LDS once per workgroup.  An index at or above the count is what status 9 reports: one
-// atomicOr per wavefront that saw one.
+// PLTE's count), copied to the LDS once per workgroup.  An index at or above the count is what kPngIndexOutsidePalette
+// reports: one atomicOr per wavefront that saw one.
 #include "device_common.h"
-
-#include <algorithm>
-#include <cstdlib>
+#include "launch.h"
+#include "png_common.h"
 
 namespace fdh {
 
@@ -59,8 +58,8 @@ struct ExpandBytes {
 
 template <int DEPTH, int COLOUR>
 struct Expand {
-    static constexpr int CH = COLOUR == 0 || COLOUR == 3 ? 1 : COLOUR == 4 ? 2 : COLOUR == 2 ? 3 : 4;
-    static constexpr int BITS = CH * DEPTH;                    // per pixel
+    static constexpr int CH = (int)png_channels(COLOUR);
+    static constexpr int BITS = (int)png_pixel_bits(DEPTH, COLOUR);  // per pixel
     static constexpr int QUAD = BITS * 4 / 8 ? BITS * 4 / 8 : 1;  // bytes that hold four pixels (1-bit: half of one)
     static constexpr uint32_t MAXV = (1u << DEPTH) - 1;
 
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(kWave) void png_expand_kernel(PngExpandArgs a) {
     const uint64_t rows = (s1 - s0) / rb;
     const bool fits = rows * rb == s1 - s0 && o1 - o0 == rows * width * 4;
     if (!fits) {
-        if (first) a.status[i] = 2;
+        if (first) a.status[i] = kPngBadSizes;
         return;
     }
     const uint64_t bands = (rows + kExpandBand - 1) / kExpandBand;
@@ -206,13 +205,13 @@ __global__ __launch_bounds__(kWave) void png_expand_kernel(PngExpandArgs a) {
                 for (uint64_t r = r0 + lr; r < r1; r += per) item(img + r * rb, dst + r * width * 4, width, lq);
         }
     }
-    if (COLOUR == 3 && __any(bad) && lane == 0) atomicOr(&a.status[i], 9u);
+    if (COLOUR == 3 && __any(bad) && lane == 0) atomicOr(&a.status[i], kPngIndexOutsidePalette);
 }
 
 }  // namespace fdh
 
 // A wavefront takes the bands b, b + Y, .. of its image; Y is chosen so that a small batch of tall images still fills the
-// GPU (as fdh_launch_png_choose does), FDH_PNG_EXPAND_WAVES sets it.  The statuses start at 0: status 9 is OR-ed in.
+// GPU (png_waves_per_image), FDH_PNG_EXPAND_WAVES sets it.  The statuses start at kPngOk: kPngIndexOutsidePalette is OR-ed in.
 extern "C" int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
                                      const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* status,
                                      uint64_t n, uint32_t width, uint64_t row_bytes, uint32_t bit_depth, uint32_t colour_type,
@@ -220,11 +219,7 @@ extern "C" int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off
     if (n == 0) return 0;
     hipError_t e = hipMemsetAsync(status, 0, n * 4, stream);
     if (e != hipSuccess) return (int)e;
-    uint32_t waves = (uint32_t)std::min<uint64_t>(4096, (32768 + n - 1) / n);
-    if (const char* v = getenv("FDH_PNG_EXPAND_WAVES")) {
-        const int w = atoi(v);
-        if (w >= 1 && w <= 65535) waves = (uint32_t)w;
-    }
+    const uint32_t waves = fdh::png_waves_per_image(n, "FDH_PNG_EXPAND_WAVES");
     fdh::PngExpandArgs a{pix, pix_off, rgba, rgba_off, pal, colour, upstream, status, n, row_bytes, width};
     const dim3 block(fdh::kWave), grid((unsigned)n, waves);
 #define FDH_EXPAND_CASE(D, C)                                                                  \

@@ -16,8 +16,8 @@
 //
 // Nothing here allocates, synchronises or reads anything back.
 #include "device_common.h"
-
-#include <cstdlib>
+#include "launch.h"
+#include "png_common.h"
 
 namespace fdh {
 
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(THREADS) void crc32_ranges_kernel(CrcArgs a) {
     CrcLane<COPIES> T{&lds.t[lane % COPIES]};
     const uint64_t o = a.off[i], slot = a.off[i + 1] - o;
     if (a.png_status) {
-        if (a.png_status[i] != 0) return;
+        if (a.png_status[i] != kPngOk) return;
         const uint32_t s = a.len[i];
         const uint8_t* b = a.data + o + (kPngPrefix - 4);
         const uint32_t c = crc_piece<COPIES>(T, lane, b, b + 4 + s, 0u, w, a.pieces);
@@ -222,14 +222,14 @@ __global__ __launch_bounds__(THREADS) void crc32_ranges_kernel(CrcArgs a) {
     if (bad) {
         if (lane == 0 && w == 0) {
             a.crc[i] = 0;
-            a.status[i] = 2;
+            a.status[i] = kPngBadSizes;
         }
         return;
     }
     const uint8_t* b = a.data + o;
     const uint32_t c = crc_piece<COPIES>(T, lane, b, b + L, a.seed ? a.seed[i] : 0u, w, a.pieces);
     if (lane == 0) {
-        if (w == 0) a.status[i] = 0;
+        if (w == 0) a.status[i] = kPngOk;
         if (a.pieces == 1) a.crc[i] = c;
         else if (c) atomicXor(&a.crc[i], c);
     }
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void png_frame_prefix_kernel(FrameArgs a) {
     const uint64_t o = a.file_off[i], slot = a.file_off[i + 1] - o;
     const uint32_t s = a.idat_len[i], h = a.height[i];
     if (s == 0 || s > 0x7FFFFFFFu || (uint64_t)s + kPngPrefix + kPngSuffix > slot || h == 0 || h > 0x7FFFFFFFu) {
-        a.png_status[i] = 2;  // (0xFFFFFFFF, the encoders' "slot too small", is above 2^31 - 1)
+        a.png_status[i] = kPngBadSizes;  // (0xFFFFFFFF, the encoders' "slot too small", is above 2^31 - 1)
         a.file_len[i] = 0;
         return;
     }
@@ -302,13 +302,13 @@ __global__ __launch_bounds__(256) void png_frame_prefix_kernel(FrameArgs a) {
     f[40] = 'T';
     *frame_sum_word(f + kPngPrefix + s) = 0;
     a.file_len[i] = s + kPngPrefix + kPngSuffix;
-    a.png_status[i] = 0;
+    a.png_status[i] = kPngOk;
 }
 
 // One file per lane: the IDAT's CRC from the word it was summed in, then IEND.
 __global__ __launch_bounds__(256) void png_frame_finish_kernel(FrameArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.n || a.png_status[i] != 0) return;
+    if (i >= a.n || a.png_status[i] != kPngOk) return;
     uint8_t* t = a.file + a.file_off[i] + kPngPrefix + a.idat_len[i];
     const uint32_t c = *frame_sum_word(t);
     const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
@@ -317,12 +317,8 @@ __global__ __launch_bounds__(256) void png_frame_finish_kernel(FrameArgs a) {
 }
 
 // ---- fdh_png_scan_files_batch ----
-struct PngInfo {  // fdh_png_info
-    uint32_t status, width, height;
-    uint8_t bit_depth, colour_type, interlace, pad;
-    uint32_t idat_bytes, idat_chunks, first_idat, chunks;
-};
-static_assert(sizeof(PngInfo) == 32 && sizeof(fdh_png_info) == 32, "fdh_png_info is 32 bytes");
+using PngInfo = fdh_png_info;
+static_assert(sizeof(PngInfo) == 32, "fdh_png_info is 32 bytes");
 
 struct ScanArgs {
     const uint8_t* file;
@@ -332,17 +328,6 @@ struct ScanArgs {
     uint64_t n;
     bool adam7;  // FDH_PNG_FLAG_ADAM7: interlace method 1 is no finding
 };
-
-__device__ __forceinline__ bool png_pair_ok(uint32_t depth, uint32_t colour) {
-    switch (colour) {
-        case 0: return depth == 1 || depth == 2 || depth == 4 || depth == 8 || depth == 16;
-        case 3: return depth == 1 || depth == 2 || depth == 4 || depth == 8;
-        case 2:
-        case 4:
-        case 6: return depth == 8 || depth == 16;
-        default: return false;
-    }
-}
 
 constexpr uint32_t kIHDR = 0x49484452u, kPLTE = 0x504C5445u, kIDAT = 0x49444154u, kIEND = 0x49454E44u;
 
@@ -355,22 +340,22 @@ __global__ __launch_bounds__(64) void png_scan_kernel(ScanArgs a) {
     const uint64_t flen = a.file_len ? (a.file_len[i] < slot ? a.file_len[i] : slot) : slot;
     const uint8_t* f = a.file + o;
     PngInfo r{};
-    uint32_t st = 0;
-    if (flen < 8 || get_be32(f) != 0x89504E47u || get_be32(f + 4) != 0x0D0A1A0Au) st = 1;
+    uint32_t st = kPngOk;
+    if (flen < 8 || get_be32(f) != 0x89504E47u || get_be32(f + 4) != 0x0D0A1A0Au) st = kPngScanNoSignature;
     uint64_t pos = 8, idat = 0;
     bool seen_idat = false, idat_over = false;
-    while (st == 0) {
+    while (st == kPngOk) {
         if (pos + 12 > flen) {
-            st = 2;
+            st = kPngScanTruncated;
             break;
         }
         const uint32_t len = get_be32(f + pos), type = get_be32(f + pos + 4);
         if (r.chunks == 0 && (type != kIHDR || len != 13)) {
-            st = 3;
+            st = kPngScanBadIhdr;
             break;
         }
         if (pos + 12 + len > flen) {
-            st = 2;
+            st = kPngScanTruncated;
             break;
         }
         if (r.chunks == 0) {
@@ -382,26 +367,26 @@ __global__ __launch_bounds__(64) void png_scan_kernel(ScanArgs a) {
             r.interlace = d[12];
             if (r.width == 0 || r.height == 0 || (r.width | r.height) >> 31 || !png_pair_ok(d[8], d[9]) || d[10] != 0 ||
                 d[11] != 0 || d[12] > 1)
-                st = 3;
+                st = kPngScanBadIhdr;
             else if (d[12] == 1 && !a.adam7)
-                st = 4;
+                st = kPngScanInterlaced;
         } else if (type == kIDAT) {
-            if (idat_over) st = 5;
+            if (idat_over) st = kPngScanChunkStructure;
             else {
                 if (!seen_idat) r.first_idat = (uint32_t)pos;
                 seen_idat = true;
                 idat += len;
                 r.idat_chunks++;
-                if (idat >> 32 || pos >> 32) st = 5;  // (the counts are 32 bits wide)
+                if (idat >> 32 || pos >> 32) st = kPngScanChunkStructure;  // (the counts are 32 bits wide)
             }
         } else {
             if (seen_idat) idat_over = true;
             if (type == kIEND) {
-                if (!seen_idat) st = 5;
+                if (!seen_idat) st = kPngScanChunkStructure;
             } else if (type == kPLTE) {
-                if (seen_idat) st = 5;
+                if (seen_idat) st = kPngScanChunkStructure;
             } else if (!(type & 0x20000000u)) {  // an upper-case first letter: critical, and none that is known here
-                st = 5;
+                st = kPngScanChunkStructure;
             }
         }
         if (st) break;
@@ -415,14 +400,14 @@ __global__ __launch_bounds__(64) void png_scan_kernel(ScanArgs a) {
 }
 
 // One file per workgroup, the chunks in file order, every chunk by all wavefronts of the group together: each takes a
-// piece (crc_piece), the pieces meet in the LDS.  Only files the walk found sound are read; a mismatch makes them 6.
+// piece (crc_piece), the pieces meet in the LDS.  Only files the walk found sound are read; a mismatch: kPngScanCrcMismatch.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void png_verify_crc_kernel(ScanArgs a) {
     __shared__ CrcLds<1> lds;
     __shared__ uint32_t part[THREADS / 64];
     lds.load((int)threadIdx.x, THREADS);
     const uint64_t i = blockIdx.x;
-    if (a.info[i].status != 0) return;
+    if (a.info[i].status != kPngOk) return;
     const int lane = (int)threadIdx.x & 63;
     const uint32_t w = uni(threadIdx.x >> 6);
     CrcLane<1> T{lds.t};
@@ -445,7 +430,7 @@ __global__ __launch_bounds__(THREADS) void png_verify_crc_kernel(ScanArgs a) {
         differs = differs || c != get_be32(e);
         pos += 12ull + len;
     }
-    if (differs && threadIdx.x == 0) a.info[i].status = 6;
+    if (differs && threadIdx.x == 0) a.info[i].status = kPngScanCrcMismatch;
 }
 
 // ---- fdh_png_gather_idat_batch ----
@@ -474,10 +459,10 @@ __global__ __launch_bounds__(THREADS) void png_gather_idat_kernel(GatherArgs a) 
     const PngInfo r = a.info[i];
     const uint64_t o = a.file_off[i], slot = a.file_off[i + 1] - o;
     const uint64_t co = a.comp_off[i], room = a.comp_off[i + 1] - co;
-    uint32_t st = 0;
-    if (r.status != 0) st = 3;
-    else if (r.width != a.width || r.bit_depth != a.bit_depth || r.colour_type != a.colour_type) st = 7;
-    else if (r.idat_bytes > room) st = 8;
+    uint32_t st = kPngOk;
+    if (r.status != kPngOk) st = kPngSkipped;
+    else if (r.width != a.width || r.bit_depth != a.bit_depth || r.colour_type != a.colour_type) st = kPngOtherGeometry;
+    else if (r.idat_bytes > room) st = kPngCompSlotTooSmall;
     if (st) {
         if (threadIdx.x == 0) {
             a.png_status[i] = st;
@@ -516,7 +501,7 @@ __global__ __launch_bounds__(THREADS) void png_gather_idat_kernel(GatherArgs a) 
         pos += 12ull + len;
     }
     if (threadIdx.x == 0) {  // (an info record that does not describe the file: skipped, like a file the scan refused)
-        a.png_status[i] = sound && done == r.idat_bytes ? 0u : 3u;
+        a.png_status[i] = sound && done == r.idat_bytes ? kPngOk : kPngSkipped;
         a.comp_len[i] = sound && done == r.idat_bytes ? done : 0u;
     }
 }
@@ -545,40 +530,40 @@ __global__ __launch_bounds__(kWave) void png_colour_kernel(ColourArgs a) {
     const uint64_t slot = a.file_off[i + 1] - a.file_off[i];
     const uint8_t* f = a.file + a.file_off[i];
     const uint32_t ct = a.colour_type;
-    uint32_t st = 0;
-    if (r.status != 0) st = 3;
-    else if (r.width != a.width || r.bit_depth != a.bit_depth || r.colour_type != ct) st = 7;
-    else if (r.first_idat > slot) st = 3;  // (an info record that does not describe the file)
+    uint32_t st = kPngOk;
+    if (r.status != kPngOk) st = kPngSkipped;
+    else if (r.width != a.width || r.bit_depth != a.bit_depth || r.colour_type != ct) st = kPngOtherGeometry;
+    else if (r.first_idat > slot) st = kPngSkipped;  // (an info record that does not describe the file)
     const uint32_t end = uni(r.first_idat);
     uint64_t pos = 8;
     bool have_plte = false, have_trns = false;
     uint32_t plte_at = 0, count = 0, trns_at = 0, trns_len = 0;
-    while (st == 0 && pos < end) {
+    while (st == kPngOk && pos < end) {
         if (pos + 12 > end) {
-            st = 3;
+            st = kPngSkipped;
             break;
         }
         const uint32_t len = uni(get_be32(f + pos)), type = uni(get_be32(f + pos + 4));
         if (pos + 12 + len > end) {
-            st = 3;
+            st = kPngSkipped;
             break;
         }
         if (type == kPLTE && ct == 3) {
-            if (have_plte || len == 0 || len % 3 != 0 || len > 768) st = 10;
+            if (have_plte || len == 0 || len % 3 != 0 || len > 768) st = kPngBadPlte;
             have_plte = true;
             plte_at = (uint32_t)pos + 8;
             count = len / 3;
         } else if (type == kTRNS && (ct == 0 || ct == 2 || ct == 3)) {
-            if (have_trns || (ct == 0 && len != 2) || (ct == 2 && len != 6) || (ct == 3 && (!have_plte || len > count))) st = 11;
+            if (have_trns || (ct == 0 && len != 2) || (ct == 2 && len != 6) || (ct == 3 && (!have_plte || len > count))) st = kPngBadTrns;
             have_trns = true;
             trns_at = (uint32_t)pos + 8;
             trns_len = len;
         }
         pos += 12ull + len;
     }
-    if (st == 0 && ct == 3 && !have_plte) st = 10;
+    if (st == kPngOk && ct == 3 && !have_plte) st = kPngBadPlte;
     if (lane == 0) a.png_status[i] = st;
-    if (st != 0) return;
+    if (st != kPngOk) return;
     if (lane == 0) {
         const uint8_t* t = f + trns_at;
         const bool key = have_trns && ct != 3;
@@ -611,24 +596,19 @@ __global__ __launch_bounds__(kWave) void png_colour_kernel(ColourArgs a) {
 // ---- launchers ----
 namespace {
 
-int env_int(const char* name, int fallback) {
-    const char* e = std::getenv(name);
-    return e ? std::atoi(e) : fallback;
-}
-
 // Wavefronts per range / threads per file: a batch that fills the device by its count alone gets one wavefront per item.
 constexpr uint64_t kFillWaves = 4096;
 
 hipError_t launch_crc(fdh::CrcArgs a, hipStream_t stream) {
     a.pieces = a.n >= kFillWaves ? 1u : (uint32_t)((kFillWaves + a.n - 1) / a.n);
-    const int forced = env_int("FDH_CRC_PIECES", 0);  // tests / A-B
+    const int forced = fdh::env_int("FDH_CRC_PIECES", 0);  // tests / A-B
     if (forced >= 1 && forced <= 65536 && a.n * (uint64_t)forced < (1ull << 31)) a.pieces = (uint32_t)forced;
     if (a.pieces > 1 && !a.png_status) {
         hipError_t e = hipMemsetAsync(a.crc, 0, a.n * 4, stream);
         if (e != hipSuccess) return e;
     }
     const uint64_t waves = a.n * a.pieces;
-    const int copies = env_int("FDH_CRC_COPIES", 1);  // tests / A-B: 1, 8 or 32 copies of the tables (measured)
+    const int copies = fdh::env_int("FDH_CRC_COPIES", 1);  // tests / A-B: 1, 8 or 32 copies of the tables (measured)
     if (copies == 32) {
         hipLaunchKernelGGL((fdh::crc32_ranges_kernel<32, 1024>), dim3((unsigned)((waves + 15) / 16)), dim3(1024), 0, stream, a);
     } else if (copies == 8) {
@@ -662,9 +642,9 @@ extern "C" int fdh_launch_png_frame(uint8_t* file, const uint64_t* file_off, con
     return (int)hipGetLastError();
 }
 
-extern "C" int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, void* info,
+extern "C" int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, fdh_png_info* info,
                                    uint64_t n, int verify_crc, int adam7, hipStream_t stream) {
-    fdh::ScanArgs a{file, file_off, file_len, static_cast<fdh::PngInfo*>(info), n, adam7 != 0};
+    fdh::ScanArgs a{file, file_off, file_len, info, n, adam7 != 0};
     hipLaunchKernelGGL(fdh::png_scan_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !verify_crc) return (int)e;
@@ -673,18 +653,18 @@ extern "C" int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off
     return (int)hipGetLastError();
 }
 
-extern "C" int fdh_launch_png_colour(const uint8_t* file, const uint64_t* file_off, const void* info, uint32_t* pal,
+extern "C" int fdh_launch_png_colour(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint32_t* pal,
                                      uint32_t* colour, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
                                      uint32_t colour_type, hipStream_t stream) {
-    fdh::ColourArgs a{file, file_off, static_cast<const fdh::PngInfo*>(info), pal, colour, png_status, n, width, bit_depth, colour_type};
+    fdh::ColourArgs a{file, file_off, info, pal, colour, png_status, n, width, bit_depth, colour_type};
     hipLaunchKernelGGL(fdh::png_colour_kernel, dim3((unsigned)n), dim3(fdh::kWave), 0, stream, a);
     return (int)hipGetLastError();
 }
 
-extern "C" int fdh_launch_png_gather(const uint8_t* file, const uint64_t* file_off, const void* info, uint8_t* comp,
+extern "C" int fdh_launch_png_gather(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint8_t* comp,
                                      const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n,
                                      uint32_t width, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream) {
-    fdh::GatherArgs a{file, file_off, static_cast<const fdh::PngInfo*>(info), comp, comp_off, comp_len, png_status, n,
+    fdh::GatherArgs a{file, file_off, info, comp, comp_off, comp_len, png_status, n,
                       width, bit_depth, colour_type};
     if (n >= kFillWaves) hipLaunchKernelGGL((fdh::png_gather_idat_kernel<64>), dim3((unsigned)n), dim3(64), 0, stream, a);
     else hipLaunchKernelGGL((fdh::png_gather_idat_kernel<256>), dim3((unsigned)n), dim3(256), 0, stream, a);

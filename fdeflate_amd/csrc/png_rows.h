@@ -1,6 +1,6 @@
-// png_rows.h -- what the PNG row kernels share (png_filter.hip, png_adam7.hip): the Paeth predictor, the
-// branch-free predictor of a row's filter type, sixteen bytes of a row in registers, and the 16-byte loads and
-// stores at any alignment, whole and partial.
+// png_rows.h -- what the PNG row kernels share (png_filter.hip, png_choose.hip, png_adam7.hip): the Paeth predictor,
+// the branch-free predictor of a row's filter type, sixteen bytes of a row in registers, the 16-byte loads and stores
+// at any alignment, whole and partial, and the shift of a value to the lane above.
 #pragma once
 #include "device_common.h"
 
@@ -34,6 +34,10 @@ __device__ __forceinline__ uint4 png_load16(const uint8_t* p) {
     return v;
 }
 __device__ __forceinline__ void png_store16(uint8_t* p, const uint4& v) { __builtin_memcpy(p, &v, 16); }
+// lane j gets lane j - 1's value (lane 0: 0): how a row hands its chunk to the row below it
+__device__ __forceinline__ uint32_t png_from_lane_below(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+}
 __device__ __forceinline__ uint32_t png_byte(const uint4& v, int k) {
     const uint32_t w = k < 4 ? v.x : (k < 8 ? v.y : (k < 12 ? v.z : v.w));
     return (w >> (8 * (k & 3))) & 0xFF;

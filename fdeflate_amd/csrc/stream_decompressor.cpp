@@ -50,9 +50,7 @@
 // input is exhausted) and the png crate's finish loop ask for whatever can still be produced.
 //
 // There is no CPU decode path here: without a GPU every call returns FDH_ERR_NO_DEVICE.
-#include "../../include/fdeflate_hip.h"
-
-#include <hip/hip_runtime.h>
+#include "launch.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -60,9 +58,6 @@
 #include <cstring>
 #include <new>
 #include <string>
-
-extern "C" void fdh_set_last_error(const char* msg);
-extern "C" int fdh_launch_copy_lines(void* dst, const void* src, size_t bytes, hipStream_t stream);  // deflate_stored.hip
 
 namespace {
 

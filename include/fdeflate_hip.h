@@ -227,6 +227,10 @@ uint64_t fdh_compress_bound(uint64_t len);
  *                           stream that decoded to exactly the bytes of its slot
  * png_status[i]: 0 ok, 1 a filter type > 4, 2 sizes do not fit (fdh_inflate_png_batch: also a stream
  * that ended before its slot was full -- short IDAT data), 3 skipped (stream did not decode). */
+#define FDH_PNG_STATUS_OK 0u
+#define FDH_PNG_STATUS_BAD_FILTER_TYPE 1u
+#define FDH_PNG_STATUS_BAD_SIZES 2u
+#define FDH_PNG_STATUS_SKIPPED 3u
 int fdh_png_unfilter_batch(const uint8_t *filt, const uint64_t *filt_off, uint8_t *pix,
                            const uint64_t *pix_off, uint32_t *png_status, uint64_t n,
                            uint32_t row_bytes, uint32_t bpp, void *hip_stream);
@@ -348,6 +352,16 @@ int fdh_png_frame_batch(uint8_t *file, const uint64_t *file_off, const uint32_t 
  */
 #define FDH_PNG_FLAG_IGNORE_CRC 0x1u
 #define FDH_PNG_FLAG_ADAM7 0x2u
+/* info.status of the scan, 1 .. 6 in the order of the list above */
+#define FDH_PNG_STATUS_SCAN_NO_SIGNATURE 1u
+#define FDH_PNG_STATUS_SCAN_TRUNCATED 2u
+#define FDH_PNG_STATUS_SCAN_BAD_IHDR 3u
+#define FDH_PNG_STATUS_SCAN_INTERLACED 4u
+#define FDH_PNG_STATUS_SCAN_CHUNK_STRUCTURE 5u
+#define FDH_PNG_STATUS_SCAN_CRC_MISMATCH 6u
+/* png_status of the gather (and 7 of fdh_png_colour_batch) */
+#define FDH_PNG_STATUS_OTHER_GEOMETRY 7u
+#define FDH_PNG_STATUS_COMP_SLOT_TOO_SMALL 8u
 typedef struct fdh_png_info {
   uint32_t status, width, height;
   uint8_t bit_depth, colour_type, interlace, pad;
@@ -407,6 +421,9 @@ int fdh_png_gather_idat_batch(const uint8_t *file, const uint64_t *file_off,
  * byte outside pix[pix_off[0] .. pix_off[n]) is read.  FDH_PNG_EXPAND_WAVES (environment) sets the number of
  * wavefronts per image.
  */
+#define FDH_PNG_STATUS_INDEX_OUTSIDE_PALETTE 9u
+#define FDH_PNG_STATUS_BAD_PLTE 10u
+#define FDH_PNG_STATUS_BAD_TRNS 11u
 int fdh_png_colour_batch(const uint8_t *file, const uint64_t *file_off, const fdh_png_info *info,
                          uint32_t *pal, uint32_t *colour, uint32_t *png_status, uint64_t n,
                          uint32_t width, uint32_t bit_depth, uint32_t colour_type, void *hip_stream);

@@ -46,6 +46,22 @@ pub struct fdh_png_info {
 pub const FDH_PNG_FILE_PREFIX: u32 = 41;
 pub const FDH_PNG_FILE_SUFFIX: u32 = 16;
 pub const FDH_PNG_FLAG_IGNORE_CRC: u32 = 1;
+/// Per-image PNG status values (`FDH_PNG_STATUS_*` of include/fdeflate_hip.h).
+pub const FDH_PNG_STATUS_OK: u32 = 0;
+pub const FDH_PNG_STATUS_BAD_FILTER_TYPE: u32 = 1;
+pub const FDH_PNG_STATUS_BAD_SIZES: u32 = 2;
+pub const FDH_PNG_STATUS_SKIPPED: u32 = 3;
+pub const FDH_PNG_STATUS_SCAN_NO_SIGNATURE: u32 = 1;
+pub const FDH_PNG_STATUS_SCAN_TRUNCATED: u32 = 2;
+pub const FDH_PNG_STATUS_SCAN_BAD_IHDR: u32 = 3;
+pub const FDH_PNG_STATUS_SCAN_INTERLACED: u32 = 4;
+pub const FDH_PNG_STATUS_SCAN_CHUNK_STRUCTURE: u32 = 5;
+pub const FDH_PNG_STATUS_SCAN_CRC_MISMATCH: u32 = 6;
+pub const FDH_PNG_STATUS_OTHER_GEOMETRY: u32 = 7;
+pub const FDH_PNG_STATUS_COMP_SLOT_TOO_SMALL: u32 = 8;
+pub const FDH_PNG_STATUS_INDEX_OUTSIDE_PALETTE: u32 = 9;
+pub const FDH_PNG_STATUS_BAD_PLTE: u32 = 10;
+pub const FDH_PNG_STATUS_BAD_TRNS: u32 = 11;
 
 /// `fdh_shard_t`: the device-resident shard of one GPU for `fdh_inflate_batch_multi`.
 #[repr(C)]
