@@ -19,7 +19,10 @@ from .api import (Decompressor, DecompressionError, OutputTooLarge, STATUS_NAMES
                   PNG_INDEX_OUTSIDE_PALETTE, PNG_BAD_PLTE, PNG_BAD_TRNS, png_colour_batch, png_expand_batch,
                   png_decode_files_rgba_batch, PNG_FLAG_ADAM7, png_adam7_size, png_unfilter_interlaced_batch,
                   PNG_OK, PNG_BAD_FILTER_TYPE, PNG_BAD_SIZES, PNG_SKIPPED, PNG_SCAN_NO_SIGNATURE, PNG_SCAN_TRUNCATED,
-                  PNG_SCAN_BAD_IHDR, PNG_SCAN_INTERLACED, PNG_SCAN_CHUNK_STRUCTURE, PNG_SCAN_CRC_MISMATCH)
+                  PNG_SCAN_BAD_IHDR, PNG_SCAN_INTERLACED, PNG_SCAN_CHUNK_STRUCTURE, PNG_SCAN_CRC_MISMATCH,
+                  PNG_TOO_MANY_COLOURS, PNG_NOT_REPRESENTABLE, PNG_SUMMARY_OPAQUE, PNG_SUMMARY_GREY, PNG_ANALYSE_HASH_MUL,
+                  PNG_ANALYSE_HASH_BITS, png_analyse_batch, png_pack_batch, png_palette_file_prefix, png_frame_palette_batch,
+                  png_encode_rgba_files_batch)
 
 __all__ = [
     "Decompressor", "DecompressionError", "OutputTooLarge", "STATUS_NAMES", "FLAG_IGNORE_ADLER32",
@@ -37,4 +40,7 @@ __all__ = [
     "png_decode_files_rgba_batch", "PNG_FLAG_ADAM7", "png_adam7_size", "png_unfilter_interlaced_batch",
     "PNG_OK", "PNG_BAD_FILTER_TYPE", "PNG_BAD_SIZES", "PNG_SKIPPED", "PNG_SCAN_NO_SIGNATURE", "PNG_SCAN_TRUNCATED",
     "PNG_SCAN_BAD_IHDR", "PNG_SCAN_INTERLACED", "PNG_SCAN_CHUNK_STRUCTURE", "PNG_SCAN_CRC_MISMATCH",
+    "PNG_TOO_MANY_COLOURS", "PNG_NOT_REPRESENTABLE", "PNG_SUMMARY_OPAQUE", "PNG_SUMMARY_GREY", "PNG_ANALYSE_HASH_MUL",
+    "PNG_ANALYSE_HASH_BITS", "png_analyse_batch", "png_pack_batch", "png_palette_file_prefix", "png_frame_palette_batch",
+    "png_encode_rgba_files_batch",
 ]

@@ -474,6 +474,16 @@ PNG_COMP_SLOT_TOO_SMALL = 8
 PNG_INDEX_OUTSIDE_PALETTE = 9
 PNG_BAD_PLTE = 10
 PNG_BAD_TRNS = 11
+# png_status 12 of png_analyse_batch, 13 of png_pack_batch
+PNG_TOO_MANY_COLOURS = 12
+PNG_NOT_REPRESENTABLE = 13
+# summary of png_analyse_batch: bit 0 every A is 255, bit 1 every pixel is grey, bits 8 .. 15 the sample depth that suffices
+PNG_SUMMARY_OPAQUE = 1
+PNG_SUMMARY_GREY = 2
+# The analysis kernel's LDS table (csrc/png_pack.hip: kColourHashMul, kAnalyseSlotBits): the pixel word w = R | G << 8 |
+# B << 16 | A << 24 starts probing at slot ((w * MUL) mod 2^32) >> (32 - BITS).  Named here for tests that build collisions.
+PNG_ANALYSE_HASH_MUL = 0x9E3779B1
+PNG_ANALYSE_HASH_BITS = 11
 # fdh_png_info as eight int32 words: status, width, height, depth | colour << 8 | interlace << 16, idat_bytes,
 # idat_chunks, first_idat, chunks
 PNG_INFO_WORDS = 8
@@ -764,6 +774,146 @@ def png_decode_files_rgba_batch(file, file_off, width, bit_depth, colour_type, f
                                     upstream=upstream)
         png_status = torch.where(png_status != 0, png_status, expanded)
     return rgba[:total], rgba_off, info, status, png_status
+
+
+# ------------------------------------------------------------------------------------------
+# PNG encode from RGBA8: analysis, packing, palette files
+# ------------------------------------------------------------------------------------------
+
+def png_analyse_batch(rgba, rgba_off, width, max_colours=256, with_pal=True, pal=None, colour=None, trns_len=None, summary=None,
+                      png_status=None):
+    """What n RGBA8 images are (fdh_png_analyse_batch): image i is rgba[rgba_off[i] .. rgba_off[i+1]), whole rows of
+    width * 4 bytes.  -> (pal, colour, trns_len, summary, png_status): pal int32 [n, 256], the distinct pixels as words
+    R | G << 8 | B << 16 | A << 24 in ascending unsigned order -- entries with A < 255 first --, 0xFF000000 behind the count
+    (None with with_pal=False); colour int32 [n, 4], word 0 the count; trns_len int32 [n], the entries with A < 255;
+    summary int32 [n]: PNG_SUMMARY_OPAQUE, PNG_SUMMARY_GREY, bits 8 .. 15 the smallest sample depth of 1, 2, 4, 8 that
+    loses nothing; png_status 0 ok, 2 the slot is not whole rows (nothing written for the image), PNG_TOO_MANY_COLOURS
+    (12: more than max_colours distinct pixels; only summary is valid)."""
+    import torch
+    n = rgba_off.numel() - 1
+    dev = rgba.device
+    if pal is None and with_pal:
+        pal = torch.empty((n, 256), dtype=torch.int32, device=dev)
+    if colour is None:
+        colour = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    if trns_len is None:
+        trns_len = torch.empty(n, dtype=torch.int32, device=dev)
+    if summary is None:
+        summary = torch.empty(n, dtype=torch.int32, device=dev)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=dev)
+    with _OnDevice(rgba, rgba_off, pal, colour, trns_len, summary, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_analyse_batch(_ptr(rgba), _ptr(rgba_off), _ptr(pal), _ptr(colour), _ptr(trns_len),
+                                                   _ptr(summary), _ptr(png_status), n, width, max_colours, C.c_void_p(stream)))
+    return pal, colour, trns_len, summary, png_status
+
+
+def png_pack_batch(rgba, rgba_off, pix, pix_off, width, bit_depth, colour_type, pal=None, colour=None, upstream=None,
+                   png_status=None):
+    """RGBA8 to packed scanlines, the inverse of png_expand_batch (fdh_png_pack_batch): image i, whole rows of width * 4
+    bytes at rgba_off[i] .. rgba_off[i+1], goes to the slot pix[pix_off[i] .. pix_off[i+1]) of exactly rows * row_bytes
+    bytes.  pal / colour as png_analyse_batch or png_colour_batch write them (pal is needed for colour type 3: the index
+    is the lowest one whose word equals the pixel; without colour all 256 words count); upstream (int32 [n]): where not 0
+    the image is skipped and its png_status is that value.  -> png_status: 0 ok, 2 the slots do not fit (nothing
+    written), PNG_NOT_REPRESENTABLE (13: some pixel cannot be held by the pair without loss)."""
+    import torch
+    n = rgba_off.numel() - 1
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=rgba.device)
+    with _OnDevice(rgba, rgba_off, pix, pix_off, pal, colour, upstream, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_pack_batch(_ptr(rgba), _ptr(rgba_off), _ptr(pix), _ptr(pix_off), _ptr(pal), _ptr(colour),
+                                                _ptr(upstream), _ptr(png_status), n, width, bit_depth, colour_type,
+                                                C.c_void_p(stream)))
+    return png_status
+
+
+def png_palette_file_prefix(plte_entries, trns_entries):
+    """The bytes in front of the zlib stream of a palette file with a PLTE of plte_entries entries and, where trns_entries
+    is not 0, a tRNS of that many bytes: 41 + 12 + 3 E + (12 + T) (fdh_png_palette_file_prefix)."""
+    v = int(_lib.lib().fdh_png_palette_file_prefix(int(plte_entries), int(trns_entries)))
+    if v == 0:
+        raise ValueError("plte_entries must be 1 .. 256 and trns_entries 0 .. plte_entries")
+    return v
+
+
+def png_frame_palette_batch(file, file_off, idat_len, height, pal, colour, trns_len, width, bit_depth, plte_entries, trns_entries,
+                            file_len=None, png_status=None):
+    """png_frame_batch for colour type 3 (fdh_png_frame_palette_batch): signature, IHDR, a PLTE of plte_entries entries
+    (the colour[i, 0] words of pal[i], then zeros), a tRNS of trns_entries alphas where that is not 0, and the IDAT's head
+    in front of the zlib streams that lie png_palette_file_prefix(plte_entries, trns_entries) bytes into their file slots;
+    the IDAT's CRC and IEND behind them.  -> (file_len, png_status): 0 ok, 2 as png_frame_batch, 10 colour[i, 0] is 0 or
+    above plte_entries, 11 trns_len[i] is above trns_entries (nothing written, file_len 0)."""
+    import torch
+    n = file_off.numel() - 1
+    if file_len is None:
+        file_len = torch.empty(n, dtype=torch.int32, device=file.device)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
+    with _OnDevice(file, file_off, idat_len, height, pal, colour, trns_len, file_len, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_frame_palette_batch(_ptr(file), _ptr(file_off), _ptr(idat_len), _ptr(height), _ptr(pal),
+                                                         _ptr(colour), _ptr(trns_len), _ptr(file_len), _ptr(png_status), n, width,
+                                                         bit_depth, plte_entries, trns_entries, C.c_void_p(stream)))
+    return file_len, png_status
+
+
+def png_encode_rgba_files_batch(rgba, rgba_off, file, file_off, width, bit_depth, colour_type, plte_entries=None, trns_entries=None):
+    """RGBA8 pictures in, PNG files of the given depth / colour type out, on torch's current stream and without a read-back:
+    for colour type 3 png_analyse_batch (max_colours = plte_entries, by default min(256, 2^bit_depth); trns_entries is
+    plte_entries by default), then png_pack_batch, the rows' filter types and the fused filter + ultra-fast encode
+    (png_encode_ultrafast_batch) at file_off + the prefix, and png_frame_batch or png_frame_palette_batch around the
+    streams.  Image i is rgba[rgba_off[i] .. rgba_off[i+1]), whole rows of width * 4 bytes; its file goes to the slot
+    file[file_off[i] .. file_off[i+1]) -- png_file_bound(rows, row_bytes), plus png_palette_file_prefix(..) - 41 for a
+    palette file, always suffices.
+    -> (file_len, png_status): png_status[i] is the first that is not 0 of analyse (2, 12), pack (2, 13), the encoder and
+    the framing (2, 10, 11); an image that failed in front of the framing gets no file: file_len[i] = 0, nothing is framed,
+    and the contents of its file slot are not specified (the encoder has run over that image's packed slot, which pack did
+    not write: disregard the slot).
+    The encoders take ONE offsets array, so the encoder's slot for image i reaches `prefix` bytes into slot i + 1 (the
+    last one ends 16 bytes in front of its slot's end): the bytes that image i + 1's own prefix is written to afterwards.
+    A stream that does not fit its file slot can therefore leave bytes in the first `prefix` of the next slot; they stay
+    there only if that next image fails as well."""
+    import torch
+    row_bytes, bpp = png_geometry(width, bit_depth, colour_type)
+    n = rgba_off.numel() - 1
+    dev = rgba.device
+    if colour_type == 3:
+        if plte_entries is None:
+            plte_entries = min(256, 1 << bit_depth)
+        if trns_entries is None:
+            trns_entries = plte_entries
+        if not 1 <= plte_entries <= min(256, 1 << bit_depth) or not 0 <= trns_entries <= plte_entries:
+            raise ValueError("plte_entries must be 1 .. min(256, 2^bit_depth) and trns_entries 0 .. plte_entries")
+        prefix = png_palette_file_prefix(plte_entries, trns_entries)
+    else:
+        prefix = PNG_FILE_PREFIX
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=dev)
+        return e, e.clone()
+    rows = (rgba_off[1:] - rgba_off[:-1]) // (width * 4)
+    height = rows.clamp(max=0xFFFFFFFF).to(torch.int32)                       # (bit pattern of the u32)
+    # packed rows and one filter type per row; both buffers are sized by what `rgba` could hold at most: no read-back
+    pix_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(rows * row_bytes, 0, out=pix_off[1:])
+    types_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(rows, 0, out=types_off[1:])
+    most = max(1, rgba.numel() // (width * 4))
+    pix = torch.empty(most * row_bytes, dtype=torch.uint8, device=dev)
+    types = torch.empty(most, dtype=torch.uint8, device=dev)
+    pal = colour = trns_len = upstream = None
+    if colour_type == 3:
+        pal, colour, trns_len, _, upstream = png_analyse_batch(rgba, rgba_off, width, max_colours=plte_entries)
+    packed = png_pack_batch(rgba, rgba_off, pix, pix_off, width, bit_depth, colour_type, pal=pal, colour=colour, upstream=upstream)
+    enc_off = file_off + prefix
+    enc_off[n] = torch.maximum(file_off[n] - PNG_FILE_SUFFIX, enc_off[n - 1])
+    idat_len, enc_status, _ = png_encode_ultrafast_batch(pix, pix_off, file, enc_off, row_bytes, bpp, types=types, types_off=types_off)
+    before = torch.where(packed != 0, packed, enc_status)
+    idat_len = torch.where(before != 0, torch.zeros_like(idat_len), idat_len)     # (the framing then writes nothing)
+    if colour_type == 3:
+        file_len, framed = png_frame_palette_batch(file, file_off, idat_len, height, pal, colour, trns_len, width, bit_depth,
+                                                   plte_entries, trns_entries)
+    else:
+        file_len, framed = png_frame_batch(file, file_off, idat_len, height, width, bit_depth, colour_type)
+    return file_len, torch.where(before != 0, before, framed)
 
 
 def inflate_batch_multi(shards, flags=0, gather=True):

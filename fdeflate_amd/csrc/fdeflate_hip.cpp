@@ -308,6 +308,47 @@ int fdh_png_unfilter_interlaced_batch(uint8_t* filt, const uint64_t* filt_off, u
                     upstream_len, png_status, n, width, bit_depth, colour_type, stream_of(hip_stream)));
 }
 
+// ---- PNG encode from RGBA8: analysis and packing (png_pack.hip), palette framing (png_file.hip) ----
+int fdh_png_analyse_batch(const uint8_t* rgba, const uint64_t* rgba_off, uint32_t* pal, uint32_t* colour, uint32_t* trns_len,
+                          uint32_t* summary, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t max_colours, void* hip_stream) {
+    if (width == 0 || width > 0x7FFFFFFFu) return fail(FDH_ERR_INVALID_ARGUMENT, "width must be 1 .. 2^31-1");
+    if (max_colours == 0 || max_colours > 256) return fail(FDH_ERR_INVALID_ARGUMENT, "max_colours must be 1 .. 256");
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({rgba, rgba_off, colour, trns_len, summary, png_status}, "null pointer", n, "images")) return rc;
+    return launched("RGBA analysis kernel launch", fdh_launch_png_analyse(rgba, rgba_off, pal, colour, trns_len, summary, png_status, n,
+                    width, max_colours, stream_of(hip_stream)));
+}
+
+int fdh_png_pack_batch(const uint8_t* rgba, const uint64_t* rgba_off, uint8_t* pix, const uint64_t* pix_off, const uint32_t* pal,
+                       const uint32_t* colour, const uint32_t* upstream, uint32_t* png_status, uint64_t n, uint32_t width,
+                       uint32_t bit_depth, uint32_t colour_type, void* hip_stream) {
+    if (int rc = png_geometry_ok(width, bit_depth, colour_type)) return rc;
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({rgba, rgba_off, pix, pix_off, png_status, colour_type == 3 ? pal : png_status}, "null pointer", n, "images")) return rc;
+    const uint64_t row_bytes = fdh::png_row_bytes(width, fdh::png_pixel_bits(bit_depth, colour_type));
+    return launched("RGBA packing kernel launch", fdh_launch_png_pack(rgba, rgba_off, pix, pix_off, pal, colour, upstream, png_status, n,
+                    width, row_bytes, bit_depth, colour_type, stream_of(hip_stream)));
+}
+
+uint64_t fdh_png_palette_file_prefix(uint32_t plte_entries, uint32_t trns_entries) {
+    if (plte_entries == 0 || plte_entries > 256 || trns_entries > plte_entries) return 0;
+    return FDH_PNG_FILE_PREFIX + 12 + 3 * (uint64_t)plte_entries + (trns_entries ? 12 + (uint64_t)trns_entries : 0);
+}
+
+int fdh_png_frame_palette_batch(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height,
+                                const uint32_t* pal, const uint32_t* colour, const uint32_t* trns_len, uint32_t* file_len,
+                                uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t plte_entries,
+                                uint32_t trns_entries, void* hip_stream) {
+    if (int rc = png_geometry_ok(width, bit_depth, 3)) return rc;
+    if (plte_entries == 0 || plte_entries > std::min(256u, 1u << bit_depth))
+        return fail(FDH_ERR_INVALID_ARGUMENT, "plte_entries must be 1 .. min(256, 2^bit_depth)");
+    if (trns_entries > plte_entries) return fail(FDH_ERR_INVALID_ARGUMENT, "trns_entries must be 0 .. plte_entries");
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({file, file_off, idat_len, height, pal, colour, trns_len, file_len, png_status}, "null pointer", n, "files")) return rc;
+    return launched("PNG palette framing kernel launch", fdh_launch_png_frame_palette(file, file_off, idat_len, height, pal, colour, trns_len,
+                    file_len, png_status, n, width, bit_depth, plte_entries, trns_entries, stream_of(hip_stream)));
+}
+
 // ---- general encoder (levels 1-3 / RLE): per-device workspace, grown on demand, never shrunk ----
 namespace {
 struct GenWork {

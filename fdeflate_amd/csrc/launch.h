@@ -62,10 +62,20 @@ int fdh_launch_png_gather(const uint8_t* file, const uint64_t* file_off, const f
                           hipStream_t stream);
 int fdh_launch_png_colour(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, uint32_t* pal, uint32_t* colour,
                           uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+int fdh_launch_png_frame_palette(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height,
+                                 const uint32_t* pal, const uint32_t* colour, const uint32_t* trns_len, uint32_t* file_len,
+                                 uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t plte_entries,
+                                 uint32_t trns_entries, hipStream_t stream);
 // png_expand.hip
 int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off, const uint32_t* pal,
                           const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n, uint32_t width,
                           uint64_t row_bytes, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+// png_pack.hip
+int fdh_launch_png_analyse(const uint8_t* rgba, const uint64_t* rgba_off, uint32_t* pal, uint32_t* colour, uint32_t* trns_len,
+                           uint32_t* summary, uint32_t* status, uint64_t n, uint32_t width, uint32_t max_colours, hipStream_t stream);
+int fdh_launch_png_pack(const uint8_t* rgba, const uint64_t* rgba_off, uint8_t* pix, const uint64_t* pix_off, const uint32_t* pal,
+                        const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n, uint32_t width,
+                        uint64_t row_bytes, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
 // png_adam7.hip
 int fdh_launch_png_adam7(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, const uint8_t* method,
                          const uint32_t* upstream, const uint32_t* upstream_len, uint32_t* status, uint64_t n, uint32_t width,

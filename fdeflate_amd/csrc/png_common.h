@@ -22,6 +22,8 @@ constexpr uint32_t kPngScanNoSignature = 1, kPngScanTruncated = 2, kPngScanBadIh
 constexpr uint32_t kPngScanChunkStructure = 5, kPngScanCrcMismatch = 6;
 // the decode steps behind the scan: the file's geometry is not the call's; the gather's destination; OR-ed into kPngOk by the expansion
 constexpr uint32_t kPngOtherGeometry = 7, kPngCompSlotTooSmall = 8, kPngIndexOutsidePalette = 9, kPngBadPlte = 10, kPngBadTrns = 11;
+// the encode steps in front of the filters: more distinct colours than the call allows; a pixel the pair cannot hold (OR-ed into kPngOk)
+constexpr uint32_t kPngTooManyColours = 12, kPngNotRepresentable = 13;
 
 static_assert(kPngOk == FDH_PNG_STATUS_OK && kPngBadFilterType == FDH_PNG_STATUS_BAD_FILTER_TYPE && kPngBadSizes == FDH_PNG_STATUS_BAD_SIZES &&
               kPngSkipped == FDH_PNG_STATUS_SKIPPED && kPngScanNoSignature == FDH_PNG_STATUS_SCAN_NO_SIGNATURE &&
@@ -29,7 +31,8 @@ static_assert(kPngOk == FDH_PNG_STATUS_OK && kPngBadFilterType == FDH_PNG_STATUS
               kPngScanInterlaced == FDH_PNG_STATUS_SCAN_INTERLACED && kPngScanChunkStructure == FDH_PNG_STATUS_SCAN_CHUNK_STRUCTURE &&
               kPngScanCrcMismatch == FDH_PNG_STATUS_SCAN_CRC_MISMATCH && kPngOtherGeometry == FDH_PNG_STATUS_OTHER_GEOMETRY &&
               kPngCompSlotTooSmall == FDH_PNG_STATUS_COMP_SLOT_TOO_SMALL && kPngIndexOutsidePalette == FDH_PNG_STATUS_INDEX_OUTSIDE_PALETTE &&
-              kPngBadPlte == FDH_PNG_STATUS_BAD_PLTE && kPngBadTrns == FDH_PNG_STATUS_BAD_TRNS, "the public header names the same values");
+              kPngBadPlte == FDH_PNG_STATUS_BAD_PLTE && kPngBadTrns == FDH_PNG_STATUS_BAD_TRNS &&
+              kPngTooManyColours == FDH_PNG_STATUS_TOO_MANY_COLOURS && kPngNotRepresentable == FDH_PNG_STATUS_NOT_REPRESENTABLE, "the public header names the same values");
 
 // ---- geometry ----
 // the fifteen depth / colour-type pairs of the PNG specification (11.2.2, table 11.1)

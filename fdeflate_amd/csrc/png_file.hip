@@ -182,9 +182,10 @@ struct CrcArgs {
     uint32_t* status;
     uint64_t n;
     uint32_t pieces;  // wavefronts per range; above 1 they xor into crc[i], which the host has zeroed
-    // frame mode (png_status != nullptr): range i is "IDAT" + the stream of file i, 37 bytes into its slot, and the sum
-    // goes to the aligned word inside the 16 bytes behind the stream (png_frame_finish_kernel picks it up there)
+    // frame mode (png_status != nullptr): range i is "IDAT" + the stream of file i, prefix - 4 bytes into its slot, and the
+    // sum goes to the aligned word inside the 16 bytes behind the stream (png_frame_finish_kernel picks it up there)
     const uint32_t* png_status;
+    uint32_t prefix;
 };
 
 constexpr uint32_t kPngPrefix = 41, kPngSuffix = 16;
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(THREADS) void crc32_ranges_kernel(CrcArgs a) {
     if (a.png_status) {
         if (a.png_status[i] != kPngOk) return;
         const uint32_t s = a.len[i];
-        const uint8_t* b = a.data + o + (kPngPrefix - 4);
+        const uint8_t* b = a.data + o + (a.prefix - 4);
         const uint32_t c = crc_piece<COPIES>(T, lane, b, b + 4 + s, 0u, w, a.pieces);
         uint32_t* sum = frame_sum_word(const_cast<uint8_t*>(b) + 4 + s);
         if (lane == 0) {
@@ -245,6 +246,12 @@ struct FrameArgs {
     uint32_t* png_status;
     uint64_t n;
     uint32_t width, bit_depth, colour_type;
+    uint32_t prefix;  // bytes in front of the stream: kPngPrefix, more with PLTE and tRNS
+    // fdh_png_frame_palette_batch only
+    const uint32_t* pal;
+    const uint32_t* colour;
+    const uint32_t* trns_len;
+    uint32_t plte_entries, trns_entries;
 };
 
 __device__ __forceinline__ uint32_t crc_bitwise(uint32_t c, uint32_t v) {
@@ -264,19 +271,13 @@ __device__ __forceinline__ uint32_t get_be32(const uint8_t* p) {
     return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
 }
 
-// One file per lane: the checks, the prefix (the IHDR's own CRC is 17 bytes of bit-at-a-time arithmetic), a zero in the
-// word that will collect the IDAT checksum.
-__global__ __launch_bounds__(256) void png_frame_prefix_kernel(FrameArgs a) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.n) return;
-    const uint64_t o = a.file_off[i], slot = a.file_off[i + 1] - o;
-    const uint32_t s = a.idat_len[i], h = a.height[i];
-    if (s == 0 || s > 0x7FFFFFFFu || (uint64_t)s + kPngPrefix + kPngSuffix > slot || h == 0 || h > 0x7FFFFFFFu) {
-        a.png_status[i] = kPngBadSizes;  // (0xFFFFFFFF, the encoders' "slot too small", is above 2^31 - 1)
-        a.file_len[i] = 0;
-        return;
-    }
-    uint8_t* f = a.file + o;
+// what both framing calls refuse: (0xFFFFFFFF, the encoders' "slot too small", is above 2^31 - 1)
+__device__ __forceinline__ bool frame_sizes_bad(uint32_t s, uint32_t h, uint64_t slot, uint32_t prefix) {
+    return s == 0 || s > 0x7FFFFFFFu || (uint64_t)s + prefix + kPngSuffix > slot || h == 0 || h > 0x7FFFFFFFu;
+}
+
+// the first 33 bytes of a file: signature and IHDR (its CRC is 17 bytes of bit-at-a-time arithmetic)
+__device__ __forceinline__ void put_signature_ihdr(uint8_t* f, const FrameArgs& a, uint32_t h) {
     const uint8_t head[16] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n', 0, 0, 0, 13, 'I', 'H', 'D', 'R'};
     for (int k = 0; k < 16; k++) f[k] = head[k];
     put_be32(f + 16, a.width);
@@ -295,21 +296,99 @@ __global__ __launch_bounds__(256) void png_frame_prefix_kernel(FrameArgs a) {
     c = crc_bitwise(c, a.colour_type);
     for (int k = 0; k < 3; k++) c = crc_bitwise(c, 0);
     put_be32(f + 29, ~c);
-    put_be32(f + 33, s);
-    f[37] = 'I';
-    f[38] = 'D';
-    f[39] = 'A';
-    f[40] = 'T';
+}
+
+// a chunk's length and type
+__device__ __forceinline__ void put_chunk_head(uint8_t* p, uint32_t len, char t0, char t1, char t2, char t3) {
+    put_be32(p, len);
+    p[4] = (uint8_t)t0;
+    p[5] = (uint8_t)t1;
+    p[6] = (uint8_t)t2;
+    p[7] = (uint8_t)t3;
+}
+
+// One file per lane: the checks, the prefix, a zero in the word that will collect the IDAT checksum.
+__global__ __launch_bounds__(256) void png_frame_prefix_kernel(FrameArgs a) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const uint64_t o = a.file_off[i], slot = a.file_off[i + 1] - o;
+    const uint32_t s = a.idat_len[i], h = a.height[i];
+    if (frame_sizes_bad(s, h, slot, kPngPrefix)) {
+        a.png_status[i] = kPngBadSizes;
+        a.file_len[i] = 0;
+        return;
+    }
+    uint8_t* f = a.file + o;
+    put_signature_ihdr(f, a, h);
+    put_chunk_head(f + 33, s, 'I', 'D', 'A', 'T');
     *frame_sum_word(f + kPngPrefix + s) = 0;
     a.file_len[i] = s + kPngPrefix + kPngSuffix;
     a.png_status[i] = kPngOk;
+}
+
+// fdh_png_frame_palette_batch: one file per wavefront, four to a workgroup that shares the CRC tables.  Lane 0 writes
+// signature, IHDR and the chunk heads; the lanes together write the PLTE's E entries (the image's own, then 0, 0, 0) and
+// the tRNS's T alphas (then 255), and the CRC of each chunk is wave_crc over the bytes just written.
+__global__ __launch_bounds__(256) void png_frame_palette_prefix_kernel(FrameArgs a) {
+    __shared__ CrcLds<1> lds;
+    lds.load((int)threadIdx.x, 256);
+    const int lane = (int)threadIdx.x & 63;
+    const uint64_t i = (uint64_t)blockIdx.x * 4 + uni(threadIdx.x >> 6);
+    if (i >= a.n) return;
+    const uint64_t o = a.file_off[i], slot = a.file_off[i + 1] - o;
+    const uint32_t s = uni(a.idat_len[i]), h = uni(a.height[i]);
+    const uint32_t count = uni(a.colour[4 * i]), alphas = uni(a.trns_len[i]);
+    const uint32_t E = a.plte_entries, T = a.trns_entries;
+    const uint32_t st = frame_sizes_bad(s, h, slot, a.prefix) ? kPngBadSizes : (count == 0 || count > E) ? kPngBadPlte : alphas > T ? kPngBadTrns : kPngOk;
+    if (st != kPngOk) {
+        if (lane == 0) {
+            a.png_status[i] = st;
+            a.file_len[i] = 0;
+        }
+        return;
+    }
+    CrcLane<1> C{lds.t};
+    uint8_t* f = a.file + o;
+    const uint32_t* pal = a.pal + 256 * i;
+    uint8_t* plte = f + 33;
+    if (lane == 0) {
+        put_signature_ihdr(f, a, h);
+        put_chunk_head(plte, 3 * E, 'P', 'L', 'T', 'E');
+    }
+    for (uint32_t e = (uint32_t)lane; e < E; e += 64) {
+        const uint32_t w = e < count ? pal[e] : 0u;
+        plte[8 + 3 * e] = (uint8_t)w;
+        plte[9 + 3 * e] = (uint8_t)(w >> 8);
+        plte[10 + 3 * e] = (uint8_t)(w >> 16);
+    }
+    uint8_t* next = plte + 12 + 3 * E;
+    if (T) {
+        if (lane == 0) put_chunk_head(next, T, 't', 'R', 'N', 'S');
+        for (uint32_t e = (uint32_t)lane; e < T; e += 64) next[8 + e] = e < count ? (uint8_t)(pal[e] >> 24) : (uint8_t)255;
+    }
+    // the wavefront reads back what its lanes wrote: the stores are complete before the loads are issued
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t c_plte = ~wave_crc<1>(C, lane, plte + 4, plte + 8 + 3 * E, 0xFFFFFFFFu);
+    if (lane == 0) put_be32(plte + 8 + 3 * E, c_plte);
+    if (T) {
+        const uint32_t c_trns = ~wave_crc<1>(C, lane, next + 4, next + 8 + T, 0xFFFFFFFFu);
+        if (lane == 0) put_be32(next + 8 + T, c_trns);
+        next += 12 + T;
+    }
+    if (lane == 0) {
+        put_chunk_head(next, s, 'I', 'D', 'A', 'T');
+        *frame_sum_word(f + a.prefix + s) = 0;
+        a.file_len[i] = s + a.prefix + kPngSuffix;
+        a.png_status[i] = kPngOk;
+    }
 }
 
 // One file per lane: the IDAT's CRC from the word it was summed in, then IEND.
 __global__ __launch_bounds__(256) void png_frame_finish_kernel(FrameArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n || a.png_status[i] != kPngOk) return;
-    uint8_t* t = a.file + a.file_off[i] + kPngPrefix + a.idat_len[i];
+    uint8_t* t = a.file + a.file_off[i] + a.prefix + a.idat_len[i];
     const uint32_t c = *frame_sum_word(t);
     const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
     put_be32(t, c);
@@ -619,27 +698,47 @@ hipError_t launch_crc(fdh::CrcArgs a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// what follows a framing call's prefix kernel: the IDAT's checksum into its word, then the 16 bytes behind the stream
+hipError_t launch_frame_tail(const fdh::FrameArgs& a, hipStream_t stream) {
+    fdh::CrcArgs c{a.file, a.file_off, a.idat_len, nullptr, nullptr, nullptr, a.n, 1, a.png_status, a.prefix};
+    hipError_t e = launch_crc(c, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fdh::png_frame_finish_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" int fdh_launch_crc32(const uint8_t* data, const uint64_t* off, const uint32_t* len, const uint32_t* seed,
                                 uint32_t* crc, uint32_t* status, uint64_t n, hipStream_t stream) {
-    fdh::CrcArgs a{data, off, len, seed, crc, status, n, 1, nullptr};
+    fdh::CrcArgs a{data, off, len, seed, crc, status, n, 1, nullptr, 0};
     return (int)launch_crc(a, stream);
 }
 
 extern "C" int fdh_launch_png_frame(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height,
                                     uint32_t* file_len, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth,
                                     uint32_t colour_type, hipStream_t stream) {
-    fdh::FrameArgs a{file, file_off, idat_len, height, file_len, png_status, n, width, bit_depth, colour_type};
+    fdh::FrameArgs a{file, file_off, idat_len, height, file_len, png_status, n, width, bit_depth, colour_type, fdh::kPngPrefix,
+                     nullptr, nullptr, nullptr, 0, 0};
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     hipLaunchKernelGGL(fdh::png_frame_prefix_kernel, grid, block, 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    fdh::CrcArgs c{file, file_off, idat_len, nullptr, nullptr, nullptr, n, 1, png_status};
-    e = launch_crc(c, stream);
+    return (int)launch_frame_tail(a, stream);
+}
+
+// The same three steps with a longer prefix: signature, IHDR, PLTE, tRNS and the IDAT's head in front of the stream.
+extern "C" int fdh_launch_png_frame_palette(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const uint32_t* height,
+                                            const uint32_t* pal, const uint32_t* colour, const uint32_t* trns_len, uint32_t* file_len,
+                                            uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t plte_entries,
+                                            uint32_t trns_entries, hipStream_t stream) {
+    const uint32_t prefix = fdh::kPngPrefix + 12 + 3 * plte_entries + (trns_entries ? 12 + trns_entries : 0);
+    fdh::FrameArgs a{file, file_off, idat_len, height, file_len, png_status, n, width, bit_depth, 3, prefix,
+                     pal, colour, trns_len, plte_entries, trns_entries};
+    hipLaunchKernelGGL(fdh::png_frame_palette_prefix_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(fdh::png_frame_finish_kernel, grid, block, 0, stream, a);
-    return (int)hipGetLastError();
+    return (int)launch_frame_tail(a, stream);
 }
 
 extern "C" int fdh_launch_png_scan(const uint8_t* file, const uint64_t* file_off, const uint32_t* file_len, fdh_png_info* info,

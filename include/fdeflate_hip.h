@@ -477,6 +477,81 @@ int fdh_png_unfilter_interlaced_batch(uint8_t *filt, const uint64_t *filt_off, u
                                       uint32_t *png_status, uint64_t n, uint32_t width,
                                       uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
 
+/* ---- PNG encode from RGBA8: analysis, packing, palette files ----------------------------------------
+ * The encode side's counterpart of the section "PNG decode to RGBA8": [rows, width, 4] uint8 pictures, R, G, B, A,
+ * become packed scanlines of a depth / colour pair (what fdh_png_choose_filters_batch and
+ * fdh_png_filter_deflate_ultrafast_batch take), and a palette file gets its PLTE and tRNS.  Nothing is read back.
+ *
+ * fdh_png_analyse_batch -- what image i = rgba[rgba_off[i] .. rgba_off[i+1]) is: whole rows of width * 4 bytes at
+ * any alignment.  max_colours is 1 .. 256.
+ *   pal[256 n]    the image's distinct pixels as words R | G << 8 | B << 16 | A << 24 (the layout of
+ *                 fdh_png_colour_batch) in ASCENDING order as unsigned 32-bit integers.  A is the most significant
+ *                 byte, so every entry with A < 255 sits in front of every opaque one and a tRNS chunk can end behind
+ *                 the last of them; and the order makes the result independent of launch shape and scheduling.
+ *                 Entries behind the count are 0xFF000000.  Nullable: then only the other outputs are produced.
+ *   colour[4 n]   word 0 the number of distinct pixels, words 1 .. 3 zero: what fdh_png_expand_batch takes
+ *   trns_len[n]   the number of entries with A < 255
+ *   summary[n]    bit 0: every A is 255; bit 1: every pixel has R == G == B; bits 8 .. 15: the smallest d of 1, 2, 4,
+ *                 8 such that every R, G and B is a multiple of 255 / (2^d - 1), the grey / RGB sample depth that
+ *                 loses nothing.  Always over the whole image, also when the colours overflow.  An image of no rows:
+ *                 status 0, no colours, bits 0 and 1 set, depth 1.
+ * png_status[i]: 0 ok; 2 the slot is not whole rows: nothing is written for that image; 12 more than max_colours
+ * distinct pixels: summary[i] is valid, pal, colour and trns_len of the image are not specified.
+ * One workgroup per image with the set in an LDS hash table; FDH_PNG_ANALYSE_WAVES (environment) sets its wavefronts,
+ * 1 .. 16, and the result is the same at every setting.  No workspace, no host synchronisation.  width 0 or above
+ * 2^31-1, or max_colours outside 1 .. 256: FDH_ERR_INVALID_ARGUMENT.
+ *
+ * fdh_png_pack_batch -- the exact inverse of fdh_png_expand_batch: image i to the slot pix[pix_off[i] ..
+ * pix_off[i+1]) of exactly rows * row_bytes bytes.  Samples are packed as PNG packs them (most significant bits
+ * first, 16-bit samples big-endian); the padding bits of a row are zero.
+ *   colour type 6  depth 8 copies; depth 16 writes each sample s as the bytes s, s (s * 257: to8 gives s back)
+ *   colour type 2  the same without A; needs every A == 255
+ *   colour type 4  R and A; needs R == G == B
+ *   colour type 0  needs both; below depth 8, R must be a multiple of 255 / (2^depth - 1): the sample is the quotient
+ *   colour type 3  the index is the lowest k < count with pal[k] equal to the pixel word, count = colour[4 i]
+ *                  (256 where colour is null, and at most 256); it must be below 2^depth.  pal is required; it need
+ *                  not be sorted or free of duplicates.
+ * Colour keys (tRNS with colour types 0 and 2) are not produced: colour words 1 .. 3 are ignored.
+ *   upstream  nullable; where upstream[i] != 0 the image is skipped and png_status[i] = upstream[i]
+ * png_status[i]:
+ *   0  ok: fdh_png_expand_batch of the pix slot, with the same pal / colour, gives the image back byte for byte
+ *   2  the RGBA slot is not whole rows, or the pix slot is not exactly rows * row_bytes: nothing is written
+ *   13 some pixel has no lossless representation in the pair; the contents of the pix slot are not specified
+ * No byte outside a pix slot is written, no byte outside rgba[rgba_off[0] .. rgba_off[n]) is read.  An illegal pair
+ * or width: FDH_ERR_INVALID_ARGUMENT.  FDH_PNG_PACK_WAVES (environment) sets the number of wavefronts per image.
+ *
+ * fdh_png_palette_file_prefix / fdh_png_frame_palette_batch -- fdh_png_frame_batch for colour type 3, where a file
+ * needs a PLTE: again the zlib stream of image i is already in place, now at file_off[i] + prefix with
+ *   prefix = 41 + 12 + 3 E + (T ? 12 + T : 0),   E = plte_entries in 1 .. min(256, 2^bit_depth),  T = trns_entries in 0 .. E
+ * the same for every file of the call, so that the encoders' single offsets array still serves (the function returns 0
+ * for an E outside 1 .. 256 or a T above E).  The prefix holds, in order: signature, IHDR, a PLTE of E entries -- the
+ * colour[4 i] entries of pal[256 i ..], then 0, 0, 0 --, where T > 0 a tRNS of T bytes -- the alphas of those entries,
+ * then 255 --, and the IDAT's length and type; the 16 bytes behind the stream are fdh_png_frame_batch's.  Every
+ * chunk's CRC is computed on the device.  file_len[i] = idat_len[i] + prefix + 16.  Unused palette entries and a tRNS
+ * shorter than the PLTE are both legal PNG.
+ * png_status[i] -- nothing is written and file_len[i] = 0 unless it is 0; the first that applies:
+ *   2  fdh_png_frame_batch's conditions (with this prefix)
+ *   10 colour[4 i] is 0 or above E
+ *   11 trns_len[i] is above T
+ * An illegal width or depth, E or T: FDH_ERR_INVALID_ARGUMENT.
+ */
+#define FDH_PNG_STATUS_TOO_MANY_COLOURS 12u  /* fdh_png_analyse_batch */
+#define FDH_PNG_STATUS_NOT_REPRESENTABLE 13u /* fdh_png_pack_batch */
+int fdh_png_analyse_batch(const uint8_t *rgba, const uint64_t *rgba_off, uint32_t *pal,
+                          uint32_t *colour, uint32_t *trns_len, uint32_t *summary,
+                          uint32_t *png_status, uint64_t n, uint32_t width, uint32_t max_colours,
+                          void *hip_stream);
+int fdh_png_pack_batch(const uint8_t *rgba, const uint64_t *rgba_off, uint8_t *pix,
+                       const uint64_t *pix_off, const uint32_t *pal, const uint32_t *colour,
+                       const uint32_t *upstream, uint32_t *png_status, uint64_t n, uint32_t width,
+                       uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
+uint64_t fdh_png_palette_file_prefix(uint32_t plte_entries, uint32_t trns_entries);
+int fdh_png_frame_palette_batch(uint8_t *file, const uint64_t *file_off, const uint32_t *idat_len,
+                                const uint32_t *height, const uint32_t *pal, const uint32_t *colour,
+                                const uint32_t *trns_len, uint32_t *file_len, uint32_t *png_status,
+                                uint64_t n, uint32_t width, uint32_t bit_depth,
+                                uint32_t plte_entries, uint32_t trns_entries, void *hip_stream);
+
 /* ---- streaming decoder: `Decompressor` (src/decompress.rs:96-156, 179-342) ----------------
  * A host-side object with exactly `Decompressor::read`'s contract on HOST buffers; every bit of
  * decoding is done by fdh_inflate_batch_resumable on the device (the object keeps a device-resident
