@@ -777,6 +777,208 @@ def png_decode_files_rgba_batch(file, file_off, width, bit_depth, colour_type, f
 
 
 # ------------------------------------------------------------------------------------------
+# PNG decode: mixed batches (every image's geometry from its own scan record)
+# ------------------------------------------------------------------------------------------
+
+class _PngInfoRecord(C.Structure):
+    """fdh_png_info"""
+    _fields_ = [("status", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("bit_depth", C.c_uint8),
+                ("colour_type", C.c_uint8), ("interlace", C.c_uint8), ("pad", C.c_uint8), ("idat_bytes", C.c_uint32),
+                ("idat_chunks", C.c_uint32), ("first_idat", C.c_uint32), ("chunks", C.c_uint32)]
+
+
+def png_plan_sizes(record, max_bytes=0):
+    """What a pipeline has to allocate for one image (fdh_png_plan_sizes: host arithmetic, no device call).  `record`:
+    a mapping with the fields of fdh_png_info that matter here (status, width, height, bit_depth, colour_type,
+    interlace, idat_bytes; a field that is missing counts as 0).  -> (status, compressed, filtered, packed, rgba):
+    status 0 ok, 3 the record is not decodable, 2 the filtered size is 2^32 or more or the largest size exceeds a
+    max_bytes that is not 0; the sizes are all 0 unless the status is."""
+    rec = _PngInfoRecord(**{k: int(record.get(k, 0)) for k, _ in _PngInfoRecord._fields_})
+    sizes = (C.c_uint64 * 4)()
+    st = _lib.lib().fdh_png_plan_sizes(C.byref(rec), int(max_bytes), sizes)
+    return (int(st),) + tuple(int(v) for v in sizes)
+
+
+def png_plan_batch(info, max_bytes=0, comp_size=True, filt_size=True, pix_size=True, rgba_size=True, png_status=None):
+    """png_plan_sizes for n scan records on the device (fdh_png_plan_batch).  Each of the four outputs is True
+    (allocated), a tensor (int64 [n]) or None / False (not wanted).
+    -> (comp_size, filt_size, pix_size, rgba_size, png_status), None for an output that was not wanted."""
+    import torch
+    n = info.numel() // PNG_INFO_WORDS
+    outs = []
+    for want in (comp_size, filt_size, pix_size, rgba_size):
+        if want is True:
+            want = torch.empty(n, dtype=torch.int64, device=info.device)
+        elif want is False:
+            want = None
+        outs.append(want)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=info.device)
+    with _OnDevice(info, png_status, *outs) as stream:
+        _lib.check(_lib.lib().fdh_png_plan_batch(_ptr(info), int(max_bytes), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]),
+                                                _ptr(png_status), n, C.c_void_p(stream)))
+    return outs[0], outs[1], outs[2], outs[3], png_status
+
+
+def png_gather_idat_mixed_batch(file, file_off, info, comp, comp_off, upstream=None, comp_len=None, png_status=None):
+    """png_gather_idat_batch for files of any geometry (fdh_png_gather_idat_mixed_batch) -> (comp_len, png_status):
+    0 ok, 3 the record is not decodable (or does not describe the file), 8 comp slot too small, or upstream[i] where
+    that is not 0."""
+    import torch
+    n = file_off.numel() - 1
+    if comp_len is None:
+        comp_len = torch.empty(n, dtype=torch.int32, device=file.device)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
+    with _OnDevice(file, file_off, info, upstream, comp, comp_off, comp_len, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_gather_idat_mixed_batch(_ptr(file), _ptr(file_off), _ptr(info), _ptr(upstream), _ptr(comp),
+                                                             _ptr(comp_off), _ptr(comp_len), _ptr(png_status), n, C.c_void_p(stream)))
+    return comp_len, png_status
+
+
+def png_colour_mixed_batch(file, file_off, info, upstream=None, pal=None, colour=None, png_status=None):
+    """png_colour_batch with every file's own depth and colour type (fdh_png_colour_mixed_batch) -> (pal, colour,
+    png_status): pal int32 [n, 256] -- row i is written only if file i has colour type 3 --, colour int32 [n, 4];
+    png_status 0, 3, 10, 11, or upstream[i] where that is not 0."""
+    import torch
+    n = file_off.numel() - 1
+    dev = file.device
+    if pal is None:
+        pal = torch.empty((n, 256), dtype=torch.int32, device=dev)
+    if colour is None:
+        colour = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=dev)
+    with _OnDevice(file, file_off, info, upstream, pal, colour, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_colour_mixed_batch(_ptr(file), _ptr(file_off), _ptr(info), _ptr(upstream), _ptr(pal), _ptr(colour),
+                                                        _ptr(png_status), n, C.c_void_p(stream)))
+    return pal, colour, png_status
+
+
+def png_unfilter_mixed_batch(filt, filt_off, pix, pix_off, info, upstream=None, upstream_len=None, png_status=None):
+    """png_unfilter_interlaced_batch at every image's own geometry and interlace method (fdh_png_unfilter_mixed_batch):
+    the slots must be exactly the plan's filtered and packed sizes.  `filt` is reconstructed in place.
+    -> png_status: 0 ok, 1 a filter type above 4, 2 sizes do not fit, 3 not decodable or upstream[i] != 0."""
+    import torch
+    n = filt_off.numel() - 1
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=filt.device)
+    with _OnDevice(filt, filt_off, pix, pix_off, info, upstream, upstream_len, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_unfilter_mixed_batch(_ptr(filt), _ptr(filt_off), _ptr(pix), _ptr(pix_off), _ptr(info), _ptr(upstream),
+                                                          _ptr(upstream_len), _ptr(png_status), n, C.c_void_p(stream)))
+    return png_status
+
+
+def png_expand_mixed_batch(pix, pix_off, rgba, rgba_off, info, pal=None, colour=None, upstream=None, png_status=None):
+    """png_expand_batch at every image's own geometry (fdh_png_expand_mixed_batch).  pal / colour as
+    png_colour_mixed_batch writes them; an image of colour type 3 without `pal` is status 10.
+    -> png_status: 0 ok, 2 the slots do not fit, 3 not decodable, 9 an index outside the palette, or upstream[i]."""
+    import torch
+    n = pix_off.numel() - 1
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
+    with _OnDevice(pix, pix_off, rgba, rgba_off, info, pal, colour, upstream, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_expand_mixed_batch(_ptr(pix), _ptr(pix_off), _ptr(rgba), _ptr(rgba_off), _ptr(info), _ptr(pal),
+                                                        _ptr(colour), _ptr(upstream), _ptr(png_status), n, C.c_void_p(stream)))
+    return png_status
+
+
+def _read_back(t):
+    """The one place where the mixed pipeline moves anything from the device to the host (tests count the bytes)."""
+    return t.tolist()
+
+
+def _png_mixed_files_to_pixels(file, file_off, file_len, flags, max_bytes, route, rgba):
+    """What png_decode_mixed_files_batch and png_decode_mixed_files_rgba_batch share: scan, plan, the four cumulative
+    sums on the device, ONE read-back of six 64-bit words (the four totals, and the smallest and largest of the keys
+    width | depth << 32 | colour << 40 | interlace << 48 over the images the plan accepts), then gather, colour,
+    inflate and reconstruction.  A batch whose keys are all the same and not interlaced takes the calls of
+    png_decode_files_batch with that geometry, any other the mixed calls; `route` forces one.
+    -> (pix, pix_off, info, status, png_status, rgba_off, pal, colour, total pixel bytes, total RGBA bytes, geometry of
+    the uniform route or None)."""
+    import torch
+    if route not in (None, "mixed", "uniform"):
+        raise ValueError("route must be None, 'mixed' or 'uniform'")
+    n = file_off.numel() - 1
+    dev = file.device
+    info = png_scan_files_batch(file, file_off, file_len, flags=flags)
+    comp_size, filt_size, pix_size, rgba_size, png_status = png_plan_batch(info, max_bytes)
+    offs = torch.zeros((4, n + 1), dtype=torch.int64, device=dev)
+    torch.cumsum(torch.stack((comp_size, filt_size, pix_size, rgba_size)), 1, out=offs[:, 1:])
+    words = info.view(-1, PNG_INFO_WORDS).to(torch.int64)
+    key = (words[:, 1] & 0xFFFFFFFF) | ((words[:, 3] & 0xFFFFFF) << 32)
+    planned = png_status == 0
+    none_lo, none_hi = torch.full((1,), 1 << 62, dtype=torch.int64, device=dev), torch.full((1,), -1, dtype=torch.int64, device=dev)
+    key_lo = torch.where(planned, key, none_lo).amin(0, keepdim=True) if n else none_lo
+    key_hi = torch.where(planned, key, none_hi).amax(0, keepdim=True) if n else none_hi
+    summary = torch.cat((offs[:, n], key_lo, key_hi))
+    total_comp, total_filt, total_pix, total_rgba, key_min, key_max = _read_back(summary)   # the one read-back: 48 bytes
+    uniform = key_min == key_max and (key_min >> 48) == 0
+    if route == "uniform" and not uniform and key_min <= key_max:
+        raise ValueError("route='uniform' on a batch whose files differ in geometry (or are interlaced)")
+    uniform = uniform and route != "mixed"
+    comp_off, filt_off, pix_off = offs[0], offs[1], offs[2]
+    comp = torch.empty(max(1, total_comp), dtype=torch.uint8, device=dev)
+    filt = torch.empty(max(1, total_filt), dtype=torch.uint8, device=dev)
+    pix = torch.empty(max(1, total_pix), dtype=torch.uint8, device=dev)
+    pal = colour = geometry = None
+    if uniform:
+        geometry = (key_min & 0xFFFFFFFF, (key_min >> 32) & 0xFF, (key_min >> 40) & 0xFF)
+        row_bytes, bpp = png_geometry(*geometry)
+        _, gathered = png_gather_idat_batch(file, file_off, info, comp, comp_off, *geometry)
+        png_status = torch.where(png_status != 0, png_status, gathered)
+        if rgba:
+            pal, colour, coloured = png_colour_batch(file, file_off, info, *geometry)
+            png_status = torch.where(png_status != 0, png_status, coloured)
+        _, status, _, unfiltered = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0)
+    else:
+        _, png_status = png_gather_idat_mixed_batch(file, file_off, info, comp, comp_off, upstream=png_status)
+        if rgba:
+            pal, colour, png_status = png_colour_mixed_batch(file, file_off, info, upstream=png_status)
+        out_len, status, _ = inflate_batch(comp, comp_off, filt, filt_off, flags=0)
+        unfiltered = png_unfilter_mixed_batch(filt, filt_off, pix, pix_off, info, upstream=torch.where(png_status != 0, png_status, status),
+                                              upstream_len=out_len)
+    png_status = torch.where(png_status != 0, png_status, unfiltered)
+    return pix, pix_off, info, status, png_status, offs[3], pal, colour, total_pix, total_rgba, geometry
+
+
+def png_decode_mixed_files_batch(file, file_off, file_len=None, flags=0, max_bytes=0, route=None):
+    """PNG files of any width, height, depth, colour type and interlace method in, packed scanlines out, on torch's
+    current stream: png_scan_files_batch, png_plan_batch, the buffers sized on the device with ONE read-back of 48
+    bytes (not of `info`), png_gather_idat_mixed_batch, inflate_batch, png_unfilter_mixed_batch.  `flags` as
+    png_decode_files_batch (without PNG_FLAG_ADAM7 an interlaced file is info.status 4 and png_status 3); max_bytes:
+    a file one of whose buffers would be larger is png_status 2 with empty slots, before anything is allocated (0: no
+    limit but the decoder's 2^32 - 1 bytes per stream).  A batch whose sound files all have one geometry and are not
+    interlaced takes png_decode_files_batch's calls instead (the fused inflate_png_batch) and loses nothing;
+    route="mixed" / "uniform" forces one of the two for tests (ValueError for "uniform" on a batch that is not).
+    -> (pix, pix_off, info, status, png_status): image i at pix[pix_off[i]:pix_off[i+1]], height_i rows of ITS
+    row_bytes (info says which); status the zlib decoder's; png_status the first that is not 0 of plan, gather,
+    reconstruction (2, 3; 3, 8; 1 .. 3)."""
+    pix, pix_off, info, status, png_status, _, _, _, total, _, _ = _png_mixed_files_to_pixels(file, file_off, file_len, flags, max_bytes,
+                                                                                             route, False)
+    return pix[:total], pix_off, info, status, png_status
+
+
+def png_decode_mixed_files_rgba_batch(file, file_off, file_len=None, flags=0, max_bytes=0, route=None):
+    """png_decode_mixed_files_batch with png_colour_mixed_batch behind the gather and png_expand_mixed_batch at the end
+    -> (rgba, rgba_off, info, status, png_status): rgba[rgba_off[i]:rgba_off[i+1]].view(height_i, width_i, 4) is
+    picture i as png_decode_files_rgba_batch makes it; png_status the first that is not 0 of plan, gather, colour,
+    reconstruction and expansion (2, 3; 3, 8; 10, 11; 1 .. 3; 9)."""
+    import torch
+    pix, pix_off, info, status, png_status, rgba_off, pal, colour, _, total, geometry = _png_mixed_files_to_pixels(
+        file, file_off, file_len, flags, max_bytes, route, True)
+    rgba = torch.empty(max(1, total), dtype=torch.uint8, device=file.device)
+    if file_off.numel() > 1:
+        upstream = torch.where(png_status != 0, png_status, status)   # (a zlib status reaches expand as "not 0")
+        if geometry is not None:
+            expanded = png_expand_batch(pix, pix_off, rgba, rgba_off, *geometry, pal=pal, colour=colour, upstream=upstream)
+        else:
+            expanded = png_expand_mixed_batch(pix, pix_off, rgba, rgba_off, info, pal=pal, colour=colour, upstream=upstream)
+        png_status = torch.where(png_status != 0, png_status, expanded)
+    return rgba[:total], rgba_off, info, status, png_status
+
+
+# ------------------------------------------------------------------------------------------
 # PNG encode from RGBA8: analysis, packing, palette files
 # ------------------------------------------------------------------------------------------
 

@@ -308,6 +308,57 @@ int fdh_png_unfilter_interlaced_batch(uint8_t* filt, const uint64_t* filt_off, u
                     upstream_len, png_status, n, width, bit_depth, colour_type, stream_of(hip_stream)));
 }
 
+// ---- PNG decode: mixed batches (png_mixed.hip) ----
+uint32_t fdh_png_plan_sizes(const fdh_png_info* rec, uint64_t max_bytes, uint64_t sizes[4]) {
+    uint64_t s[4] = {0, 0, 0, 0};
+    const uint32_t st = rec ? fdh::png_plan(*rec, max_bytes, s[0], s[1], s[2], s[3]) : FDH_PNG_STATUS_SKIPPED;
+    if (sizes) std::copy(s, s + 4, sizes);
+    return st;
+}
+
+int fdh_png_plan_batch(const fdh_png_info* info, uint64_t max_bytes, uint64_t* comp_size, uint64_t* filt_size, uint64_t* pix_size,
+                       uint64_t* rgba_size, uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({info, png_status}, "null pointer", n, "records")) return rc;
+    return launched("PNG plan kernel launch", fdh_launch_png_plan(info, max_bytes, comp_size, filt_size, pix_size, rgba_size, png_status, n,
+                    stream_of(hip_stream)));
+}
+
+int fdh_png_gather_idat_mixed_batch(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, const uint32_t* upstream,
+                                    uint8_t* comp, const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n,
+                                    void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({file, file_off, info, comp, comp_off, comp_len, png_status}, "null pointer", n, "files")) return rc;
+    return launched("IDAT gather kernel launch", fdh_launch_png_gather_mixed(file, file_off, info, upstream, comp, comp_off, comp_len,
+                    png_status, n, stream_of(hip_stream)));
+}
+
+int fdh_png_colour_mixed_batch(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, const uint32_t* upstream,
+                               uint32_t* pal, uint32_t* colour, uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({file, file_off, info, pal, colour, png_status}, "null pointer", n, "files")) return rc;
+    return launched("PLTE / tRNS kernel launch", fdh_launch_png_colour_mixed(file, file_off, info, upstream, pal, colour, png_status, n,
+                    stream_of(hip_stream)));
+}
+
+int fdh_png_unfilter_mixed_batch(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, const fdh_png_info* info,
+                                 const uint32_t* upstream, const uint32_t* upstream_len, uint32_t* png_status, uint64_t n,
+                                 void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({filt, filt_off, pix, pix_off, info, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed reconstruction / placement kernel launch", fdh_launch_png_unfilter_mixed(filt, filt_off, pix, pix_off, info,
+                    upstream, upstream_len, png_status, n, stream_of(hip_stream)));
+}
+
+int fdh_png_expand_mixed_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
+                               const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
+                               uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({pix, pix_off, rgba, rgba_off, info, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed RGBA expansion kernel launch", fdh_launch_png_expand_mixed(pix, pix_off, rgba, rgba_off, info, pal, colour,
+                    upstream, png_status, n, stream_of(hip_stream)));
+}
+
 // ---- PNG encode from RGBA8: analysis and packing (png_pack.hip), palette framing (png_file.hip) ----
 int fdh_png_analyse_batch(const uint8_t* rgba, const uint64_t* rgba_off, uint32_t* pal, uint32_t* colour, uint32_t* trns_len,
                           uint32_t* summary, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t max_colours, void* hip_stream) {

@@ -80,6 +80,19 @@ int fdh_launch_png_pack(const uint8_t* rgba, const uint64_t* rgba_off, uint8_t* 
 int fdh_launch_png_adam7(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, const uint8_t* method,
                          const uint32_t* upstream, const uint32_t* upstream_len, uint32_t* status, uint64_t n, uint32_t width,
                          uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+// png_mixed.hip
+int fdh_launch_png_plan(const fdh_png_info* info, uint64_t max_bytes, uint64_t* comp_size, uint64_t* filt_size, uint64_t* pix_size,
+                        uint64_t* rgba_size, uint32_t* png_status, uint64_t n, hipStream_t stream);
+int fdh_launch_png_gather_mixed(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, const uint32_t* upstream,
+                                uint8_t* comp, const uint64_t* comp_off, uint32_t* comp_len, uint32_t* png_status, uint64_t n,
+                                hipStream_t stream);
+int fdh_launch_png_colour_mixed(const uint8_t* file, const uint64_t* file_off, const fdh_png_info* info, const uint32_t* upstream,
+                                uint32_t* pal, uint32_t* colour, uint32_t* png_status, uint64_t n, hipStream_t stream);
+int fdh_launch_png_unfilter_mixed(uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, const fdh_png_info* info,
+                                  const uint32_t* upstream, const uint32_t* upstream_len, uint32_t* status, uint64_t n, hipStream_t stream);
+int fdh_launch_png_expand_mixed(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
+                                const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
+                                uint32_t* status, uint64_t n, hipStream_t stream);
 }
 
 namespace fdh {
@@ -89,6 +102,10 @@ inline int env_int(const char* name, int fallback) {
     const char* e = std::getenv(name);
     return e ? std::atoi(e) : fallback;
 }
+
+// Wavefronts per range / threads per file in the kernels of png_file.hip and png_mixed.hip that serve one file per
+// workgroup: a batch that fills the device by its count alone gets one wavefront per item.
+constexpr uint64_t kFillWaves = 4096;
 
 // Wavefronts per image for the kernels that hand an image's bands b, b + Y, .. to wavefront b of Y: Y is chosen so that
 // a small batch of tall images still fills the device; the environment variable `name` (1 .. 65535) sets it.

@@ -73,7 +73,7 @@ FDH_PNG_FN void adam7_pass_dims(uint32_t method, uint32_t p, uint64_t width, uin
 
 // The bytes the IDAT stream of a width x height image of `bits` bits per pixel decodes to: every row of every pass
 // with its type byte (method 1), or height * (1 + row bytes) (method 0).  An empty pass has no bytes.  adam7_image
-// (png_adam7.hip) checks every slot against this sum, written out there from the same adam7_pass_dims and png_row_bytes.
+// (png_adam7_body.h) checks every slot against this sum, written out there from the same adam7_pass_dims and png_row_bytes.
 FDH_PNG_FN uint64_t png_adam7_size(uint32_t width, uint64_t height, uint32_t bits, uint32_t method) {
     uint64_t total = 0;
     for (uint32_t p = 0; p < 7; p++) {
@@ -82,6 +82,43 @@ FDH_PNG_FN uint64_t png_adam7_size(uint32_t width, uint64_t height, uint32_t bit
         total += ph * (1 + png_row_bytes(pw, bits));
     }
     return total;
+}
+
+// ---- mixed batches: the geometry is each image's own, read from its fdh_png_info record ----
+// A record the decode steps can work with: the scan found nothing (or the caller says so), and the IHDR values are
+// ones the specification allows.  Records need not come from the scan, so every kernel asks this itself.
+FDH_PNG_FN bool png_decodable(uint32_t status, uint32_t width, uint32_t height, uint32_t depth, uint32_t colour, uint32_t interlace) {
+    return status == kPngOk && width >= 1 && width <= 0x7FFFFFFFu && height >= 1 && height <= 0x7FFFFFFFu && png_pair_ok(depth, colour) &&
+           interlace <= 1;
+}
+
+// The four buffer sizes of an image -- compressed (idat_bytes), filtered (what the IDAT stream decodes to), packed
+// scanlines, RGBA8 -- and whether a pipeline can take it: kPngSkipped for a record that is not decodable,
+// kPngBadSizes for a filtered size of 2^32 or more (a decoder slot cannot hold it) or, with max_bytes != 0, a
+// largest size above max_bytes; all four sizes are 0 then.  Nothing wraps: with row_bytes below 2^32 every product
+// stays below 2^63 and the seven passes have fewer than 2^32 rows together; with row_bytes of 2^32 or more the
+// filtered size is out of range whatever the height (it exceeds the packed size in both layouts: every picture row
+// has at least one pass row, with a type byte, that starts in it).
+FDH_PNG_FN uint32_t png_plan(uint32_t status, uint32_t width, uint32_t height, uint32_t depth, uint32_t colour, uint32_t interlace,
+                             uint32_t idat_bytes, uint64_t max_bytes, uint64_t& comp, uint64_t& filt, uint64_t& pix, uint64_t& rgba) {
+    comp = filt = pix = rgba = 0;
+    if (!png_decodable(status, width, height, depth, colour, interlace)) return kPngSkipped;
+    const uint32_t bits = png_pixel_bits(depth, colour);
+    const uint64_t rb = png_row_bytes(width, bits);
+    if (rb >> 32) return kPngBadSizes;
+    const uint64_t f = png_adam7_size(width, height, bits, interlace);
+    if (f >> 32) return kPngBadSizes;
+    const uint64_t p = (uint64_t)height * rb, r = (uint64_t)height * width * 4;
+    uint64_t largest = idat_bytes;
+    if (f > largest) largest = f;
+    if (p > largest) largest = p;
+    if (r > largest) largest = r;
+    if (max_bytes != 0 && largest > max_bytes) return kPngBadSizes;
+    comp = idat_bytes, filt = f, pix = p, rgba = r;
+    return kPngOk;
+}
+FDH_PNG_FN uint32_t png_plan(const fdh_png_info& r, uint64_t max_bytes, uint64_t& comp, uint64_t& filt, uint64_t& pix, uint64_t& rgba) {
+    return png_plan(r.status, r.width, r.height, r.bit_depth, r.colour_type, r.interlace, r.idat_bytes, max_bytes, comp, filt, pix, rgba);
 }
 
 // ---- values that follow from the specification ----

@@ -477,6 +477,77 @@ int fdh_png_unfilter_interlaced_batch(uint8_t *filt, const uint64_t *filt_off, u
                                       uint32_t *png_status, uint64_t n, uint32_t width,
                                       uint32_t bit_depth, uint32_t colour_type, void *hip_stream);
 
+/* ---- PNG decode: mixed batches ----------------------------------------------------------------------
+ * The decode steps above take width, bit_depth and colour_type as arguments of the call: one geometry per batch.
+ * The calls of this section take them per image from info[i], so one batch can hold files of any width, height,
+ * depth, colour type and interlace method.  The records may be fdh_png_scan_files_batch's or the caller's own, so
+ * every call checks them itself.  A record is DECODABLE when status == 0, width and height are 1 .. 2^31-1, the
+ * depth / colour pair is one of the fifteen and interlace <= 1; a record that is not gives png_status 3 and
+ * nothing is written for that image.  No new status value: 0, 1, 2, 3, 8, 9, 10, 11 mean what they mean above, and
+ * 7 (another geometry than the call's) does not occur.
+ * All calls enqueue on hip_stream and return: no allocation, no synchronisation, nothing outside a slot written,
+ * nothing outside [off[0], off[n]) read, n == 0 is success, more than 2^31-1 images FDH_ERR_INVALID_ARGUMENT.
+ *   upstream  (every call but the plan) nullable; where upstream[i] != 0 the image is skipped and png_status[i] =
+ *             upstream[i], as with fdh_png_expand_batch.  The exception is fdh_png_unfilter_mixed_batch, whose
+ *             upstream is the zlib decoder's status as in fdh_png_unfilter_interlaced_batch: it gives 3.
+ *
+ * fdh_png_plan_sizes / fdh_png_plan_batch -- what a pipeline has to allocate for an image, on the host for one
+ * record (plain arithmetic, no device) and on the device for n (one record per lane).  The four sizes, sizes[0 .. 3]
+ * or the four arrays of n (each nullable):
+ *   compressed  info.idat_bytes
+ *   filtered    what the IDAT stream decodes to: height * (1 + row_bytes), or fdh_png_adam7_size for interlace 1
+ *   packed      height * row_bytes                       (row_bytes = ceil(width * channels * depth / 8))
+ *   RGBA8       height * width * 4
+ * status (the return value, or png_status[i]): 0 ok; 3 the record is not decodable (or rec is null); 2 the filtered
+ * size is 2^32 or more -- more than a slot of fdh_inflate_batch can hold --, or max_bytes != 0 and the largest of the
+ * four sizes exceeds it.  Where it is not 0 all four sizes are 0: a 40-byte file may declare 2^31-1 by 2^31-1
+ * pixels, and a pipeline that sums the sizes allocates nothing for it.  The arithmetic does not wrap.
+ *
+ * fdh_png_gather_idat_mixed_batch -- fdh_png_gather_idat_batch without the comparison of geometries.
+ * png_status[i]: 0 ok; 3 not decodable, or info does not describe the file; 8 the comp slot is too small; or upstream.
+ * Where it is not 0, comp_len[i] = 0 and nothing is written.
+ *
+ * fdh_png_colour_mixed_batch -- fdh_png_colour_batch with the colour type and depth of info[i].  pal[256 n] is
+ * required; the 256 words of file i are written only if its colour type is 3, the rows of other files are left as
+ * they are.  colour[4 n] is written for every file whose png_status is 0.
+ * png_status[i]: 0 ok; 3 not decodable, or info does not describe the file; 10, 11 as there; or upstream.
+ *
+ * fdh_png_unfilter_mixed_batch -- fdh_png_unfilter_interlaced_batch at image i's own width, depth and colour type,
+ * with method = info[i].interlace.  The pix slot and png_status[i] are byte for byte what that call gives for the
+ * image alone, the rules about padding bits and upstream_len included; `filt` is reconstructed in place as there.
+ * The slots must be exactly the plan's filtered and packed sizes for the record (so the height is info[i].height,
+ * not the slot's), else 2.
+ * png_status[i]: 0 ok; 1 a filter type above 4; 2 a slot or upstream_len[i] does not fit, or the filtered size is
+ * 2^32 or more; 3 not decodable, or upstream[i] != 0.  Where it is 2 or 3 nothing is written.
+ *
+ * fdh_png_expand_mixed_batch -- fdh_png_expand_batch at image i's own geometry: the RGBA slot and png_status[i]
+ * (0, 2, 9) are byte for byte what that call gives for the image alone (the number of rows is the pix slot's, as
+ * there).  pal may be null only if no decodable image has colour type 3: such an image gets status 10 then.
+ * colour: nullable, with the meaning it has there.  png_status[i] otherwise: 3 not decodable; or upstream.
+ *
+ * One wavefront per image and step as in the calls these derive from; FDH_PNG_ADAM7_WAVES and
+ * FDH_PNG_EXPAND_WAVES apply.
+ */
+uint32_t fdh_png_plan_sizes(const fdh_png_info *rec, uint64_t max_bytes, uint64_t sizes[4]);
+int fdh_png_plan_batch(const fdh_png_info *info, uint64_t max_bytes, uint64_t *comp_size,
+                       uint64_t *filt_size, uint64_t *pix_size, uint64_t *rgba_size,
+                       uint32_t *png_status, uint64_t n, void *hip_stream);
+int fdh_png_gather_idat_mixed_batch(const uint8_t *file, const uint64_t *file_off,
+                                    const fdh_png_info *info, const uint32_t *upstream, uint8_t *comp,
+                                    const uint64_t *comp_off, uint32_t *comp_len, uint32_t *png_status,
+                                    uint64_t n, void *hip_stream);
+int fdh_png_colour_mixed_batch(const uint8_t *file, const uint64_t *file_off, const fdh_png_info *info,
+                               const uint32_t *upstream, uint32_t *pal, uint32_t *colour,
+                               uint32_t *png_status, uint64_t n, void *hip_stream);
+int fdh_png_unfilter_mixed_batch(uint8_t *filt, const uint64_t *filt_off, uint8_t *pix,
+                                 const uint64_t *pix_off, const fdh_png_info *info,
+                                 const uint32_t *upstream, const uint32_t *upstream_len,
+                                 uint32_t *png_status, uint64_t n, void *hip_stream);
+int fdh_png_expand_mixed_batch(const uint8_t *pix, const uint64_t *pix_off, uint8_t *rgba,
+                               const uint64_t *rgba_off, const fdh_png_info *info, const uint32_t *pal,
+                               const uint32_t *colour, const uint32_t *upstream, uint32_t *png_status,
+                               uint64_t n, void *hip_stream);
+
 /* ---- PNG encode from RGBA8: analysis, packing, palette files ----------------------------------------
  * The encode side's counterpart of the section "PNG decode to RGBA8": [rows, width, 4] uint8 pictures, R, G, B, A,
  * become packed scanlines of a depth / colour pair (what fdh_png_choose_filters_batch and
