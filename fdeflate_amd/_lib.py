@@ -106,6 +106,20 @@ def lib():
     L.fdh_png_unfilter_mixed_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
     L.fdh_png_expand_mixed_batch.restype = C.c_int
     L.fdh_png_expand_mixed_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
+    L.fdh_png_encode_plan_one.restype = u32
+    L.fdh_png_encode_plan_one.argtypes = [vp, vp, vp, u32, u32, u32, vp]
+    L.fdh_png_encode_plan_batch.restype = C.c_int
+    L.fdh_png_encode_plan_batch.argtypes = [vp, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, vp]
+    L.fdh_png_analyse_mixed_batch.restype = C.c_int
+    L.fdh_png_analyse_mixed_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, u32, vp]
+    L.fdh_png_pack_mixed_batch.restype = C.c_int
+    L.fdh_png_pack_mixed_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
+    L.fdh_png_choose_filters_mixed_batch.restype = C.c_int
+    L.fdh_png_choose_filters_mixed_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, vp]
+    L.fdh_png_filter_deflate_ultrafast_mixed_batch.restype = C.c_int
+    L.fdh_png_filter_deflate_ultrafast_mixed_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
+    L.fdh_png_frame_mixed_batch.restype = C.c_int
+    L.fdh_png_frame_mixed_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, vp]
     L.fdh_init.restype = C.c_int
     L.fdh_init.argtypes = [u64]
     L.fdh_shutdown.restype = C.c_int
@@ -159,6 +173,8 @@ EXPORTED_SYMBOLS = [
     "fdh_png_analyse_batch", "fdh_png_pack_batch", "fdh_png_palette_file_prefix", "fdh_png_frame_palette_batch",
     "fdh_png_plan_sizes", "fdh_png_plan_batch", "fdh_png_gather_idat_mixed_batch", "fdh_png_colour_mixed_batch",
     "fdh_png_unfilter_mixed_batch", "fdh_png_expand_mixed_batch",
+    "fdh_png_encode_plan_one", "fdh_png_encode_plan_batch", "fdh_png_analyse_mixed_batch", "fdh_png_pack_mixed_batch",
+    "fdh_png_choose_filters_mixed_batch", "fdh_png_filter_deflate_ultrafast_mixed_batch", "fdh_png_frame_mixed_batch",
     "fdh_init", "fdh_shutdown", "fdh_multi_device_count", "fdh_multi_uses_rccl", "fdh_inflate_batch_multi",
 ]
 

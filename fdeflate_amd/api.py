@@ -979,6 +979,210 @@ def png_decode_mixed_files_rgba_batch(file, file_off, file_len=None, flags=0, ma
 
 
 # ------------------------------------------------------------------------------------------
+# PNG encode: mixed batches (every picture's size and pair from its own record)
+# ------------------------------------------------------------------------------------------
+
+def png_encode_plan_one(record, count=None, trns_len=None, summary=0, analyse_status=0, allowed=0):
+    """The encode plan of one picture (fdh_png_encode_plan_one: host arithmetic, no device call).  `record`: a mapping
+    with the fields of fdh_png_info that matter here (status, width, height, bit_depth, colour_type, interlace; a field
+    that is missing counts as 0); bit_depth == colour_type == 0 asks for the pair to be chosen.  count / trns_len: the
+    palette's entries and how many of them have A < 255 (None: there is no palette); summary and analyse_status as
+    png_analyse_batch gives them; allowed: bit c set = colour type c may be chosen, 0 = all.
+    -> (status, bit_depth, colour_type, packed, types, prefix, file): status 0 ok, 3 the record is of neither kind,
+    analyse_status where that is neither 0 nor 12, 13 no candidate left, 10 / 11 a palette record without a usable count /
+    with trns_len above it, 2 beyond the encode steps' size limits; the sizes are all 0 unless the status is."""
+    rec = _PngInfoRecord(**{k: int(record.get(k, 0)) for k, _ in _PngInfoRecord._fields_})
+    have = count is not None and trns_len is not None
+    c, t = C.c_uint32(int(count) if have else 0), C.c_uint32(int(trns_len) if have else 0)
+    sizes = (C.c_uint64 * 4)()
+    st = _lib.lib().fdh_png_encode_plan_one(C.byref(rec), C.byref(c) if have else None, C.byref(t) if have else None, int(summary),
+                                            int(analyse_status), int(allowed), sizes)
+    return (int(st), int(rec.bit_depth), int(rec.colour_type)) + tuple(int(v) for v in sizes)
+
+
+def png_encode_records(width, height, pairs=None):
+    """fdh_png_info records for n pictures to encode: int32 [n, 8] on the device of `width`.  width, height: int tensors
+    [n]; pairs: None (dimension records: the plan chooses), a (bit_depth, colour_type) tuple for all, or an int tensor
+    [n, 2] of them."""
+    import torch
+    n = width.numel()
+    info = torch.zeros((n, PNG_INFO_WORDS), dtype=torch.int32, device=width.device)
+    info[:, 1] = width.to(torch.int32)
+    info[:, 2] = height.to(torch.int32)
+    if pairs is not None:
+        if not torch.is_tensor(pairs):
+            pairs = torch.tensor([[int(pairs[0]), int(pairs[1])]], dtype=torch.int32, device=width.device).expand(n, 2)
+        info[:, 3] = (pairs[:, 0].to(torch.int32) & 0xFF) | ((pairs[:, 1].to(torch.int32) & 0xFF) << 8)
+    return info
+
+
+def png_analyse_mixed_batch(rgba, rgba_off, info, max_colours=256, with_pal=True, upstream=None, pal=None, colour=None, trns_len=None,
+                            summary=None, png_status=None):
+    """png_analyse_batch at every picture's own width (fdh_png_analyse_mixed_batch): the slot of image i must be exactly
+    height_i * width_i * 4 bytes.  info: dimension records or encodable ones (png_encode_records).
+    -> (pal, colour, trns_len, summary, png_status) as png_analyse_batch; png_status also 3 (neither kind of record) or
+    upstream[i] where that is not 0."""
+    import torch
+    n = rgba_off.numel() - 1
+    dev = rgba.device
+    if pal is None and with_pal:
+        pal = torch.empty((n, 256), dtype=torch.int32, device=dev)
+    if colour is None:
+        colour = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    if trns_len is None:
+        trns_len = torch.empty(n, dtype=torch.int32, device=dev)
+    if summary is None:
+        summary = torch.empty(n, dtype=torch.int32, device=dev)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=dev)
+    with _OnDevice(rgba, rgba_off, info, upstream, pal, colour, trns_len, summary, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_analyse_mixed_batch(_ptr(rgba), _ptr(rgba_off), _ptr(info), _ptr(upstream), _ptr(pal), _ptr(colour),
+                                                         _ptr(trns_len), _ptr(summary), _ptr(png_status), n, max_colours,
+                                                         C.c_void_p(stream)))
+    return pal, colour, trns_len, summary, png_status
+
+
+def png_encode_plan_batch(info, colour=None, trns_len=None, summary=None, analyse_status=None, allowed=0, pix_size=True,
+                          types_size=True, prefix=True, file_size=True, png_status=None):
+    """png_encode_plan_one for n records on the device (fdh_png_encode_plan_batch); `info` is changed in place: a dimension
+    record gets its pair.  colour / trns_len / summary / analyse_status as png_analyse_mixed_batch writes them.  Each of the
+    four outputs is True (allocated), a tensor (int64 [n]) or None / False (not wanted).
+    -> (pix_size, types_size, prefix, file_size, png_status), None for an output that was not wanted."""
+    import torch
+    n = info.numel() // PNG_INFO_WORDS
+    outs = []
+    for want in (pix_size, types_size, prefix, file_size):
+        if want is True:
+            want = torch.empty(n, dtype=torch.int64, device=info.device)
+        elif want is False:
+            want = None
+        outs.append(want)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=info.device)
+    with _OnDevice(info, colour, trns_len, summary, analyse_status, png_status, *outs) as stream:
+        _lib.check(_lib.lib().fdh_png_encode_plan_batch(_ptr(info), _ptr(colour), _ptr(trns_len), _ptr(summary), _ptr(analyse_status),
+                                                       int(allowed), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]),
+                                                       _ptr(png_status), n, C.c_void_p(stream)))
+    return outs[0], outs[1], outs[2], outs[3], png_status
+
+
+def png_pack_mixed_batch(rgba, rgba_off, pix, pix_off, info, pal=None, colour=None, upstream=None, png_status=None):
+    """png_pack_batch at every picture's own pair and width (fdh_png_pack_mixed_batch): the slots must be exactly the plan's
+    sizes.  An image of colour type 3 without `pal` is status 10.
+    -> png_status: 0 ok, 2 the slots do not fit, 3 not encodable, 13 not representable, or upstream[i]."""
+    import torch
+    n = rgba_off.numel() - 1
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=rgba.device)
+    with _OnDevice(rgba, rgba_off, pix, pix_off, info, pal, colour, upstream, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_pack_mixed_batch(_ptr(rgba), _ptr(rgba_off), _ptr(pix), _ptr(pix_off), _ptr(info), _ptr(pal),
+                                                      _ptr(colour), _ptr(upstream), _ptr(png_status), n, C.c_void_p(stream)))
+    return png_status
+
+
+def png_choose_filters_mixed_batch(pix, pix_off, types, types_off, info, upstream=None, png_status=None):
+    """png_choose_filters_batch at every picture's own row_bytes and bpp (fdh_png_choose_filters_mixed_batch).
+    -> png_status: 0 ok, 2 the slots are not the plan's, 3 not encodable, or upstream[i]."""
+    import torch
+    n = pix_off.numel() - 1
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
+    with _OnDevice(pix, pix_off, types, types_off, info, upstream, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_choose_filters_mixed_batch(_ptr(pix), _ptr(pix_off), _ptr(types), _ptr(types_off), _ptr(info),
+                                                                _ptr(upstream), _ptr(png_status), n, C.c_void_p(stream)))
+    return png_status
+
+
+def png_filter_deflate_ultrafast_mixed_batch(pix, pix_off, types, types_off, out, out_off, info, upstream=None, out_len=None,
+                                             png_status=None):
+    """png_filter_deflate_ultrafast_batch at every picture's own row_bytes and bpp
+    (fdh_png_filter_deflate_ultrafast_mixed_batch) -> (out_len, png_status): 0 ok, 1 a filter type above 4, 2 the slots are
+    not the plan's, 3 not encodable, or upstream[i]; out_len 0xFFFFFFFF (-1) where the out slot is too small."""
+    import torch
+    n = pix_off.numel() - 1
+    if out_len is None:
+        out_len = torch.empty(n, dtype=torch.int32, device=pix.device)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
+    with _OnDevice(pix, pix_off, types, types_off, out, out_off, out_len, info, upstream, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_filter_deflate_ultrafast_mixed_batch(_ptr(pix), _ptr(pix_off), _ptr(types), _ptr(types_off),
+                                                                          _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(info),
+                                                                          _ptr(upstream), _ptr(png_status), n, C.c_void_p(stream)))
+    return out_len, png_status
+
+
+def png_frame_mixed_batch(file, file_off, idat_len, info, pal=None, colour=None, trns_len=None, file_len=None, png_status=None):
+    """png_frame_batch / png_frame_palette_batch with every file's own IHDR and, for colour type 3, a PLTE of exactly
+    colour[i, 0] entries and a tRNS of exactly trns_len[i] bytes (fdh_png_frame_mixed_batch); the zlib streams lie the plan's
+    prefix into their file slots.  -> (file_len, png_status): 0 ok, 3 not encodable, 2, 10, 11 as the framing calls (nothing
+    written, file_len 0)."""
+    import torch
+    n = file_off.numel() - 1
+    if file_len is None:
+        file_len = torch.empty(n, dtype=torch.int32, device=file.device)
+    if png_status is None:
+        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
+    with _OnDevice(file, file_off, idat_len, info, pal, colour, trns_len, file_len, png_status) as stream:
+        _lib.check(_lib.lib().fdh_png_frame_mixed_batch(_ptr(file), _ptr(file_off), _ptr(idat_len), _ptr(info), _ptr(pal), _ptr(colour),
+                                                       _ptr(trns_len), _ptr(file_len), _ptr(png_status), n, C.c_void_p(stream)))
+    return file_len, png_status
+
+
+def png_encode_mixed_rgba_files_batch(rgba, rgba_off, width, height, allowed=0, pairs=None, file=None, file_off=None):
+    """RGBA8 pictures of any size in, PNG files out, each with the smallest of the depth / colour pairs that holds it (or with
+    the pair `pairs` names, see png_encode_records), on torch's current stream: png_analyse_mixed_batch,
+    png_encode_plan_batch, the buffers sized on the device with ONE read-back of 24 bytes (the three totals),
+    png_pack_mixed_batch, png_choose_filters_mixed_batch, png_filter_deflate_ultrafast_mixed_batch, png_frame_mixed_batch.
+    Picture i is rgba[rgba_off[i] .. rgba_off[i+1]), exactly height[i] * width[i] * 4 bytes; width, height: int tensors [n]
+    on the device.  allowed: the colour types the plan may choose (bit c = colour type c, 0 = all).  file / file_off: the
+    caller's file slots (both or neither); by default they are the plan's file sizes, which always suffice.
+    -> (file, file_off, file_len, png_status, info): file i is file[file_off[i] : file_off[i] + file_len[i]]; info the
+    records with the pairs that were written; png_status[i] the first that is not 0 of the plan (2, 3, 10, 11, 13, and 12
+    for a forced palette pair with more than 256 colours), packing (2, 10, 13), filter selection, the encoder and the
+    framing (2, 10, 11).  An image that fails gets file_len[i] = 0.
+    The encoder takes ONE offsets array, as in png_encode_rgba_files_batch: enc_off[i] = file_off[i] + prefix_i, so the
+    encoder's slot for image i reaches prefix_(i+1) bytes into slot i + 1 -- the bytes that image i + 1's own prefix is
+    written to afterwards -- and the last one ends 16 bytes in front of its slot's end.  A caller's slot that is shorter
+    than its prefix + 16 is status 2 before anything is written to it."""
+    import torch
+    n = rgba_off.numel() - 1
+    dev = rgba.device
+    if (file is None) != (file_off is None):
+        raise ValueError("file and file_off go together")
+    info = png_encode_records(width, height, pairs)
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=dev)
+        return (file if file is not None else torch.empty(0, dtype=torch.uint8, device=dev),
+                file_off if file_off is not None else torch.zeros(1, dtype=torch.int64, device=dev), e, e.clone(), info)
+    pal, colour, trns_len, summary, analysed = png_analyse_mixed_batch(rgba, rgba_off, info)
+    pix_size, types_size, prefix, file_size, planned = png_encode_plan_batch(info, colour, trns_len, summary, analysed, allowed)
+    if pairs is not None:   # a forced palette pair with too many colours: the analysis' finding, not the plan's "no count"
+        overflow = (analysed == PNG_TOO_MANY_COLOURS) & (((info[:, 3] >> 8) & 0xFF) == 3) & (planned == PNG_BAD_PLTE)
+        planned = torch.where(overflow, analysed, planned)
+    offs = torch.zeros((3, n + 1), dtype=torch.int64, device=dev)
+    torch.cumsum(torch.stack((pix_size, types_size, file_size)), 1, out=offs[:, 1:])
+    total_pix, total_types, total_file = _read_back(offs[:, n])                    # the one read-back: 24 bytes
+    pix = torch.empty(max(1, total_pix), dtype=torch.uint8, device=dev)
+    types = torch.empty(max(1, total_types), dtype=torch.uint8, device=dev)
+    if file is None:
+        file = torch.empty(max(1, total_file), dtype=torch.uint8, device=dev)
+        file_off = offs[2]
+    else:
+        slot = file_off[1:] - file_off[:-1]
+        planned = torch.where((planned == 0) & (slot < prefix + PNG_FILE_SUFFIX), torch.full_like(planned, PNG_BAD_SIZES), planned)
+        prefix = torch.minimum(prefix, slot)
+    status = png_pack_mixed_batch(rgba, rgba_off, pix, offs[0], info, pal=pal, colour=colour, upstream=planned)
+    status = png_choose_filters_mixed_batch(pix, offs[0], types, offs[1], info, upstream=status)
+    enc_off = file_off.clone()
+    enc_off[:n] += prefix
+    enc_off[n] = torch.maximum(file_off[n] - PNG_FILE_SUFFIX, enc_off[n - 1])
+    idat_len, status = png_filter_deflate_ultrafast_mixed_batch(pix, offs[0], types, offs[1], file, enc_off, info, upstream=status)
+    idat_len = torch.where(status != 0, torch.zeros_like(idat_len), idat_len)     # (the framing then writes nothing)
+    file_len, framed = png_frame_mixed_batch(file, file_off, idat_len, info, pal, colour, trns_len)
+    return file, file_off, file_len, torch.where(status != 0, status, framed), info
+
+
+# ------------------------------------------------------------------------------------------
 # PNG encode from RGBA8: analysis, packing, palette files
 # ------------------------------------------------------------------------------------------
 

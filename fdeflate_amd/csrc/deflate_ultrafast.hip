@@ -21,6 +21,7 @@
 #include "bit_ring.h"
 #include "launch.h"
 #include "png_common.h"
+#include "png_record.h"
 
 namespace fdh {
 
@@ -136,6 +137,9 @@ struct DeflateBatchArgs {
     const uint64_t* types_off;
     uint32_t* png_status;       // kPngOk, kPngBadFilterType, kPngBadSizes
     uint32_t row_bytes, bpp;
+    // mixed PNG source (fdh_png_filter_deflate_ultrafast_mixed_batch): row_bytes and bpp are each image's own, from info[i]
+    const fdh_png_info* info;
+    const uint32_t* upstream;   // nullable
 };
 
 // ---- PNG filtering as the encoder's source (PNG specification 9.2: filtering uses the RAW neighbours,
@@ -290,12 +294,18 @@ struct PngSource {
     }
 };
 
-template <bool PNG>
+// SRC: where the encoder's input comes from -- kSrcBytes the buffer itself, kSrcPng PNG rows of the call's row_bytes and
+// bpp filtered on the way in, kSrcPngMixed the same with every image's row size from its fdh_png_info record (the record
+// is read once per wavefront into scalar registers, where the call's arguments are for kSrcPng: the tile loop is the same).
+constexpr int kSrcBytes = 0, kSrcPng = 1, kSrcPngMixed = 2;
+
+template <int SRC>
 // Wavefronts per SIMD: five for the plain encoder (96 VGPRs, 12 B of scratch outside the tile loop, 4 KiB rings: 20 wavefronts
 // per CU, 2.91 -> 2.71 ms -- the vector ALUs were 86 % busy at four and still had stalls to fill), four for the one that
 // filters PNG rows on the way in (114 VGPRs: at 96 it spills 56 B into the loop, 6.45 -> 10.0 ms).
-__global__ __launch_bounds__(kEncWaves * kWave) __attribute__((amdgpu_waves_per_eu(PNG ? 4 : 5, PNG ? 4 : 5)))
+__global__ __launch_bounds__(kEncWaves * kWave) __attribute__((amdgpu_waves_per_eu(SRC != kSrcBytes ? 4 : 5, SRC != kSrcBytes ? 4 : 5)))
 void deflate_ultrafast_kernel_t(DeflateBatchArgs a) {
+    constexpr bool PNG = SRC != kSrcBytes;
     __shared__ EncLds lds;
     const int lane = threadIdx.x & (kWave - 1);
     const int wid = threadIdx.x / kWave;
@@ -319,14 +329,28 @@ void deflate_ultrafast_kernel_t(DeflateBatchArgs a) {
     uint64_t len = a.in_off[sid + 1] - a.in_off[sid];
     PngSource png{nullptr, nullptr, 0, 0, 0, 0};
     if (PNG) {  // the encoder's input: rows x (1 + row_bytes) filtered bytes
-        const uint64_t plen = len, nrows = plen / a.row_bytes;
+        const uint64_t plen = len;
         const uint64_t tlen = a.types_off[sid + 1] - a.types_off[sid];
-        uint32_t st = (nrows * a.row_bytes != plen || tlen != nrows || nrows >= (1ull << 31) / (a.row_bytes + 1ull)) ? kPngBadSizes : kPngOk;
+        uint32_t row_bytes = a.row_bytes, bpp = a.bpp, st;
+        uint64_t nrows;
+        if constexpr (SRC == kSrcPngMixed) {  // the slots must be exactly the record's (png_encode_sizes has the limits)
+            const PngInfo r = mixed_record(a.info, sid);
+            uint64_t rb64, pix_size;
+            st = mixed_encode_image(r, a.upstream, sid, rb64, pix_size);
+            if (st == kPngOk && (plen != pix_size || tlen != r.height)) st = kPngBadSizes;
+            st = uni(st);  // (the slots' sizes come through vector loads: said so, the row size stays in scalar registers)
+            row_bytes = st ? 1u : (uint32_t)rb64;
+            bpp = st ? 1u : png_bpp(png_pixel_bits(r.bit_depth, r.colour_type));
+            nrows = r.height;
+        } else {
+            nrows = plen / row_bytes;
+            st = (nrows * row_bytes != plen || tlen != nrows || nrows >= (1ull << 31) / (row_bytes + 1ull)) ? kPngBadSizes : kPngOk;
+        }
         png.pix = in;
         png.types = a.types + a.types_off[sid];
-        png.rb = a.row_bytes;
-        png.bpp = a.bpp;
-        png.magic = (uint32_t)(0x100000000ull / ((uint64_t)a.row_bytes + 1));
+        png.rb = row_bytes;
+        png.bpp = bpp;
+        png.magic = (uint32_t)(0x100000000ull / ((uint64_t)row_bytes + 1));
         png.rows = st ? 0u : (uint32_t)nrows;
         bool bad_type = false;
         for (uint32_t r = (uint32_t)lane; r < png.rows; r += kWave) bad_type = bad_type || png.types[r] > 4;
@@ -336,7 +360,7 @@ void deflate_ultrafast_kernel_t(DeflateBatchArgs a) {
             if (lane == 0) a.out_len[sid] = 0;
             return;
         }
-        len = nrows * (a.row_bytes + 1ull);
+        len = nrows * (row_bytes + 1ull);
     }
     uint8_t* out = a.out + a.out_off[sid];
     const uint64_t cap = a.out_off[sid + 1] - a.out_off[sid];
@@ -578,7 +602,7 @@ extern "C" int fdh_launch_deflate_ultrafast(const uint8_t* in, const uint64_t* i
     fdh::DeflateBatchArgs a{in, in_off, out, out_off, out_len, n, nullptr, nullptr, nullptr, 0, 0};
     if (n == 0) return 0;
     unsigned blocks = (unsigned)((n + fdh::kEncWaves - 1) / fdh::kEncWaves);
-    hipLaunchKernelGGL(fdh::deflate_ultrafast_kernel_t<false>, dim3(blocks), dim3(fdh::kEncWaves * fdh::kWave), 0, stream, a);
+    hipLaunchKernelGGL(fdh::deflate_ultrafast_kernel_t<fdh::kSrcBytes>, dim3(blocks), dim3(fdh::kEncWaves * fdh::kWave), 0, stream, a);
     return (int)hipGetLastError();
 }
 
@@ -591,6 +615,18 @@ extern "C" int fdh_launch_png_filter_deflate_ultrafast(const uint8_t* pix, const
     fdh::DeflateBatchArgs a{pix, pix_off, out, out_off, out_len, n, types, types_off, png_status, row_bytes, bpp};
     if (n == 0) return 0;
     unsigned blocks = (unsigned)((n + fdh::kEncWaves - 1) / fdh::kEncWaves);
-    hipLaunchKernelGGL(fdh::deflate_ultrafast_kernel_t<true>, dim3(blocks), dim3(fdh::kEncWaves * fdh::kWave), 0, stream, a);
+    hipLaunchKernelGGL(fdh::deflate_ultrafast_kernel_t<fdh::kSrcPng>, dim3(blocks), dim3(fdh::kEncWaves * fdh::kWave), 0, stream, a);
+    return (int)hipGetLastError();
+}
+
+// The same with row_bytes and bpp of every image from its record (fdh_png_filter_deflate_ultrafast_mixed_batch).
+extern "C" int fdh_launch_png_filter_deflate_ultrafast_mixed(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types,
+                                                             const uint64_t* types_off, uint8_t* out, const uint64_t* out_off,
+                                                             uint32_t* out_len, const fdh_png_info* info, const uint32_t* upstream,
+                                                             uint32_t* png_status, uint64_t n, hipStream_t stream) {
+    fdh::DeflateBatchArgs a{pix, pix_off, out, out_off, out_len, n, types, types_off, png_status, 0, 0, info, upstream};
+    if (n == 0) return 0;
+    unsigned blocks = (unsigned)((n + fdh::kEncWaves - 1) / fdh::kEncWaves);
+    hipLaunchKernelGGL(fdh::deflate_ultrafast_kernel_t<fdh::kSrcPngMixed>, dim3(blocks), dim3(fdh::kEncWaves * fdh::kWave), 0, stream, a);
     return (int)hipGetLastError();
 }

@@ -105,7 +105,7 @@ int fdh_device_count(void) {
     return n;
 }
 
-uint64_t fdh_ultrafast_bound(uint64_t len) { return 53 + (5 + 12 * len + 12 + 7) / 8 + 4; }
+uint64_t fdh_ultrafast_bound(uint64_t len) { return fdh::png_ultrafast_bound(len); }
 
 uint64_t fdh_stored_size(uint64_t len) {
     const uint64_t nb = len / 65535, rem = len - nb * 65535;
@@ -398,6 +398,79 @@ int fdh_png_frame_palette_batch(uint8_t* file, const uint64_t* file_off, const u
     if (int rc = batch_ok({file, file_off, idat_len, height, pal, colour, trns_len, file_len, png_status}, "null pointer", n, "files")) return rc;
     return launched("PNG palette framing kernel launch", fdh_launch_png_frame_palette(file, file_off, idat_len, height, pal, colour, trns_len,
                     file_len, png_status, n, width, bit_depth, plte_entries, trns_entries, stream_of(hip_stream)));
+}
+
+// ---- PNG encode: mixed batches (png_encode_mixed.hip; the fused encoder in deflate_ultrafast.hip, the framing in png_file.hip) ----
+uint32_t fdh_png_encode_plan_one(fdh_png_info* rec, const uint32_t* colour_count, const uint32_t* trns_len, uint32_t summary,
+                                 uint32_t analyse_status, uint32_t allowed, uint64_t sizes[4]) {
+    uint64_t s[4] = {0, 0, 0, 0};
+    uint32_t st = FDH_PNG_STATUS_SKIPPED;
+    if (rec) {
+        const bool dimension = fdh::png_dimension_record(rec->status, rec->width, rec->height, rec->bit_depth, rec->colour_type, rec->interlace);
+        const bool have_colour = colour_count && trns_len;
+        uint32_t depth = rec->bit_depth, colour = rec->colour_type;
+        st = fdh::png_encode_plan(rec->status, rec->width, rec->height, depth, colour, rec->interlace, have_colour, have_colour ? *colour_count : 0u,
+                                  have_colour ? *trns_len : 0u, summary, analyse_status, allowed, s[0], s[1], s[2], s[3]);
+        if (st == FDH_PNG_STATUS_OK && dimension) rec->bit_depth = (uint8_t)depth, rec->colour_type = (uint8_t)colour;
+    }
+    if (sizes) std::copy(s, s + 4, sizes);
+    return st;
+}
+
+int fdh_png_encode_plan_batch(fdh_png_info* info, const uint32_t* colour, const uint32_t* trns_len, const uint32_t* summary,
+                              const uint32_t* analyse_status, uint32_t allowed, uint64_t* pix_size, uint64_t* types_size, uint64_t* prefix,
+                              uint64_t* file_size, uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (allowed & ~0x5Du) return fail(FDH_ERR_INVALID_ARGUMENT, "allowed may hold the bits of colour types 0, 2, 3, 4 and 6 only");
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({info}, "null pointer", n, "records")) return rc;
+    return launched("PNG encode plan kernel launch", fdh_launch_png_encode_plan(info, colour, trns_len, summary, analyse_status, allowed,
+                    pix_size, types_size, prefix, file_size, png_status, n, stream_of(hip_stream)));
+}
+
+int fdh_png_analyse_mixed_batch(const uint8_t* rgba, const uint64_t* rgba_off, const fdh_png_info* info, const uint32_t* upstream,
+                                uint32_t* pal, uint32_t* colour, uint32_t* trns_len, uint32_t* summary, uint32_t* png_status, uint64_t n,
+                                uint32_t max_colours, void* hip_stream) {
+    if (max_colours == 0 || max_colours > 256) return fail(FDH_ERR_INVALID_ARGUMENT, "max_colours must be 1 .. 256");
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({rgba, rgba_off, info, colour, trns_len, summary, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed RGBA analysis kernel launch", fdh_launch_png_analyse_mixed(rgba, rgba_off, info, upstream, pal, colour, trns_len,
+                    summary, png_status, n, max_colours, stream_of(hip_stream)));
+}
+
+int fdh_png_pack_mixed_batch(const uint8_t* rgba, const uint64_t* rgba_off, uint8_t* pix, const uint64_t* pix_off, const fdh_png_info* info,
+                             const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* png_status, uint64_t n,
+                             void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({rgba, rgba_off, pix, pix_off, info, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed RGBA packing kernel launch", fdh_launch_png_pack_mixed(rgba, rgba_off, pix, pix_off, info, pal, colour, upstream,
+                    png_status, n, stream_of(hip_stream)));
+}
+
+int fdh_png_choose_filters_mixed_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off,
+                                       const fdh_png_info* info, const uint32_t* upstream, uint32_t* png_status, uint64_t n,
+                                       void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({pix, pix_off, types, types_off, info, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed filter-selection kernel launch", fdh_launch_png_choose_mixed(pix, pix_off, types, types_off, info, upstream,
+                    png_status, n, stream_of(hip_stream)));
+}
+
+int fdh_png_filter_deflate_ultrafast_mixed_batch(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
+                                                 uint8_t* out, const uint64_t* out_off, uint32_t* out_len, const fdh_png_info* info,
+                                                 const uint32_t* upstream, uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({pix, pix_off, types, types_off, out, out_off, out_len, info, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed filter + deflate kernel launch", fdh_launch_png_filter_deflate_ultrafast_mixed(pix, pix_off, types, types_off, out,
+                    out_off, out_len, info, upstream, png_status, n, stream_of(hip_stream)));
+}
+
+int fdh_png_frame_mixed_batch(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const fdh_png_info* info, const uint32_t* pal,
+                              const uint32_t* colour, const uint32_t* trns_len, uint32_t* file_len, uint32_t* png_status, uint64_t n,
+                              void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({file, file_off, idat_len, info, file_len, png_status}, "null pointer", n, "files")) return rc;
+    return launched("mixed PNG framing kernel launch", fdh_launch_png_frame_mixed(file, file_off, idat_len, info, pal, colour, trns_len,
+                    file_len, png_status, n, stream_of(hip_stream)));
 }
 
 // ---- general encoder (levels 1-3 / RLE): per-device workspace, grown on demand, never shrunk ----

@@ -32,6 +32,9 @@ int fdh_launch_deflate_ultrafast(const uint8_t* in, const uint64_t* in_off, uint
 int fdh_launch_png_filter_deflate_ultrafast(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
                                             uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint32_t* png_status, uint64_t n,
                                             uint32_t row_bytes, uint32_t bpp, hipStream_t stream);
+int fdh_launch_png_filter_deflate_ultrafast_mixed(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
+                                                  uint8_t* out, const uint64_t* out_off, uint32_t* out_len, const fdh_png_info* info,
+                                                  const uint32_t* upstream, uint32_t* png_status, uint64_t n, hipStream_t stream);
 // deflate_general.hip
 int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
                                uint64_t n, int kind, void* hash, void* matches, void* blocks, uint32_t* nblocks, unsigned waves,
@@ -66,6 +69,9 @@ int fdh_launch_png_frame_palette(uint8_t* file, const uint64_t* file_off, const 
                                  const uint32_t* pal, const uint32_t* colour, const uint32_t* trns_len, uint32_t* file_len,
                                  uint32_t* png_status, uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t plte_entries,
                                  uint32_t trns_entries, hipStream_t stream);
+int fdh_launch_png_frame_mixed(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const fdh_png_info* info, const uint32_t* pal,
+                               const uint32_t* colour, const uint32_t* trns_len, uint32_t* file_len, uint32_t* png_status, uint64_t n,
+                               hipStream_t stream);
 // png_expand.hip
 int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off, const uint32_t* pal,
                           const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n, uint32_t width,
@@ -93,6 +99,18 @@ int fdh_launch_png_unfilter_mixed(uint8_t* filt, const uint64_t* filt_off, uint8
 int fdh_launch_png_expand_mixed(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
                                 const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
                                 uint32_t* status, uint64_t n, hipStream_t stream);
+// png_encode_mixed.hip
+int fdh_launch_png_encode_plan(fdh_png_info* info, const uint32_t* colour, const uint32_t* trns_len, const uint32_t* summary,
+                               const uint32_t* analyse_status, uint32_t allowed, uint64_t* pix_size, uint64_t* types_size, uint64_t* prefix,
+                               uint64_t* file_size, uint32_t* png_status, uint64_t n, hipStream_t stream);
+int fdh_launch_png_analyse_mixed(const uint8_t* rgba, const uint64_t* rgba_off, const fdh_png_info* info, const uint32_t* upstream,
+                                 uint32_t* pal, uint32_t* colour, uint32_t* trns_len, uint32_t* summary, uint32_t* status, uint64_t n,
+                                 uint32_t max_colours, hipStream_t stream);
+int fdh_launch_png_pack_mixed(const uint8_t* rgba, const uint64_t* rgba_off, uint8_t* pix, const uint64_t* pix_off, const fdh_png_info* info,
+                              const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n,
+                              hipStream_t stream);
+int fdh_launch_png_choose_mixed(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off,
+                                const fdh_png_info* info, const uint32_t* upstream, uint32_t* status, uint64_t n, hipStream_t stream);
 }
 
 namespace fdh {

@@ -4,15 +4,13 @@
 #pragma once
 #include "device_common.h"
 #include "png_common.h"
+#include "png_record.h"
 
 namespace fdh {
 
 __device__ __forceinline__ uint32_t get_be32(const uint8_t* p) {
     return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
 }
-
-using PngInfo = fdh_png_info;
-static_assert(sizeof(PngInfo) == 32, "fdh_png_info is 32 bytes");
 
 constexpr uint32_t kIHDR = 0x49484452u, kPLTE = 0x504C5445u, kIDAT = 0x49444154u, kIEND = 0x49454E44u;
 

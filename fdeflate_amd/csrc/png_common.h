@@ -121,7 +121,95 @@ FDH_PNG_FN uint32_t png_plan(const fdh_png_info& r, uint64_t max_bytes, uint64_t
     return png_plan(r.status, r.width, r.height, r.bit_depth, r.colour_type, r.interlace, r.idat_bytes, max_bytes, comp, filt, pix, rgba);
 }
 
+// ---- encode: mixed batches (include/fdeflate_hip.h, "PNG encode: mixed batches") ----
+// A record the encode steps can work with: as png_decodable, without interlacing (interlaced writing does not exist).
+FDH_PNG_FN bool png_encodable(uint32_t status, uint32_t width, uint32_t height, uint32_t depth, uint32_t colour, uint32_t interlace) {
+    return interlace == 0 && png_decodable(status, width, height, depth, colour, interlace);
+}
+// A record that says only how large the picture is: depth 0 and colour type 0 mean "choose for me" (png_encode_plan does).
+FDH_PNG_FN bool png_dimension_record(uint32_t status, uint32_t width, uint32_t height, uint32_t depth, uint32_t colour, uint32_t interlace) {
+    return status == kPngOk && width >= 1 && width <= 0x7FFFFFFFu && height >= 1 && height <= 0x7FFFFFFFu && depth == 0 && colour == 0 &&
+           interlace == 0;
+}
+
+// fdh_ultrafast_bound: the largest stream the ultra-fast encoder makes of `len` bytes
+FDH_PNG_FN uint64_t png_ultrafast_bound(uint64_t len) { return 53 + (5 + 12 * len + 12 + 7) / 8 + 4; }
+
+// The bytes of a file in front of its zlib stream: signature, IHDR and the IDAT's head (41), and for colour type 3 a PLTE
+// of exactly `count` entries and, where there are alphas, a tRNS of exactly `trns_len` bytes.  The plan, the framing, the
+// IDAT's CRC pass and the finishing kernel all ask here.
+constexpr uint32_t kPngFilePrefix = FDH_PNG_FILE_PREFIX, kPngFileSuffix = FDH_PNG_FILE_SUFFIX;
+FDH_PNG_FN uint32_t png_encode_prefix(uint32_t colour, uint32_t count, uint32_t trns_len) {
+    return colour == 3 ? kPngFilePrefix + 12 + 3 * count + (trns_len ? 12 + trns_len : 0) : kPngFilePrefix;
+}
+
+// Row bytes and packed size of an encodable geometry, and whether the encode steps can take it: kPngBadSizes for
+// row_bytes of 2^25 or more (a row's filter cost is summed in 32 bits) or a filtered size height * (row_bytes + 1) of
+// 2^31 or more (the fused encoder's limit); both sizes are 0 then.  Nothing wraps: row_bytes is below 2^34, and it is
+// below 2^25 before it is multiplied.
+FDH_PNG_FN uint32_t png_encode_sizes(uint32_t width, uint32_t height, uint32_t depth, uint32_t colour, uint64_t& row_bytes, uint64_t& pix) {
+    row_bytes = pix = 0;
+    const uint64_t rb = png_row_bytes(width, png_pixel_bits(depth, colour));
+    if (rb >= (1ull << 25) || (uint64_t)height * (rb + 1) >= (1ull << 31)) return kPngBadSizes;
+    row_bytes = rb, pix = (uint64_t)height * rb;
+    return kPngOk;
+}
+
+// The encode plan of one image: the pair for a dimension record (written to depth / colour where the status is kPngOk),
+// and the four sizes -- packed scanlines, filter types, prefix, file slot -- of the pair.  have_colour: count and
+// trns_len are known (the palette's entries, and how many of them have A < 255); summary and analyse_status are
+// fdh_png_analyse_batch's; allowed: bit c set = colour type c may be chosen, 0 = all five.
+//   candidates   grey (0, d): summary bits 0 and 1, d the summary's depth; palette (3, p): analyse_status 0, count in
+//                1 .. 256, trns_len <= count, p the smallest of 1, 2, 4, 8 with 2^p >= count; grey-alpha (4, 8): bit 1;
+//                RGB (2, 8): bit 0; RGBA (6, 8) always
+//   cost         height * row_bytes, for the palette + 12 + 3 count + (trns_len ? 12 + trns_len : 0): the smallest wins,
+//                the lower colour type on equal cost (below 2^64: 32 bits per pixel at the most)
+// status: kPngSkipped the record is of neither kind; analyse_status where it is neither 0 nor kPngTooManyColours;
+// kPngNotRepresentable no candidate is left; kPngBadPlte / kPngBadTrns an encodable record of colour type 3 without
+// count (or with one outside 1 .. 2^depth) / with trns_len above count; kPngBadSizes png_encode_sizes refuses the pair.
+// All four sizes are 0 unless the status is kPngOk.
+FDH_PNG_FN uint32_t png_encode_plan(uint32_t status, uint32_t width, uint32_t height, uint32_t& depth, uint32_t& colour, uint32_t interlace,
+                                    bool have_colour, uint32_t count, uint32_t trns_len, uint32_t summary, uint32_t analyse_status,
+                                    uint32_t allowed, uint64_t& pix, uint64_t& types, uint64_t& prefix, uint64_t& file) {
+    pix = types = prefix = file = 0;
+    const bool dimension = png_dimension_record(status, width, height, depth, colour, interlace);
+    if (!dimension && !png_encodable(status, width, height, depth, colour, interlace)) return kPngSkipped;
+    if (analyse_status != kPngOk && analyse_status != kPngTooManyColours) return analyse_status;
+    uint32_t d = depth, c = colour;
+    if (dimension) {
+        if (allowed == 0) allowed = 0x5Du;  // colour types 0, 2, 3, 4, 6
+        const bool opaque = (summary & 1u) != 0, grey = (summary & 2u) != 0;
+        const uint32_t sd = (summary >> 8) & 0xFFu;
+        const bool palette = analyse_status == kPngOk && have_colour && count >= 1 && count <= 256 && trns_len <= count;
+        const uint32_t pd = count <= 2 ? 1u : count <= 4 ? 2u : count <= 16 ? 4u : 8u;
+        const uint32_t cand_colour[5] = {0, 2, 3, 4, 6}, cand_depth[5] = {sd, 8, pd, 8, 8};
+        const bool cand_ok[5] = {opaque && grey && (sd == 1 || sd == 2 || sd == 4 || sd == 8), opaque, palette, grey, true};
+        bool found = false;
+        uint64_t least = 0;
+        for (int k = 0; k < 5; k++) {
+            if (!cand_ok[k] || !((allowed >> cand_colour[k]) & 1u)) continue;
+            uint64_t cost = (uint64_t)height * png_row_bytes(width, png_pixel_bits(cand_depth[k], cand_colour[k]));
+            if (cand_colour[k] == 3) cost += png_encode_prefix(3, count, trns_len) - kPngFilePrefix;
+            if (!found || cost < least) found = true, least = cost, d = cand_depth[k], c = cand_colour[k];  // (ascending colour types)
+        }
+        if (!found) return kPngNotRepresentable;
+    } else if (c == 3) {
+        if (!have_colour || count < 1 || count > (1u << d)) return kPngBadPlte;
+        if (trns_len > count) return kPngBadTrns;
+    }
+    uint64_t rb = 0, p = 0;
+    if (png_encode_sizes(width, height, d, c, rb, p) != kPngOk) return kPngBadSizes;
+    depth = d, colour = c;
+    pix = p, types = height;
+    prefix = png_encode_prefix(c, count, trns_len);
+    file = prefix + png_ultrafast_bound((uint64_t)height * (rb + 1)) + kPngFileSuffix;
+    return kPngOk;
+}
+
 // ---- values that follow from the specification ----
+static_assert(png_encode_prefix(0, 7, 7) == 41 && png_encode_prefix(3, 1, 0) == 56 && png_encode_prefix(3, 256, 256) == 41 + 12 + 768 + 12 + 256,
+              "the exact-palette prefix");
+static_assert(png_ultrafast_bound(0) == 60 && png_ultrafast_bound(65536) == 98364, "fdh_ultrafast_bound");
 static_assert(png_pair_ok(1, 0) && png_pair_ok(2, 0) && png_pair_ok(4, 0) && png_pair_ok(8, 0) && png_pair_ok(16, 0) &&
               png_pair_ok(8, 2) && png_pair_ok(16, 2) && png_pair_ok(1, 3) && png_pair_ok(2, 3) && png_pair_ok(4, 3) &&
               png_pair_ok(8, 3) && png_pair_ok(8, 4) && png_pair_ok(16, 4) && png_pair_ok(8, 6) && png_pair_ok(16, 6),

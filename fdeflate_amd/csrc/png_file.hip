@@ -187,9 +187,23 @@ struct CrcArgs {
     // sum goes to the aligned word inside the 16 bytes behind the stream (png_frame_finish_kernel picks it up there)
     const uint32_t* png_status;
     uint32_t prefix;
+    // fdh_png_frame_mixed_batch (info != nullptr): the prefix is each file's own, frame_prefix
+    const PngInfo* info;
+    const uint32_t* colour;
+    const uint32_t* trns_len;
 };
 
-constexpr uint32_t kPngPrefix = 41, kPngSuffix = 16;
+constexpr uint32_t kPngPrefix = kPngFilePrefix, kPngSuffix = kPngFileSuffix;
+
+// The bytes in front of file i's stream: the call's, or in a mixed batch (info != nullptr) what follows from the file's
+// record and palette (png_encode_prefix).  Asked only for files the prefix kernel has accepted: the arrays are there
+// where the colour type is 3.  The prefix kernel, the IDAT's CRC pass and the finishing kernel all ask here.
+__device__ __forceinline__ uint32_t frame_prefix(const PngInfo* info, const uint32_t* colour, const uint32_t* trns_len, uint64_t i,
+                                                 uint32_t call_prefix) {
+    if (!info) return call_prefix;
+    const bool palette = info[i].colour_type == 3;
+    return png_encode_prefix(info[i].colour_type, palette ? colour[4 * i] : 0u, palette ? trns_len[i] : 0u);
+}
 
 __device__ __forceinline__ uint32_t* frame_sum_word(uint8_t* stream_end) {
     return reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(stream_end) + 3) & ~(uintptr_t)3);
@@ -210,7 +224,7 @@ __global__ __launch_bounds__(THREADS) void crc32_ranges_kernel(CrcArgs a) {
     if (a.png_status) {
         if (a.png_status[i] != kPngOk) return;
         const uint32_t s = a.len[i];
-        const uint8_t* b = a.data + o + (a.prefix - 4);
+        const uint8_t* b = a.data + o + (frame_prefix(a.info, a.colour, a.trns_len, i, a.prefix) - 4);
         const uint32_t c = crc_piece<COPIES>(T, lane, b, b + 4 + s, 0u, w, a.pieces);
         uint32_t* sum = frame_sum_word(const_cast<uint8_t*>(b) + 4 + s);
         if (lane == 0) {
@@ -253,6 +267,8 @@ struct FrameArgs {
     const uint32_t* colour;
     const uint32_t* trns_len;
     uint32_t plte_entries, trns_entries;
+    // fdh_png_frame_mixed_batch only: width, bit_depth, colour_type and prefix are each file's own
+    const PngInfo* info;
 };
 
 __device__ __forceinline__ uint32_t crc_bitwise(uint32_t c, uint32_t v) {
@@ -324,6 +340,48 @@ __global__ __launch_bounds__(256) void png_frame_prefix_kernel(FrameArgs a) {
     a.png_status[i] = kPngOk;
 }
 
+// What stands in front of the stream of file i, written by one wavefront: signature and IHDR (a.width, a.bit_depth,
+// a.colour_type), with `palette` a PLTE of E entries -- the image's `count`, then 0, 0, 0 -- and where T > 0 a tRNS of T
+// alphas (then 255), the IDAT's head; a zero in the word that will collect the IDAT checksum, the file's length and status.
+__device__ __forceinline__ void frame_write_prefix(const FrameArgs& a, uint64_t i, int lane, CrcLane<1>& C, uint32_t s, uint32_t h,
+                                                   uint32_t count, uint32_t E, uint32_t T, uint32_t prefix, bool palette) {
+    uint8_t* f = a.file + a.file_off[i];
+    uint8_t* next = f + 33;
+    if (lane == 0) put_signature_ihdr(f, a, h);
+    if (palette) {
+        const uint32_t* pal = a.pal + 256 * i;
+        uint8_t* plte = next;
+        if (lane == 0) put_chunk_head(plte, 3 * E, 'P', 'L', 'T', 'E');
+        for (uint32_t e = (uint32_t)lane; e < E; e += 64) {
+            const uint32_t w = e < count ? pal[e] : 0u;
+            plte[8 + 3 * e] = (uint8_t)w;
+            plte[9 + 3 * e] = (uint8_t)(w >> 8);
+            plte[10 + 3 * e] = (uint8_t)(w >> 16);
+        }
+        next = plte + 12 + 3 * E;
+        if (T) {
+            if (lane == 0) put_chunk_head(next, T, 't', 'R', 'N', 'S');
+            for (uint32_t e = (uint32_t)lane; e < T; e += 64) next[8 + e] = e < count ? (uint8_t)(pal[e] >> 24) : (uint8_t)255;
+        }
+        // the wavefront reads back what its lanes wrote: the stores are complete before the loads are issued
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t c_plte = ~wave_crc<1>(C, lane, plte + 4, plte + 8 + 3 * E, 0xFFFFFFFFu);
+        if (lane == 0) put_be32(plte + 8 + 3 * E, c_plte);
+        if (T) {
+            const uint32_t c_trns = ~wave_crc<1>(C, lane, next + 4, next + 8 + T, 0xFFFFFFFFu);
+            if (lane == 0) put_be32(next + 8 + T, c_trns);
+            next += 12 + T;
+        }
+    }
+    if (lane == 0) {
+        put_chunk_head(next, s, 'I', 'D', 'A', 'T');
+        *frame_sum_word(f + prefix + s) = 0;
+        a.file_len[i] = s + prefix + kPngSuffix;
+        a.png_status[i] = kPngOk;
+    }
+}
+
 // fdh_png_frame_palette_batch: one file per wavefront, four to a workgroup that shares the CRC tables.  Lane 0 writes
 // signature, IHDR and the chunk heads; the lanes together write the PLTE's E entries (the image's own, then 0, 0, 0) and
 // the tRNS's T alphas (then 255), and the CRC of each chunk is wave_crc over the bytes just written.
@@ -346,47 +404,55 @@ __global__ __launch_bounds__(256) void png_frame_palette_prefix_kernel(FrameArgs
         return;
     }
     CrcLane<1> C{lds.t};
-    uint8_t* f = a.file + o;
-    const uint32_t* pal = a.pal + 256 * i;
-    uint8_t* plte = f + 33;
-    if (lane == 0) {
-        put_signature_ihdr(f, a, h);
-        put_chunk_head(plte, 3 * E, 'P', 'L', 'T', 'E');
+    frame_write_prefix(a, i, lane, C, s, h, count, E, T, a.prefix, true);
+}
+
+// fdh_png_frame_mixed_batch: the same wavefront per file with width, pair and palette sizes of the file's own: E is the
+// image's count and T its trns_len, so no entry is padding.
+__global__ __launch_bounds__(256) void png_frame_mixed_prefix_kernel(FrameArgs a) {
+    __shared__ CrcLds<1> lds;
+    lds.load((int)threadIdx.x, 256);
+    const int lane = (int)threadIdx.x & 63;
+    const uint64_t i = (uint64_t)blockIdx.x * 4 + uni(threadIdx.x >> 6);
+    if (i >= a.n) return;
+    const PngInfo r = mixed_record(a.info, i);
+    const uint64_t slot = a.file_off[i + 1] - a.file_off[i];
+    const uint32_t s = uni(a.idat_len[i]);
+    uint32_t st = kPngOk, count = 0, alphas = 0;
+    if (!mixed_encodable(r)) st = kPngSkipped;
+    else {
+        const bool palette = r.colour_type == 3;
+        bool bad_plte = false, bad_trns = false;
+        if (palette) {
+            const bool have = a.pal && a.colour && a.trns_len;
+            count = have ? uni(a.colour[4 * i]) : 0u;
+            alphas = have ? uni(a.trns_len[i]) : 0u;
+            bad_plte = count == 0 || count > (1u << r.bit_depth);
+            bad_trns = !bad_plte && alphas > count;
+            if (bad_plte) count = 1;  // (the sizes are checked with the smallest prefix a palette file can have)
+            if (bad_plte || bad_trns) alphas = 0;
+        }
+        st = frame_sizes_bad(s, r.height, slot, png_encode_prefix(r.colour_type, count, alphas)) ? kPngBadSizes
+             : bad_plte ? kPngBadPlte : bad_trns ? kPngBadTrns : kPngOk;
     }
-    for (uint32_t e = (uint32_t)lane; e < E; e += 64) {
-        const uint32_t w = e < count ? pal[e] : 0u;
-        plte[8 + 3 * e] = (uint8_t)w;
-        plte[9 + 3 * e] = (uint8_t)(w >> 8);
-        plte[10 + 3 * e] = (uint8_t)(w >> 16);
+    if (st != kPngOk) {
+        if (lane == 0) {
+            a.png_status[i] = st;
+            a.file_len[i] = 0;
+        }
+        return;
     }
-    uint8_t* next = plte + 12 + 3 * E;
-    if (T) {
-        if (lane == 0) put_chunk_head(next, T, 't', 'R', 'N', 'S');
-        for (uint32_t e = (uint32_t)lane; e < T; e += 64) next[8 + e] = e < count ? (uint8_t)(pal[e] >> 24) : (uint8_t)255;
-    }
-    // the wavefront reads back what its lanes wrote: the stores are complete before the loads are issued
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t c_plte = ~wave_crc<1>(C, lane, plte + 4, plte + 8 + 3 * E, 0xFFFFFFFFu);
-    if (lane == 0) put_be32(plte + 8 + 3 * E, c_plte);
-    if (T) {
-        const uint32_t c_trns = ~wave_crc<1>(C, lane, next + 4, next + 8 + T, 0xFFFFFFFFu);
-        if (lane == 0) put_be32(next + 8 + T, c_trns);
-        next += 12 + T;
-    }
-    if (lane == 0) {
-        put_chunk_head(next, s, 'I', 'D', 'A', 'T');
-        *frame_sum_word(f + a.prefix + s) = 0;
-        a.file_len[i] = s + a.prefix + kPngSuffix;
-        a.png_status[i] = kPngOk;
-    }
+    CrcLane<1> C{lds.t};
+    FrameArgs g = a;
+    g.width = r.width, g.bit_depth = r.bit_depth, g.colour_type = r.colour_type;
+    frame_write_prefix(g, i, lane, C, s, r.height, count, count, alphas, png_encode_prefix(r.colour_type, count, alphas), r.colour_type == 3);
 }
 
 // One file per lane: the IDAT's CRC from the word it was summed in, then IEND.
 __global__ __launch_bounds__(256) void png_frame_finish_kernel(FrameArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n || a.png_status[i] != kPngOk) return;
-    uint8_t* t = a.file + a.file_off[i] + a.prefix + a.idat_len[i];
+    uint8_t* t = a.file + a.file_off[i] + frame_prefix(a.info, a.colour, a.trns_len, i, a.prefix) + a.idat_len[i];
     const uint32_t c = *frame_sum_word(t);
     const uint8_t iend[12] = {0, 0, 0, 0, 'I', 'E', 'N', 'D', 0xAE, 0x42, 0x60, 0x82};
     put_be32(t, c);
@@ -559,7 +625,7 @@ hipError_t launch_crc(fdh::CrcArgs a, hipStream_t stream) {
 
 // what follows a framing call's prefix kernel: the IDAT's checksum into its word, then the 16 bytes behind the stream
 hipError_t launch_frame_tail(const fdh::FrameArgs& a, hipStream_t stream) {
-    fdh::CrcArgs c{a.file, a.file_off, a.idat_len, nullptr, nullptr, nullptr, a.n, 1, a.png_status, a.prefix};
+    fdh::CrcArgs c{a.file, a.file_off, a.idat_len, nullptr, nullptr, nullptr, a.n, 1, a.png_status, a.prefix, a.info, a.colour, a.trns_len};
     hipError_t e = launch_crc(c, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(fdh::png_frame_finish_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, stream, a);
@@ -595,6 +661,18 @@ extern "C" int fdh_launch_png_frame_palette(uint8_t* file, const uint64_t* file_
     fdh::FrameArgs a{file, file_off, idat_len, height, file_len, png_status, n, width, bit_depth, 3, prefix,
                      pal, colour, trns_len, plte_entries, trns_entries};
     hipLaunchKernelGGL(fdh::png_frame_palette_prefix_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    return (int)launch_frame_tail(a, stream);
+}
+
+// ... and with every file's own: the geometry from info[i], a PLTE / tRNS of exactly the image's entries.
+extern "C" int fdh_launch_png_frame_mixed(uint8_t* file, const uint64_t* file_off, const uint32_t* idat_len, const fdh_png_info* info,
+                                          const uint32_t* pal, const uint32_t* colour, const uint32_t* trns_len, uint32_t* file_len,
+                                          uint32_t* png_status, uint64_t n, hipStream_t stream) {
+    if (n == 0) return 0;
+    fdh::FrameArgs a{file, file_off, idat_len, nullptr, file_len, png_status, n, 0, 0, 0, 0, pal, colour, trns_len, 0, 0, info};
+    hipLaunchKernelGGL(fdh::png_frame_mixed_prefix_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     return (int)launch_frame_tail(a, stream);

@@ -20,20 +20,7 @@
 
 namespace fdh {
 
-// Record i with every field the same in all lanes as far as the compiler is concerned.
-__device__ __forceinline__ PngInfo mixed_record(const PngInfo* info, uint64_t i) {
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(info + i);
-    const uint32_t geom = uni(w[3]);
-    PngInfo r;
-    r.status = uni(w[0]), r.width = uni(w[1]), r.height = uni(w[2]);
-    r.bit_depth = (uint8_t)geom, r.colour_type = (uint8_t)(geom >> 8), r.interlace = (uint8_t)(geom >> 16), r.pad = 0;
-    r.idat_bytes = uni(w[4]), r.idat_chunks = uni(w[5]), r.first_idat = uni(w[6]), r.chunks = uni(w[7]);
-    return r;
-}
-
-__device__ __forceinline__ bool mixed_decodable(const PngInfo& r) {
-    return png_decodable(r.status, r.width, r.height, r.bit_depth, r.colour_type, r.interlace);
-}
+// (mixed_record and mixed_decodable: png_record.h, shared with the encode side's mixed batches)
 
 // ---- fdh_png_plan_batch ----
 struct PlanArgs {

@@ -623,6 +623,111 @@ int fdh_png_frame_palette_batch(uint8_t *file, const uint64_t *file_off, const u
                                 uint64_t n, uint32_t width, uint32_t bit_depth,
                                 uint32_t plte_entries, uint32_t trns_entries, void *hip_stream);
 
+/* ---- PNG encode: mixed batches ----------------------------------------------------------------------
+ * The encode steps above take width, bit_depth and colour_type as arguments of the call: one geometry per batch.
+ * The calls of this section take them per image from info[i], the record of "PNG decode: mixed batches", of which
+ * they read status, width, height, bit_depth, colour_type and interlace: one batch can hold pictures of any width,
+ * height, depth and colour type, and the calls of that section give the pictures back from what these write.  A record is
+ * ENCODABLE when status == 0, width and height are 1 .. 2^31-1, the depth / colour pair is one of the fifteen and
+ * interlace == 0 (interlaced files are not written); a DIMENSION record is the same with bit_depth == 0 and
+ * colour_type == 0, which means "choose for me": fdh_png_analyse_mixed_batch and the plan take it, the plan turns it
+ * into an encodable one.  A record that is neither gives png_status 3 and nothing is written for that image.  No new
+ * status value: 0, 1, 2, 3, 10, 11, 12, 13 mean what they mean above.
+ * All _batch calls take device pointers, enqueue on hip_stream and return: no allocation, no synchronisation, nothing
+ * outside a slot written, nothing outside [off[0], off[n]) read, n == 0 is success, more than 2^31-1 images
+ * FDH_ERR_INVALID_ARGUMENT.
+ *   upstream  (analyse, pack, choose, fused encoder) nullable; where upstream[i] != 0 the image is skipped and
+ *             png_status[i] = upstream[i]
+ * The geometry limits of the encode steps are the plan's: row_bytes below 2^25 (fdh_png_choose_filters_batch's) and
+ * height * (row_bytes + 1) below 2^31 (the fused encoder's); pack, choose and the fused encoder give 2 for an
+ * encodable record beyond them.
+ *
+ * fdh_png_analyse_mixed_batch -- fdh_png_analyse_batch at info[i].width; the record may be a dimension record or an
+ * encodable one.  The slot must be exactly height * width * 4 bytes, else 2.  pal, colour, trns_len, summary and
+ * the statuses 0 / 2 / 12 are byte for byte those of the per-width call on the image alone; the palette comes out
+ * sorted and FDH_PNG_ANALYSE_WAVES applies.  png_status[i] otherwise: 3 neither kind of record; or upstream.
+ *
+ * fdh_png_encode_plan_one / fdh_png_encode_plan_batch -- which pair a picture is written with and what a pipeline
+ * has to allocate for it, on the host for one record (plain arithmetic, no device) and on the device for n (one
+ * record per lane).  colour_count / trns_len point to one word each on the host; colour[4 n] (word 0 the count) /
+ * trns_len[n], summary[n] and analyse_status[n] are fdh_png_analyse_mixed_batch's outputs, each nullable: without
+ * colour or trns_len there is no palette; a missing summary counts as 0; a missing analyse_status as 12 for a
+ * dimension record and 0 for an encodable one.
+ * For a dimension record the pair is chosen and written into the record (only where the status is 0).  Candidates:
+ *   grey        (0, d)  summary bits 0 and 1 set; d the summary's depth
+ *   palette     (3, p)  analyse_status 0, count = colour[4 i] in 1 .. 256 and trns_len[i] <= count; p the smallest of
+ *                       1, 2, 4, 8 with 2^p >= count
+ *   grey-alpha  (4, 8)  bit 1 set
+ *   RGB         (2, 8)  bit 0 set
+ *   RGBA        (6, 8)  always
+ * A candidate is dropped where bit colour_type of `allowed` is clear; allowed == 0 means all five (other bits:
+ * FDH_ERR_INVALID_ARGUMENT from the batch call, ignored by the host call).  The cost of a candidate is height *
+ * row_bytes, for the palette plus 12 + 3 count + (trns_len ? 12 + trns_len : 0), its chunks; the smallest cost wins,
+ * the lower colour type on equal cost.  For an encodable record the pair is kept.
+ * The sizes, sizes[0 .. 3] or the four arrays of n (each nullable, as is png_status):
+ *   packed      height * row_bytes
+ *   types       height
+ *   prefix      41, or for colour type 3  41 + 12 + 3 count + (trns_len ? 12 + trns_len : 0): the EXACT palette, no
+ *               padding entries
+ *   file        prefix + fdh_ultrafast_bound(height * (row_bytes + 1)) + 16: a slot that always suffices
+ * status (the return value, or png_status[i]), the first that applies: 3 neither kind of record (or rec is null);
+ * analyse_status where it is neither 0 nor 12; 13 no candidate is left; for an encodable record of colour type 3,
+ * 10 without colour / trns_len or with a count outside 1 .. 2^depth, 11 trns_len above the count; 2 row_bytes is 2^25
+ * or more, or height * (row_bytes + 1) is 2^31 or more.  Where it is not 0 all four sizes are 0.  Nothing wraps.
+ *
+ * fdh_png_pack_mixed_batch -- fdh_png_pack_batch at image i's own pair and width.  The slots must be exactly the
+ * plan's sizes (height * width * 4 and height * row_bytes), else 2.  pal may be null only if no encodable image has
+ * colour type 3: such an image gets status 10 then.  The pix slot and the statuses 0 / 13 are byte for byte what
+ * that call gives for the image alone.  png_status[i] otherwise: 3 not encodable; or upstream.
+ *
+ * fdh_png_choose_filters_mixed_batch -- fdh_png_choose_filters_batch at image i's own row_bytes and bpp: the same
+ * types.  The slots must be exactly the plan's packed size and height bytes, else 2.  png_status[i] otherwise: 0;
+ * 3 not encodable; or upstream.  FDH_PNG_CHOOSE_LANES and FDH_PNG_CHOOSE_WAVES apply.
+ *
+ * fdh_png_filter_deflate_ultrafast_mixed_batch -- fdh_png_filter_deflate_ultrafast_batch at image i's own
+ * row_bytes and bpp: the same stream and out_len (0xFFFFFFFF where the out slot is too small).  pix and types
+ * slots exactly the plan's, else 2.  png_status[i]: 0; 1 a filter type above 4; 2; 3 not encodable; or upstream.
+ * Where it is not 0, out_len[i] = 0 and nothing is written.
+ *
+ * fdh_png_frame_mixed_batch -- fdh_png_frame_batch / fdh_png_frame_palette_batch with the IHDR of info[i] and, for
+ * colour type 3, a PLTE of exactly colour[4 i] entries and, where trns_len[i] > 0, a tRNS of exactly trns_len[i]
+ * bytes.  The zlib stream of image i is already in place at file_off[i] + prefix_i, the plan's prefix.  Every
+ * chunk's CRC is computed on the device.  file_len[i] = idat_len[i] + prefix_i + 16.  pal, colour and trns_len
+ * may be null only if no encodable image has colour type 3.
+ * png_status[i] -- nothing is written and file_len[i] = 0 unless it is 0; the first that applies: 3 not encodable;
+ * 2 fdh_png_frame_batch's conditions with this prefix (a palette that is refused counts with one entry); 10
+ * colour[4 i] is 0 or above 2^depth, or the arrays are missing; 11 trns_len[i] is above the count.
+ */
+uint32_t fdh_png_encode_plan_one(fdh_png_info *rec /* in, out */, const uint32_t *colour_count,
+                                 const uint32_t *trns_len, uint32_t summary, uint32_t analyse_status,
+                                 uint32_t allowed, uint64_t sizes[4]);
+int fdh_png_encode_plan_batch(fdh_png_info *info /* in, out */, const uint32_t *colour,
+                              const uint32_t *trns_len, const uint32_t *summary,
+                              const uint32_t *analyse_status, uint32_t allowed, uint64_t *pix_size,
+                              uint64_t *types_size, uint64_t *prefix, uint64_t *file_size,
+                              uint32_t *png_status, uint64_t n, void *hip_stream);
+int fdh_png_analyse_mixed_batch(const uint8_t *rgba, const uint64_t *rgba_off, const fdh_png_info *info,
+                                const uint32_t *upstream, uint32_t *pal, uint32_t *colour,
+                                uint32_t *trns_len, uint32_t *summary, uint32_t *png_status, uint64_t n,
+                                uint32_t max_colours, void *hip_stream);
+int fdh_png_pack_mixed_batch(const uint8_t *rgba, const uint64_t *rgba_off, uint8_t *pix,
+                             const uint64_t *pix_off, const fdh_png_info *info, const uint32_t *pal,
+                             const uint32_t *colour, const uint32_t *upstream, uint32_t *png_status,
+                             uint64_t n, void *hip_stream);
+int fdh_png_choose_filters_mixed_batch(const uint8_t *pix, const uint64_t *pix_off, uint8_t *types,
+                                       const uint64_t *types_off, const fdh_png_info *info,
+                                       const uint32_t *upstream, uint32_t *png_status, uint64_t n,
+                                       void *hip_stream);
+int fdh_png_filter_deflate_ultrafast_mixed_batch(const uint8_t *pix, const uint64_t *pix_off,
+                                                 const uint8_t *types, const uint64_t *types_off,
+                                                 uint8_t *out, const uint64_t *out_off, uint32_t *out_len,
+                                                 const fdh_png_info *info, const uint32_t *upstream,
+                                                 uint32_t *png_status, uint64_t n, void *hip_stream);
+int fdh_png_frame_mixed_batch(uint8_t *file, const uint64_t *file_off, const uint32_t *idat_len,
+                              const fdh_png_info *info, const uint32_t *pal, const uint32_t *colour,
+                              const uint32_t *trns_len, uint32_t *file_len, uint32_t *png_status,
+                              uint64_t n, void *hip_stream);
+
 /* ---- streaming decoder: `Decompressor` (src/decompress.rs:96-156, 179-342) ----------------
  * A host-side object with exactly `Decompressor::read`'s contract on HOST buffers; every bit of
  * decoding is done by fdh_inflate_batch_resumable on the device (the object keeps a device-resident
