@@ -16,6 +16,33 @@ import ctypes as C
 
 from . import _lib
 
+# what `import fdeflate_amd` offers (the package takes exactly these names); the rest of this module is reached as api.X
+__all__ = [
+    "Decompressor", "DecompressionError", "OutputTooLarge", "STATUS_NAMES", "FLAG_IGNORE_ADLER32",
+    "FLAG_SERIAL_ONLY", "FLAG_GENERAL_ONLY", "FLAG_NO_RECHECK", "compress_to_vec_ultra_fast", "debug_build_tables", "decompress_to_vec",
+    "decompress_to_vec_bounded", "deflate_ultrafast_batch", "inflate_batch", "inflate_batch_resumable", "ultrafast_bound",
+    "compress_to_vec_stored", "deflate_stored_batch", "stored_size", "compress_to_vec", "compress_to_vec_rle",
+    "compress_bound", "deflate_general_batch", "MODE_LEVEL1", "MODE_RLE", "MODE_LEVEL2", "MODE_LEVEL3",
+    "compress_to_vec_with_level", "inflate_batch_multi", "init_devices",
+    "shutdown_devices", "multi_uses_rccl", "png_unfilter_batch", "png_filter_batch", "inflate_png_batch", "png_filter_deflate_ultrafast_batch",
+    "png_choose_filters_batch", "png_encode_ultrafast_batch",
+    "crc32_batch", "png_file_bound", "png_geometry", "png_frame_batch", "png_encode_files_batch", "png_scan_files_batch",
+    "png_info_fields", "png_gather_idat_batch", "png_decode_files_batch", "PNG_FILE_PREFIX", "PNG_FILE_SUFFIX",
+    "PNG_FLAG_IGNORE_CRC", "PNG_SCAN_STATUS_NAMES", "PNG_OTHER_GEOMETRY", "PNG_COMP_SLOT_TOO_SMALL",
+    "PNG_INDEX_OUTSIDE_PALETTE", "PNG_BAD_PLTE", "PNG_BAD_TRNS", "png_colour_batch", "png_expand_batch",
+    "png_decode_files_rgba_batch", "PNG_FLAG_ADAM7", "png_adam7_size", "png_unfilter_interlaced_batch",
+    "PNG_OK", "PNG_BAD_FILTER_TYPE", "PNG_BAD_SIZES", "PNG_SKIPPED", "PNG_SCAN_NO_SIGNATURE", "PNG_SCAN_TRUNCATED",
+    "PNG_SCAN_BAD_IHDR", "PNG_SCAN_INTERLACED", "PNG_SCAN_CHUNK_STRUCTURE", "PNG_SCAN_CRC_MISMATCH",
+    "PNG_TOO_MANY_COLOURS", "PNG_NOT_REPRESENTABLE", "PNG_SUMMARY_OPAQUE", "PNG_SUMMARY_GREY", "PNG_ANALYSE_HASH_MUL",
+    "PNG_ANALYSE_HASH_BITS", "png_analyse_batch", "png_pack_batch", "png_palette_file_prefix", "png_frame_palette_batch",
+    "png_encode_rgba_files_batch",
+    "png_plan_sizes", "png_plan_batch", "png_gather_idat_mixed_batch", "png_colour_mixed_batch", "png_unfilter_mixed_batch",
+    "png_expand_mixed_batch", "png_decode_mixed_files_batch", "png_decode_mixed_files_rgba_batch",
+    "png_encode_plan_one", "png_encode_plan_batch", "png_analyse_mixed_batch", "png_pack_mixed_batch",
+    "png_choose_filters_mixed_batch", "png_filter_deflate_ultrafast_mixed_batch", "png_frame_mixed_batch",
+    "png_encode_records", "png_encode_mixed_rgba_files_batch",
+]
+
 STATUS_NAMES = [
     "Ok", "BadZlibHeader", "InsufficientInput", "InvalidBlockType",
     "InvalidUncompressedBlockLength", "InvalidHlit", "InvalidHdist", "InvalidCodeLengthRepeat",
@@ -126,44 +153,45 @@ def _take(ptr, n):
         _lib.lib().fdh_free(ptr)
 
 
+def _compress(symbol, data, *level):
+    """The one-shot compressors: fdh_compress_to_vec*(data, len, [level,] &out, &n) -> the stream as bytes."""
+    fn = getattr(_lib.lib(), symbol)
+    data = bytes(data)
+    out, n = C.c_void_p(), C.c_size_t()
+    _lib.check(fn(data, len(data), *level, C.byref(out), C.byref(n)))
+    return _take(out, n.value)
+
+
+def _decompress(symbol, data, *maxlen):
+    """The one-shot decompressors: fdh_decompress_to_vec*(data, len, [maxlen,] &out, &n, &status) -> (bytes, status)."""
+    fn = getattr(_lib.lib(), symbol)
+    data = bytes(data)
+    out, n, st = C.c_void_p(), C.c_size_t(), C.c_uint32()
+    _lib.check(fn(data, len(data), *maxlen, C.byref(out), C.byref(n), C.byref(st)))
+    return _take(out, n.value), st.value
+
+
 def decompress_to_vec_bounded(data, maxlen):
     """fdeflate::decompress_to_vec_bounded (src/decompress.rs:1111)."""
-    L = _lib.lib()
-    data = bytes(data)
-    out = C.c_void_p()
-    n = C.c_size_t()
-    st = C.c_uint32()
-    _lib.check(L.fdh_decompress_to_vec_bounded(data, len(data), maxlen, C.byref(out), C.byref(n), C.byref(st)))
-    buf = _take(out, n.value)
-    if st.value == 0:
+    buf, status = _decompress("fdh_decompress_to_vec_bounded", data, maxlen)
+    if status == 0:
         return buf
-    if st.value == OUTPUT_TOO_LARGE:
+    if status == OUTPUT_TOO_LARGE:
         raise OutputTooLarge(buf)
-    raise DecompressionError(st.value)
+    raise DecompressionError(status)
 
 
 def decompress_to_vec(data):
     """fdeflate::decompress_to_vec (src/decompress.rs:1079)."""
-    L = _lib.lib()
-    data = bytes(data)
-    out = C.c_void_p()
-    n = C.c_size_t()
-    st = C.c_uint32()
-    _lib.check(L.fdh_decompress_to_vec(data, len(data), C.byref(out), C.byref(n), C.byref(st)))
-    buf = _take(out, n.value)
-    if st.value != 0:
-        raise DecompressionError(st.value)
+    buf, status = _decompress("fdh_decompress_to_vec", data)
+    if status != 0:
+        raise DecompressionError(status)
     return buf
 
 
 def compress_to_vec_ultra_fast(data):
     """fdeflate::compress_to_vec_ultra_fast (src/compress/mod.rs:313)."""
-    L = _lib.lib()
-    data = bytes(data)
-    out = C.c_void_p()
-    n = C.c_size_t()
-    _lib.check(L.fdh_compress_to_vec_ultra_fast(data, len(data), C.byref(out), C.byref(n)))
-    return _take(out, n.value)
+    return _compress("fdh_compress_to_vec_ultra_fast", data)
 
 
 def ultrafast_bound(n):
@@ -172,32 +200,17 @@ def ultrafast_bound(n):
 
 def compress_to_vec_stored(data):
     """fdeflate::compress_to_vec_with_level(data, 0) (src/compress/mod.rs:299): stored blocks only."""
-    L = _lib.lib()
-    data = bytes(data)
-    out = C.c_void_p()
-    n = C.c_size_t()
-    _lib.check(L.fdh_compress_to_vec_stored(data, len(data), C.byref(out), C.byref(n)))
-    return _take(out, n.value)
+    return _compress("fdh_compress_to_vec_stored", data)
 
 
 def compress_to_vec(data):
     """fdeflate::compress_to_vec (src/compress/mod.rs:294): level 1 in this snapshot."""
-    L = _lib.lib()
-    data = bytes(data)
-    out = C.c_void_p()
-    n = C.c_size_t()
-    _lib.check(L.fdh_compress_to_vec(data, len(data), C.byref(out), C.byref(n)))
-    return _take(out, n.value)
+    return _compress("fdh_compress_to_vec", data)
 
 
 def compress_to_vec_rle(data):
     """fdeflate::compress_to_vec_rle (src/compress/mod.rs:306)."""
-    L = _lib.lib()
-    data = bytes(data)
-    out = C.c_void_p()
-    n = C.c_size_t()
-    _lib.check(L.fdh_compress_to_vec_rle(data, len(data), C.byref(out), C.byref(n)))
-    return _take(out, n.value)
+    return _compress("fdh_compress_to_vec_rle", data)
 
 
 LEVELS_PROVIDED = (0, 1, 2, 3)
@@ -209,12 +222,7 @@ def compress_to_vec_with_level(data, level):
     are not provided: ValueError."""
     if isinstance(level, bool) or not isinstance(level, int) or level not in LEVELS_PROVIDED:
         raise ValueError("compression level %r is not provided (levels 0, 1, 2 and 3 are)" % (level,))
-    L = _lib.lib()
-    data = bytes(data)
-    out = C.c_void_p()
-    n = C.c_size_t()
-    _lib.check(L.fdh_compress_to_vec_with_level(data, len(data), level, C.byref(out), C.byref(n)))
-    return _take(out, n.value)
+    return _compress("fdh_compress_to_vec_with_level", data, level)
 
 
 def compress_bound(n):
@@ -231,13 +239,9 @@ def deflate_general_batch(raw, in_off, out, out_off, mode, out_len=None):
     """Level-1 / -2 / -3 / RLE encode of n buffers (fdh_deflate_general_batch): a parser kernel (one stream
     per lane) that records the back-references, then a block-writer kernel (one stream per wavefront).
     Returns when the work has finished."""
-    import torch
     n = in_off.numel() - 1
-    if out_len is None:
-        out_len = torch.empty(n, dtype=torch.int32, device=raw.device)
-    with _OnDevice(raw, in_off, out, out_off, out_len) as stream:
-        _lib.check(_lib.lib().fdh_deflate_general_batch(_ptr(raw), _ptr(in_off), _ptr(out), _ptr(out_off),
-                                                       _ptr(out_len), n, mode, C.c_void_p(stream)))
+    out_len = _i32(out_len, raw, n)
+    _call("fdh_deflate_general_batch", raw, in_off, out, out_off, out_len, n, mode)
     return out_len
 
 
@@ -249,60 +253,77 @@ def stored_size(n):
 # batched device entry points
 # ------------------------------------------------------------------------------------------
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+_PROTOTYPES = {}   # symbol -> (function, (position, dtypes a tensor may have there) per device pointer, takes a stream)
 
 
-class _OnDevice:
-    """Checks that every tensor lives on ONE GPU and makes that GPU current for the duration of
-    the call: the C ABI launches on the current device (hipGetDevice) and on the stream it is
-    handed, so both must belong to the tensors' device even when another one is current."""
+def _prototype(symbol):
+    """_lib.SIGNATURES[symbol] as _call wants it, worked out at a symbol's first call."""
+    import torch
+    ints = {1: (torch.uint8, torch.int8), 4: (torch.int32, getattr(torch, "uint32", None)),
+            8: (torch.int64, getattr(torch, "uint64", None))}
+    params = _lib.SIGNATURES[symbol][1]
+    pointers = tuple((pos, ints[_lib.DEVICE_WIDTH[p]]) for pos, p in enumerate(params) if p in _lib.DEVICE_WIDTH)
+    _PROTOTYPES[symbol] = (getattr(_lib.lib(), symbol), pointers, params[-1:] == ("stream",))
+    return _PROTOTYPES[symbol]
 
-    def __init__(self, *ts):
-        import torch
-        dev = None
-        for t in ts:
-            if t is None:
-                continue
-            if not t.is_cuda:
-                raise ValueError("batched entry points take device tensors (HBM resident)")
-            if not t.is_contiguous():
-                raise ValueError("tensors must be contiguous")
-            if dev is None:
-                dev = t.device
-            elif t.device != dev:
-                raise ValueError("all tensors of one call must live on the same GPU (%s vs %s)" % (dev, t.device))
+
+def _call(symbol, *args):
+    """What every batched entry point does with its C function: `args` are the prototype's parameters without the
+    stream, tensors (or None) where _lib.SIGNATURES has a device pointer.  Every tensor must be contiguous and live on
+    ONE GPU; then each must have integer elements of the width the table records -- the kernel would read elements of
+    another width wrongly, or past the tensor's end.  That GPU is made current for the duration of the call: the C ABI
+    launches on the current device (hipGetDevice) and on the stream it is handed, so both must belong to the tensors'
+    device even when another one is current.  The tensors go in as pointers, torch's current stream of their device goes
+    last where the prototype takes one, and a result that is not 0 raises _lib.FdeflateHipError."""
+    import torch
+    fn, pointers, takes_stream = _PROTOTYPES.get(symbol) or _prototype(symbol)
+    argv = list(args)
+    dev = misfit = None
+    for pos, dtypes in pointers:
+        t = args[pos]
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise ValueError("batched entry points take device tensors (HBM resident)")
+        if not t.is_contiguous():
+            raise ValueError("tensors must be contiguous")
         if dev is None:
-            raise ValueError("no tensors")
-        self.dev = dev
-        self._guard = torch.cuda.device(dev)
+            dev = t.device
+        elif t.device != dev:
+            raise ValueError("all tensors of one call must live on the same GPU (%s vs %s)" % (dev, t.device))
+        if misfit is None and t.dtype not in dtypes:
+            misfit = (pos, dtypes)     # (reported behind the checks above, of every tensor)
+        argv[pos] = t.data_ptr()
+    if dev is None:
+        raise ValueError("no tensors")
+    if misfit is not None:
+        raise ValueError("%s: parameter %d takes a tensor of %s, not of %s"
+                         % (symbol, misfit[0], " or ".join(str(d) for d in misfit[1] if d), args[misfit[0]].dtype))
+    with torch.cuda.device(dev):
+        if takes_stream:
+            argv.append(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(fn(*argv))
 
-    def __enter__(self):
-        import torch
-        self._guard.__enter__()
-        return torch.cuda.current_stream(self.dev).cuda_stream
 
-    def __exit__(self, *exc):
-        return self._guard.__exit__(*exc)
+def _i32(t, like, *shape):
+    """The int32 output `t`, or a new one of `shape` on the device of `like` where the caller passed None."""
+    import torch
+    return t if t is not None else torch.empty(*shape, dtype=torch.int32, device=like.device)
+
+
+def _first(a, b):
+    """Per image the first status that is not 0: a where a != 0, else b."""
+    import torch
+    return torch.where(a != 0, a, b)
 
 
 def inflate_batch(comp, in_off, out, out_off, out_len=None, status=None, adler=None, flags=0):
     """One-shot decode of n zlib streams (fdh_inflate_batch).  All tensors on the device:
     comp/out uint8, in_off/out_off int64 [n+1], out_len/status/adler int32 [n] (allocated when
     None).  Enqueued on torch's current stream; returns (out_len, status, adler)."""
-    import torch
     n = in_off.numel() - 1
-    dev = comp.device
-    if out_len is None:
-        out_len = torch.empty(n, dtype=torch.int32, device=dev)
-    if status is None:
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-    if adler is None:
-        adler = torch.empty(n, dtype=torch.int32, device=dev)
-    with _OnDevice(comp, in_off, out, out_off, out_len, status, adler) as stream:
-        _lib.check(_lib.lib().fdh_inflate_batch(_ptr(comp), _ptr(in_off), _ptr(out), _ptr(out_off),
-                                               _ptr(out_len), _ptr(status), _ptr(adler), n, flags,
-                                               C.c_void_p(stream)))
+    out_len, status, adler = _i32(out_len, comp, n), _i32(status, comp, n), _i32(adler, comp, n)
+    _call("fdh_inflate_batch", comp, in_off, out, out_off, out_len, status, adler, n, flags)
     return out_len, status, adler
 
 
@@ -312,82 +333,52 @@ def inflate_batch_resumable(comp, in_off, out, out_off, resume, out_len=None, st
     resume_in says where each stream is taken up in this call (the slots then hold the output so far)."""
     import torch
     n = in_off.numel() - 1
-    dev = comp.device
-    if out_len is None:
-        out_len = torch.empty(n, dtype=torch.int32, device=dev)
-    if status is None:
-        status = torch.empty(n, dtype=torch.int32, device=dev)
-    if adler is None:
-        adler = torch.empty(n, dtype=torch.int32, device=dev)
+    out_len, status, adler = _i32(out_len, comp, n), _i32(status, comp, n), _i32(adler, comp, n)
     assert resume.dtype == torch.int32 and resume.numel() == 4 * n and resume.is_contiguous()
-    with _OnDevice(comp, in_off, out, out_off, out_len, status, adler, resume) as stream:
-        _lib.check(_lib.lib().fdh_inflate_batch_resumable(_ptr(comp), _ptr(in_off), _ptr(out), _ptr(out_off),
-                                                         _ptr(out_len), _ptr(status), _ptr(adler), n,
-                                                         flags | (0x8000 if resume_in else 0), _ptr(resume),
-                                                         C.c_void_p(stream)))
+    _call("fdh_inflate_batch_resumable", comp, in_off, out, out_off, out_len, status, adler, n,
+          flags | (0x8000 if resume_in else 0), resume)
     return out_len, status, adler
 
 
 def deflate_ultrafast_batch(raw, in_off, out, out_off, out_len=None):
     """Ultra-fast encode of n buffers (fdh_deflate_ultrafast_batch); returns out_len (int32)."""
-    import torch
     n = in_off.numel() - 1
-    if out_len is None:
-        out_len = torch.empty(n, dtype=torch.int32, device=raw.device)
-    with _OnDevice(raw, in_off, out, out_off, out_len) as stream:
-        _lib.check(_lib.lib().fdh_deflate_ultrafast_batch(_ptr(raw), _ptr(in_off), _ptr(out), _ptr(out_off),
-                                                         _ptr(out_len), n, C.c_void_p(stream)))
+    out_len = _i32(out_len, raw, n)
+    _call("fdh_deflate_ultrafast_batch", raw, in_off, out, out_off, out_len, n)
     return out_len
 
 
 def deflate_stored_batch(raw, in_off, out, out_off, out_len=None):
     """Level-0 (stored) encode of n buffers (fdh_deflate_stored_batch); returns out_len (int32)."""
-    import torch
     n = in_off.numel() - 1
-    if out_len is None:
-        out_len = torch.empty(n, dtype=torch.int32, device=raw.device)
-    with _OnDevice(raw, in_off, out, out_off, out_len) as stream:
-        _lib.check(_lib.lib().fdh_deflate_stored_batch(_ptr(raw), _ptr(in_off), _ptr(out), _ptr(out_off),
-                                                      _ptr(out_len), n, C.c_void_p(stream)))
+    out_len = _i32(out_len, raw, n)
+    _call("fdh_deflate_stored_batch", raw, in_off, out, out_off, out_len, n)
     return out_len
 
 
 def png_unfilter_batch(filt, filt_off, pix, pix_off, row_bytes, bpp, png_status=None):
     """PNG scanline reconstruction of n images, one image per wavefront (fdh_png_unfilter_batch)."""
-    import torch
     n = filt_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=filt.device)
-    with _OnDevice(filt, filt_off, pix, pix_off, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_unfilter_batch(_ptr(filt), _ptr(filt_off), _ptr(pix), _ptr(pix_off),
-                                                    _ptr(png_status), n, row_bytes, bpp, C.c_void_p(stream)))
+    png_status = _i32(png_status, filt, n)
+    _call("fdh_png_unfilter_batch", filt, filt_off, pix, pix_off, png_status, n, row_bytes, bpp)
     return png_status
 
 
 def png_filter_batch(pix, pix_off, types, types_off, filt, filt_off, row_bytes, bpp, png_status=None):
     """PNG scanline filtering with the given per-row filter types (fdh_png_filter_batch)."""
-    import torch
     n = pix_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
-    with _OnDevice(pix, pix_off, types, types_off, filt, filt_off, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_filter_batch(_ptr(pix), _ptr(pix_off), _ptr(types), _ptr(types_off), _ptr(filt),
-                                                  _ptr(filt_off), _ptr(png_status), n, row_bytes, bpp,
-                                                  C.c_void_p(stream)))
+    png_status = _i32(png_status, pix, n)
+    _call("fdh_png_filter_batch", pix, pix_off, types, types_off, filt, filt_off, png_status, n, row_bytes, bpp)
     return png_status
 
 
 def png_filter_deflate_ultrafast_batch(pix, pix_off, types, types_off, out, out_off, row_bytes, bpp):
     """Filter n images with the given per-row types and ultra-fast-encode the filtered bytes in one
     kernel, no intermediate buffer (fdh_png_filter_deflate_ultrafast_batch) -> (out_len, png_status)."""
-    import torch
     n = pix_off.numel() - 1
-    out_len = torch.empty(n, dtype=torch.int32, device=pix.device)
-    png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
-    with _OnDevice(pix, pix_off, types, types_off, out, out_off, out_len, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_filter_deflate_ultrafast_batch(
-            _ptr(pix), _ptr(pix_off), _ptr(types), _ptr(types_off), _ptr(out), _ptr(out_off), _ptr(out_len),
-            _ptr(png_status), n, row_bytes, bpp, C.c_void_p(stream)))
+    out_len, png_status = _i32(None, pix, n), _i32(None, pix, n)
+    _call("fdh_png_filter_deflate_ultrafast_batch", pix, pix_off, types, types_off, out, out_off, out_len, png_status, n,
+          row_bytes, bpp)
     return out_len, png_status
 
 
@@ -396,13 +387,9 @@ def png_choose_filters_batch(pix, pix_off, types, types_off, row_bytes, bpp, png
     whose filtered row has the smallest sum of absolute values, the lowest type number on equal sums
     (fdh_png_choose_filters_batch).  `types` (uint8) receives them at types_off (int64 [n+1], slots of
     exactly the row counts); returns png_status (0 ok, 2 sizes do not fit: nothing written)."""
-    import torch
     n = pix_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
-    with _OnDevice(pix, pix_off, types, types_off, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_choose_filters_batch(_ptr(pix), _ptr(pix_off), _ptr(types), _ptr(types_off),
-                                                          _ptr(png_status), n, row_bytes, bpp, C.c_void_p(stream)))
+    png_status = _i32(png_status, pix, n)
+    _call("fdh_png_choose_filters_batch", pix, pix_off, types, types_off, png_status, n, row_bytes, bpp)
     return png_status
 
 
@@ -426,23 +413,16 @@ def png_encode_ultrafast_batch(pix, pix_off, out, out_off, row_bytes, bpp, types
         types = torch.empty(max(1, span // row_bytes), dtype=torch.uint8, device=pix.device)
     chosen = png_choose_filters_batch(pix, pix_off, types, types_off, row_bytes, bpp)
     out_len, png_status = png_filter_deflate_ultrafast_batch(pix, pix_off, types, types_off, out, out_off, row_bytes, bpp)
-    return out_len, torch.where(chosen != 0, chosen, png_status), types
+    return out_len, _first(chosen, png_status), types
 
 
 def inflate_png_batch(comp, in_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0):
     """Decode n IDAT-style zlib streams and reconstruct their scanlines in one call
     (fdh_inflate_png_batch) -> (out_len, status, adler, png_status)."""
-    import torch
     n = in_off.numel() - 1
-    dev = comp.device
-    out_len = torch.empty(n, dtype=torch.int32, device=dev)
-    status = torch.empty(n, dtype=torch.int32, device=dev)
-    adler = torch.empty(n, dtype=torch.int32, device=dev)
-    png_status = torch.empty(n, dtype=torch.int32, device=dev)
-    with _OnDevice(comp, in_off, filt, filt_off, pix, pix_off) as stream:
-        _lib.check(_lib.lib().fdh_inflate_png_batch(_ptr(comp), _ptr(in_off), _ptr(filt), _ptr(filt_off), _ptr(out_len),
-                                                   _ptr(status), _ptr(adler), _ptr(pix), _ptr(pix_off),
-                                                   _ptr(png_status), n, flags, row_bytes, bpp, C.c_void_p(stream)))
+    out_len, status, adler, png_status = (_i32(None, comp, n) for _ in range(4))
+    _call("fdh_inflate_png_batch", comp, in_off, filt, filt_off, out_len, status, adler, pix, pix_off, png_status, n, flags,
+          row_bytes, bpp)
     return out_len, status, adler, png_status
 
 
@@ -513,30 +493,30 @@ def crc32_batch(data, off, length=None, seed=None, crc=None, status=None):
     length[i] bytes long (int32, e.g. an encoder's out_len), or the whole slot without `length`; seed[i] (int32) is the
     CRC of what came before.  -> (crc, status), int32 [n] (bit patterns of the unsigned values); status 2 and crc 0
     where length[i] exceeds the slot or is 0xFFFFFFFF.  Enqueued on torch's current stream."""
-    import torch
     n = off.numel() - 1
-    if crc is None:
-        crc = torch.empty(n, dtype=torch.int32, device=data.device)
-    if status is None:
-        status = torch.empty(n, dtype=torch.int32, device=data.device)
-    with _OnDevice(data, off, length, seed, crc, status) as stream:
-        _lib.check(_lib.lib().fdh_crc32_batch(_ptr(data), _ptr(off), _ptr(length), _ptr(seed), _ptr(crc), _ptr(status), n,
-                                             C.c_void_p(stream)))
+    crc, status = _i32(crc, data, n), _i32(status, data, n)
+    _call("fdh_crc32_batch", data, off, length, seed, crc, status, n)
     return crc, status
+
+
+def _enc_off(file_off, prefix):
+    """The ONE offsets array the fused encoders are given for file slots: enc_off[i] = file_off[i] + prefix, an int or a
+    tensor of one prefix per image, and the last slot ends PNG_FILE_SUFFIX bytes in front of its file slot's end, though
+    not in front of its own start: enc_off[n] = max(file_off[n] - 16, enc_off[n - 1]).  n is at least 1."""
+    import torch
+    n = file_off.numel() - 1
+    enc_off = torch.empty_like(file_off)
+    torch.add(file_off[:n], prefix, out=enc_off[:n])
+    enc_off[n] = torch.maximum(file_off[n] - PNG_FILE_SUFFIX, enc_off[n - 1])
+    return enc_off
 
 
 def png_frame_batch(file, file_off, idat_len, height, width, bit_depth, colour_type, file_len=None, png_status=None):
     """Signature, IHDR and the IDAT's head in front of the zlib streams that lie PNG_FILE_PREFIX bytes into their file
     slots, the IDAT's CRC and IEND behind them (fdh_png_frame_batch) -> (file_len, png_status)."""
-    import torch
     n = file_off.numel() - 1
-    if file_len is None:
-        file_len = torch.empty(n, dtype=torch.int32, device=file.device)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
-    with _OnDevice(file, file_off, idat_len, height, file_len, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_frame_batch(_ptr(file), _ptr(file_off), _ptr(idat_len), _ptr(height), _ptr(file_len),
-                                                 _ptr(png_status), n, width, bit_depth, colour_type, C.c_void_p(stream)))
+    file_len, png_status = _i32(file_len, file, n), _i32(png_status, file, n)
+    _call("fdh_png_frame_batch", file, file_off, idat_len, height, file_len, png_status, n, width, bit_depth, colour_type)
     return file_len, png_status
 
 
@@ -560,8 +540,7 @@ def png_encode_files_batch(pix, pix_off, file, file_off, width, bit_depth, colou
         e = torch.empty(0, dtype=torch.int32, device=dev)
         return e, e.clone(), torch.empty(0, dtype=torch.uint8, device=dev)
     height = ((pix_off[1:] - pix_off[:-1]) // row_bytes).clamp(max=0xFFFFFFFF).to(torch.int32)   # (bit pattern of the u32)
-    enc_off = file_off + PNG_FILE_PREFIX
-    enc_off[n] = torch.maximum(file_off[n] - PNG_FILE_SUFFIX, enc_off[n - 1])
+    enc_off = _enc_off(file_off, PNG_FILE_PREFIX)
     # one type per row; the buffer is sized by what `pix` could hold at most, so nothing is read back
     types_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     torch.cumsum((pix_off[1:] - pix_off[:-1]) // row_bytes, 0, out=types_off[1:])
@@ -569,7 +548,7 @@ def png_encode_files_batch(pix, pix_off, file, file_off, width, bit_depth, colou
     idat_len, enc_status, types = png_encode_ultrafast_batch(pix, pix_off, file, enc_off, row_bytes, bpp, types=types,
                                                              types_off=types_off)
     file_len, png_status = png_frame_batch(file, file_off, idat_len, height, width, bit_depth, colour_type)
-    return file_len, torch.where(enc_status != 0, enc_status, png_status), types
+    return file_len, _first(enc_status, png_status), types
 
 
 def png_scan_files_batch(file, file_off, file_len=None, info=None, flags=0):
@@ -577,12 +556,9 @@ def png_scan_files_batch(file, file_off, file_len=None, info=None, flags=0):
     [n, PNG_INFO_WORDS] on the device (png_info_fields names the columns of a host copy); info[:, 0] is the status."""
     import torch
     n = file_off.numel() - 1
-    if info is None:
-        info = torch.empty((n, PNG_INFO_WORDS), dtype=torch.int32, device=file.device)
+    info = _i32(info, file, n, PNG_INFO_WORDS)
     assert info.dtype == torch.int32 and info.numel() == PNG_INFO_WORDS * n
-    with _OnDevice(file, file_off, file_len, info) as stream:
-        _lib.check(_lib.lib().fdh_png_scan_files_batch(_ptr(file), _ptr(file_off), _ptr(file_len), _ptr(info), n, flags,
-                                                      C.c_void_p(stream)))
+    _call("fdh_png_scan_files_batch", file, file_off, file_len, info, n, flags)
     return info
 
 
@@ -597,16 +573,10 @@ def png_info_fields(info):
 def png_gather_idat_batch(file, file_off, info, comp, comp_off, width, bit_depth, colour_type, comp_len=None, png_status=None):
     """The IDAT bodies of every file one behind the other at comp_off (fdh_png_gather_idat_batch) -> (comp_len,
     png_status): 0 ok, 3 info says the file is not sound, 7 another geometry than the call's, 8 comp slot too small."""
-    import torch
     n = file_off.numel() - 1
-    if comp_len is None:
-        comp_len = torch.empty(n, dtype=torch.int32, device=file.device)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
-    with _OnDevice(file, file_off, info, comp, comp_off, comp_len, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_gather_idat_batch(_ptr(file), _ptr(file_off), _ptr(info), _ptr(comp), _ptr(comp_off),
-                                                       _ptr(comp_len), _ptr(png_status), n, width, bit_depth, colour_type,
-                                                       C.c_void_p(stream)))
+    comp_len, png_status = _i32(comp_len, file, n), _i32(png_status, file, n)
+    _call("fdh_png_gather_idat_batch", file, file_off, info, comp, comp_off, comp_len, png_status, n, width, bit_depth,
+          colour_type)
     return comp_len, png_status
 
 
@@ -644,14 +614,52 @@ def png_unfilter_interlaced_batch(filt, filt_off, pix, pix_off, width, bit_depth
     afterwards are not specified.  -> png_status: 0 ok, 1 a filter type above 4, 2 sizes do not fit, 3 upstream != 0."""
     import torch
     n = filt_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=filt.device)
+    png_status = _i32(png_status, filt, n)
     assert method is None or (method.dtype == torch.uint8 and method.numel() == n and method.is_contiguous())
-    with _OnDevice(filt, filt_off, pix, pix_off, method, upstream, upstream_len, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_unfilter_interlaced_batch(_ptr(filt), _ptr(filt_off), _ptr(pix), _ptr(pix_off), _ptr(method),
-                                                               _ptr(upstream), _ptr(upstream_len), _ptr(png_status), n, width,
-                                                               bit_depth, colour_type, C.c_void_p(stream)))
+    _call("fdh_png_unfilter_interlaced_batch", filt, filt_off, pix, pix_off, method, upstream, upstream_len, png_status, n,
+          width, bit_depth, colour_type)
     return png_status
+
+
+def _png_uniform_steps(file, file_off, info, comp, comp_off, filt, filt_off, pix, pix_off, geometry, rgba, png_status=None,
+                       adam7=False):
+    """The decode steps of a batch of ONE geometry = (width, bit_depth, colour_type), behind the scan and the allocation:
+    png_gather_idat_batch, with `rgba` png_colour_batch, then inflate_png_batch -- or, with `adam7`, inflate_batch and
+    png_unfilter_interlaced_batch.  png_status: what an earlier step (the plan) found, or None.
+    -> (status, png_status, pal, colour); png_status is the first that is not 0 in that order."""
+    import torch
+    row_bytes, bpp = png_geometry(*geometry)
+    _, gathered = png_gather_idat_batch(file, file_off, info, comp, comp_off, *geometry)
+    png_status = gathered if png_status is None else _first(png_status, gathered)
+    pal = colour = None
+    if rgba:
+        pal, colour, coloured = png_colour_batch(file, file_off, info, *geometry)
+        png_status = _first(png_status, coloured)
+    if adam7:
+        method = info.view(torch.uint8).view(-1, 4 * PNG_INFO_WORDS)[:, 14].contiguous()    # info.interlace, on the device
+        out_len, status, _ = inflate_batch(comp, comp_off, filt, filt_off, flags=0)
+        unfiltered = png_unfilter_interlaced_batch(filt, filt_off, pix, pix_off, *geometry, method=method, upstream=status,
+                                                   upstream_len=out_len)
+    else:
+        _, status, _, unfiltered = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0)
+    return status, _first(png_status, unfiltered), pal, colour
+
+
+def _png_pixels_to_rgba(decoded):
+    """The end of the two RGBA pipelines; `decoded` is what _png_files_to_pixels or _png_mixed_files_to_pixels returns.  The
+    RGBA buffer, then png_expand_batch at the batch's one geometry or png_expand_mixed_batch where there is none, with
+    everything found so far as upstream.  -> (rgba, rgba_off, info, status, png_status)."""
+    import torch
+    pix, pix_off, info, status, png_status, rgba_off, pal, colour, _, total, geometry = decoded
+    rgba = torch.empty(max(1, total), dtype=torch.uint8, device=pix.device)
+    if pix_off.numel() > 1:
+        upstream = _first(png_status, status)   # (a zlib status reaches expand as "not 0")
+        if geometry is not None:
+            expanded = png_expand_batch(pix, pix_off, rgba, rgba_off, *geometry, pal=pal, colour=colour, upstream=upstream)
+        else:
+            expanded = png_expand_mixed_batch(pix, pix_off, rgba, rgba_off, info, pal=pal, colour=colour, upstream=upstream)
+        png_status = _first(png_status, expanded)
+    return rgba[:total], rgba_off, info, status, png_status
 
 
 def _png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len, flags, rgba):
@@ -659,11 +667,11 @@ def _png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len
     every buffer (with `rgba` the RGBA slots as well), gather, with `rgba` png_colour_batch, then inflate_png_batch -- or,
     with PNG_FLAG_ADAM7 and at least one good interlaced file in the batch, inflate_batch and
     png_unfilter_interlaced_batch.
-    -> (pix, pix_off, info, status, png_status, rgba_off, pal, colour, total pixel bytes, total RGBA bytes); png_status is
-    the first that is not 0 in that order."""
+    -> (pix, pix_off, info, status, png_status, rgba_off, pal, colour, total pixel bytes, total RGBA bytes, the call's
+    geometry); png_status is the first that is not 0 in that order."""
     import numpy as np
     import torch
-    row_bytes, bpp = png_geometry(width, bit_depth, colour_type)
+    row_bytes, _ = png_geometry(width, bit_depth, colour_type)
     n = file_off.numel() - 1
     dev = file.device
     info = png_scan_files_batch(file, file_off, file_len, flags=flags)
@@ -684,20 +692,10 @@ def _png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len
     comp = torch.empty(max(1, total[0]), dtype=torch.uint8, device=dev)
     filt = torch.empty(max(1, total[1]), dtype=torch.uint8, device=dev)
     pix = torch.empty(max(1, total[2]), dtype=torch.uint8, device=dev)
-    _, png_status = png_gather_idat_batch(file, file_off, info, comp, comp_off, width, bit_depth, colour_type)
-    pal = colour = None
-    if rgba:
-        pal, colour, coloured = png_colour_batch(file, file_off, info, width, bit_depth, colour_type)
-        png_status = torch.where(png_status != 0, png_status, coloured)
-    if adam7.any():
-        method = info.view(torch.uint8).view(-1, 4 * PNG_INFO_WORDS)[:, 14].contiguous()    # info.interlace, on the device
-        out_len, status, _ = inflate_batch(comp, comp_off, filt, filt_off, flags=0)
-        unfiltered = png_unfilter_interlaced_batch(filt, filt_off, pix, pix_off, width, bit_depth, colour_type, method=method,
-                                                   upstream=status, upstream_len=out_len)
-    else:
-        _, status, _, unfiltered = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0)
-    png_status = torch.where(png_status != 0, png_status, unfiltered)
-    return pix, pix_off, info, status, png_status, offs[3], pal, colour, total[2], total[3]
+    geometry = (width, bit_depth, colour_type)
+    status, png_status, pal, colour = _png_uniform_steps(file, file_off, info, comp, comp_off, filt, filt_off, pix, pix_off, geometry,
+                                                         rgba, adam7=adam7.any())
+    return pix, pix_off, info, status, png_status, offs[3], pal, colour, total[2], total[3], geometry
 
 
 def png_decode_files_batch(file, file_off, width, bit_depth, colour_type, file_len=None, flags=0):
@@ -712,8 +710,8 @@ def png_decode_files_batch(file, file_off, width, bit_depth, colour_type, file_l
     png_decode_files_rgba_batch goes on to [H, W, 4] uint8 pictures; neither applies gamma); info as png_scan_files_batch;
     status the zlib decoder's (of an empty stream for a file that was skipped); png_status the gather's where that is not
     0 (3, 7), else inflate_png_batch's."""
-    pix, pix_off, info, status, png_status, _, _, _, total, _ = _png_files_to_pixels(file, file_off, width, bit_depth, colour_type,
-                                                                                    file_len, flags, False)
+    pix, pix_off, info, status, png_status, _, _, _, total, _, _ = _png_files_to_pixels(file, file_off, width, bit_depth, colour_type,
+                                                                                       file_len, flags, False)
     return pix[:total], pix_off, info, status, png_status
 
 
@@ -722,18 +720,11 @@ def png_colour_batch(file, file_off, info, width, bit_depth, colour_type, pal=No
     words R | G << 8 | B << 16 | A << 24 (None unless colour_type is 3), colour int32 [n, 4] (PLTE entry count, bit 0 =
     a colour key is present, key R or grey | G << 16, key B); png_status 0 ok, 3 / 7 as the gather's,
     PNG_BAD_PLTE (10), PNG_BAD_TRNS (11)."""
-    import torch
     n = file_off.numel() - 1
-    dev = file.device
-    if pal is None and colour_type == 3:
-        pal = torch.empty((n, 256), dtype=torch.int32, device=dev)
-    if colour is None:
-        colour = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=dev)
-    with _OnDevice(file, file_off, info, pal, colour, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_colour_batch(_ptr(file), _ptr(file_off), _ptr(info), _ptr(pal), _ptr(colour),
-                                                  _ptr(png_status), n, width, bit_depth, colour_type, C.c_void_p(stream)))
+    if colour_type == 3:
+        pal = _i32(pal, file, n, 256)
+    colour, png_status = _i32(colour, file, n, 4), _i32(png_status, file, n)
+    _call("fdh_png_colour_batch", file, file_off, info, pal, colour, png_status, n, width, bit_depth, colour_type)
     return pal, colour, png_status
 
 
@@ -744,14 +735,10 @@ def png_expand_batch(pix, pix_off, rgba, rgba_off, width, bit_depth, colour_type
     them (pal is needed for colour type 3; without colour there is no key and every palette index counts as inside);
     upstream (int32 [n]): where not 0 the image is skipped and its png_status is that value.  -> png_status: 0 ok, 2 the
     slots do not fit (nothing written), PNG_INDEX_OUTSIDE_PALETTE (9: such pixels are (0, 0, 0, 255))."""
-    import torch
     n = pix_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
-    with _OnDevice(pix, pix_off, rgba, rgba_off, pal, colour, upstream, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_expand_batch(_ptr(pix), _ptr(pix_off), _ptr(rgba), _ptr(rgba_off), _ptr(pal),
-                                                  _ptr(colour), _ptr(upstream), _ptr(png_status), n, width, bit_depth,
-                                                  colour_type, C.c_void_p(stream)))
+    png_status = _i32(png_status, pix, n)
+    _call("fdh_png_expand_batch", pix, pix_off, rgba, rgba_off, pal, colour, upstream, png_status, n, width, bit_depth,
+          colour_type)
     return png_status
 
 
@@ -763,17 +750,7 @@ def png_decode_files_rgba_batch(file, file_off, width, bit_depth, colour_type, f
     rgba[rgba_off[i]:rgba_off[i+1]].view(h, width, 4) is picture i -- samples scaled to eight bits, palette and tRNS
     applied (PNG specification; no gamma) --; info and status as png_decode_files_batch; png_status the first that is
     not 0 of gather, colour, inflate_png_batch and expand (3, 7; 10, 11; 1 .. 3; 9)."""
-    import torch
-    pix, pix_off, info, status, png_status, rgba_off, pal, colour, _, total = _png_files_to_pixels(
-        file, file_off, width, bit_depth, colour_type, file_len, flags, True)
-    rgba = torch.empty(max(1, total), dtype=torch.uint8, device=file.device)
-    n = file_off.numel() - 1
-    if n:
-        upstream = torch.where(png_status != 0, png_status, status)   # (a zlib status reaches expand as "not 0")
-        expanded = png_expand_batch(pix, pix_off, rgba, rgba_off, width, bit_depth, colour_type, pal=pal, colour=colour,
-                                    upstream=upstream)
-        png_status = torch.where(png_status != 0, png_status, expanded)
-    return rgba[:total], rgba_off, info, status, png_status
+    return _png_pixels_to_rgba(_png_files_to_pixels(file, file_off, width, bit_depth, colour_type, file_len, flags, True))
 
 
 # ------------------------------------------------------------------------------------------
@@ -799,40 +776,31 @@ def png_plan_sizes(record, max_bytes=0):
     return (int(st),) + tuple(int(v) for v in sizes)
 
 
+def _wanted(like, n, *wants):
+    """The size outputs of the plan calls: True -> a new int64 [n] on the device of `like`, False -> None, a tensor or None
+    -> itself."""
+    import torch
+    return [torch.empty(n, dtype=torch.int64, device=like.device) if w is True else None if w is False else w for w in wants]
+
+
 def png_plan_batch(info, max_bytes=0, comp_size=True, filt_size=True, pix_size=True, rgba_size=True, png_status=None):
     """png_plan_sizes for n scan records on the device (fdh_png_plan_batch).  Each of the four outputs is True
     (allocated), a tensor (int64 [n]) or None / False (not wanted).
     -> (comp_size, filt_size, pix_size, rgba_size, png_status), None for an output that was not wanted."""
-    import torch
     n = info.numel() // PNG_INFO_WORDS
-    outs = []
-    for want in (comp_size, filt_size, pix_size, rgba_size):
-        if want is True:
-            want = torch.empty(n, dtype=torch.int64, device=info.device)
-        elif want is False:
-            want = None
-        outs.append(want)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=info.device)
-    with _OnDevice(info, png_status, *outs) as stream:
-        _lib.check(_lib.lib().fdh_png_plan_batch(_ptr(info), int(max_bytes), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]),
-                                                _ptr(png_status), n, C.c_void_p(stream)))
-    return outs[0], outs[1], outs[2], outs[3], png_status
+    outs = _wanted(info, n, comp_size, filt_size, pix_size, rgba_size)
+    png_status = _i32(png_status, info, n)
+    _call("fdh_png_plan_batch", info, int(max_bytes), *outs, png_status, n)
+    return (*outs, png_status)
 
 
 def png_gather_idat_mixed_batch(file, file_off, info, comp, comp_off, upstream=None, comp_len=None, png_status=None):
     """png_gather_idat_batch for files of any geometry (fdh_png_gather_idat_mixed_batch) -> (comp_len, png_status):
     0 ok, 3 the record is not decodable (or does not describe the file), 8 comp slot too small, or upstream[i] where
     that is not 0."""
-    import torch
     n = file_off.numel() - 1
-    if comp_len is None:
-        comp_len = torch.empty(n, dtype=torch.int32, device=file.device)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
-    with _OnDevice(file, file_off, info, upstream, comp, comp_off, comp_len, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_gather_idat_mixed_batch(_ptr(file), _ptr(file_off), _ptr(info), _ptr(upstream), _ptr(comp),
-                                                             _ptr(comp_off), _ptr(comp_len), _ptr(png_status), n, C.c_void_p(stream)))
+    comp_len, png_status = _i32(comp_len, file, n), _i32(png_status, file, n)
+    _call("fdh_png_gather_idat_mixed_batch", file, file_off, info, upstream, comp, comp_off, comp_len, png_status, n)
     return comp_len, png_status
 
 
@@ -840,18 +808,9 @@ def png_colour_mixed_batch(file, file_off, info, upstream=None, pal=None, colour
     """png_colour_batch with every file's own depth and colour type (fdh_png_colour_mixed_batch) -> (pal, colour,
     png_status): pal int32 [n, 256] -- row i is written only if file i has colour type 3 --, colour int32 [n, 4];
     png_status 0, 3, 10, 11, or upstream[i] where that is not 0."""
-    import torch
     n = file_off.numel() - 1
-    dev = file.device
-    if pal is None:
-        pal = torch.empty((n, 256), dtype=torch.int32, device=dev)
-    if colour is None:
-        colour = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=dev)
-    with _OnDevice(file, file_off, info, upstream, pal, colour, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_colour_mixed_batch(_ptr(file), _ptr(file_off), _ptr(info), _ptr(upstream), _ptr(pal), _ptr(colour),
-                                                        _ptr(png_status), n, C.c_void_p(stream)))
+    pal, colour, png_status = _i32(pal, file, n, 256), _i32(colour, file, n, 4), _i32(png_status, file, n)
+    _call("fdh_png_colour_mixed_batch", file, file_off, info, upstream, pal, colour, png_status, n)
     return pal, colour, png_status
 
 
@@ -859,13 +818,9 @@ def png_unfilter_mixed_batch(filt, filt_off, pix, pix_off, info, upstream=None, 
     """png_unfilter_interlaced_batch at every image's own geometry and interlace method (fdh_png_unfilter_mixed_batch):
     the slots must be exactly the plan's filtered and packed sizes.  `filt` is reconstructed in place.
     -> png_status: 0 ok, 1 a filter type above 4, 2 sizes do not fit, 3 not decodable or upstream[i] != 0."""
-    import torch
     n = filt_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=filt.device)
-    with _OnDevice(filt, filt_off, pix, pix_off, info, upstream, upstream_len, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_unfilter_mixed_batch(_ptr(filt), _ptr(filt_off), _ptr(pix), _ptr(pix_off), _ptr(info), _ptr(upstream),
-                                                          _ptr(upstream_len), _ptr(png_status), n, C.c_void_p(stream)))
+    png_status = _i32(png_status, filt, n)
+    _call("fdh_png_unfilter_mixed_batch", filt, filt_off, pix, pix_off, info, upstream, upstream_len, png_status, n)
     return png_status
 
 
@@ -873,13 +828,9 @@ def png_expand_mixed_batch(pix, pix_off, rgba, rgba_off, info, pal=None, colour=
     """png_expand_batch at every image's own geometry (fdh_png_expand_mixed_batch).  pal / colour as
     png_colour_mixed_batch writes them; an image of colour type 3 without `pal` is status 10.
     -> png_status: 0 ok, 2 the slots do not fit, 3 not decodable, 9 an index outside the palette, or upstream[i]."""
-    import torch
     n = pix_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
-    with _OnDevice(pix, pix_off, rgba, rgba_off, info, pal, colour, upstream, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_expand_mixed_batch(_ptr(pix), _ptr(pix_off), _ptr(rgba), _ptr(rgba_off), _ptr(info), _ptr(pal),
-                                                        _ptr(colour), _ptr(upstream), _ptr(png_status), n, C.c_void_p(stream)))
+    png_status = _i32(png_status, pix, n)
+    _call("fdh_png_expand_mixed_batch", pix, pix_off, rgba, rgba_off, info, pal, colour, upstream, png_status, n)
     return png_status
 
 
@@ -924,21 +875,15 @@ def _png_mixed_files_to_pixels(file, file_off, file_len, flags, max_bytes, route
     pal = colour = geometry = None
     if uniform:
         geometry = (key_min & 0xFFFFFFFF, (key_min >> 32) & 0xFF, (key_min >> 40) & 0xFF)
-        row_bytes, bpp = png_geometry(*geometry)
-        _, gathered = png_gather_idat_batch(file, file_off, info, comp, comp_off, *geometry)
-        png_status = torch.where(png_status != 0, png_status, gathered)
-        if rgba:
-            pal, colour, coloured = png_colour_batch(file, file_off, info, *geometry)
-            png_status = torch.where(png_status != 0, png_status, coloured)
-        _, status, _, unfiltered = inflate_png_batch(comp, comp_off, filt, filt_off, pix, pix_off, row_bytes, bpp, flags=0)
+        status, png_status, pal, colour = _png_uniform_steps(file, file_off, info, comp, comp_off, filt, filt_off, pix, pix_off,
+                                                             geometry, rgba, png_status=png_status)
     else:
         _, png_status = png_gather_idat_mixed_batch(file, file_off, info, comp, comp_off, upstream=png_status)
         if rgba:
             pal, colour, png_status = png_colour_mixed_batch(file, file_off, info, upstream=png_status)
         out_len, status, _ = inflate_batch(comp, comp_off, filt, filt_off, flags=0)
-        unfiltered = png_unfilter_mixed_batch(filt, filt_off, pix, pix_off, info, upstream=torch.where(png_status != 0, png_status, status),
-                                              upstream_len=out_len)
-    png_status = torch.where(png_status != 0, png_status, unfiltered)
+        unfiltered = png_unfilter_mixed_batch(filt, filt_off, pix, pix_off, info, upstream=_first(png_status, status), upstream_len=out_len)
+        png_status = _first(png_status, unfiltered)
     return pix, pix_off, info, status, png_status, offs[3], pal, colour, total_pix, total_rgba, geometry
 
 
@@ -964,18 +909,7 @@ def png_decode_mixed_files_rgba_batch(file, file_off, file_len=None, flags=0, ma
     -> (rgba, rgba_off, info, status, png_status): rgba[rgba_off[i]:rgba_off[i+1]].view(height_i, width_i, 4) is
     picture i as png_decode_files_rgba_batch makes it; png_status the first that is not 0 of plan, gather, colour,
     reconstruction and expansion (2, 3; 3, 8; 10, 11; 1 .. 3; 9)."""
-    import torch
-    pix, pix_off, info, status, png_status, rgba_off, pal, colour, _, total, geometry = _png_mixed_files_to_pixels(
-        file, file_off, file_len, flags, max_bytes, route, True)
-    rgba = torch.empty(max(1, total), dtype=torch.uint8, device=file.device)
-    if file_off.numel() > 1:
-        upstream = torch.where(png_status != 0, png_status, status)   # (a zlib status reaches expand as "not 0")
-        if geometry is not None:
-            expanded = png_expand_batch(pix, pix_off, rgba, rgba_off, *geometry, pal=pal, colour=colour, upstream=upstream)
-        else:
-            expanded = png_expand_mixed_batch(pix, pix_off, rgba, rgba_off, info, pal=pal, colour=colour, upstream=upstream)
-        png_status = torch.where(png_status != 0, png_status, expanded)
-    return rgba[:total], rgba_off, info, status, png_status
+    return _png_pixels_to_rgba(_png_mixed_files_to_pixels(file, file_off, file_len, flags, max_bytes, route, True))
 
 
 # ------------------------------------------------------------------------------------------
@@ -1022,23 +956,13 @@ def png_analyse_mixed_batch(rgba, rgba_off, info, max_colours=256, with_pal=True
     height_i * width_i * 4 bytes.  info: dimension records or encodable ones (png_encode_records).
     -> (pal, colour, trns_len, summary, png_status) as png_analyse_batch; png_status also 3 (neither kind of record) or
     upstream[i] where that is not 0."""
-    import torch
     n = rgba_off.numel() - 1
-    dev = rgba.device
-    if pal is None and with_pal:
-        pal = torch.empty((n, 256), dtype=torch.int32, device=dev)
-    if colour is None:
-        colour = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    if trns_len is None:
-        trns_len = torch.empty(n, dtype=torch.int32, device=dev)
-    if summary is None:
-        summary = torch.empty(n, dtype=torch.int32, device=dev)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=dev)
-    with _OnDevice(rgba, rgba_off, info, upstream, pal, colour, trns_len, summary, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_analyse_mixed_batch(_ptr(rgba), _ptr(rgba_off), _ptr(info), _ptr(upstream), _ptr(pal), _ptr(colour),
-                                                         _ptr(trns_len), _ptr(summary), _ptr(png_status), n, max_colours,
-                                                         C.c_void_p(stream)))
+    if with_pal:
+        pal = _i32(pal, rgba, n, 256)
+    colour, trns_len = _i32(colour, rgba, n, 4), _i32(trns_len, rgba, n)
+    summary, png_status = _i32(summary, rgba, n), _i32(png_status, rgba, n)
+    _call("fdh_png_analyse_mixed_batch", rgba, rgba_off, info, upstream, pal, colour, trns_len, summary, png_status, n,
+          max_colours)
     return pal, colour, trns_len, summary, png_status
 
 
@@ -1048,48 +972,29 @@ def png_encode_plan_batch(info, colour=None, trns_len=None, summary=None, analys
     record gets its pair.  colour / trns_len / summary / analyse_status as png_analyse_mixed_batch writes them.  Each of the
     four outputs is True (allocated), a tensor (int64 [n]) or None / False (not wanted).
     -> (pix_size, types_size, prefix, file_size, png_status), None for an output that was not wanted."""
-    import torch
     n = info.numel() // PNG_INFO_WORDS
-    outs = []
-    for want in (pix_size, types_size, prefix, file_size):
-        if want is True:
-            want = torch.empty(n, dtype=torch.int64, device=info.device)
-        elif want is False:
-            want = None
-        outs.append(want)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=info.device)
-    with _OnDevice(info, colour, trns_len, summary, analyse_status, png_status, *outs) as stream:
-        _lib.check(_lib.lib().fdh_png_encode_plan_batch(_ptr(info), _ptr(colour), _ptr(trns_len), _ptr(summary), _ptr(analyse_status),
-                                                       int(allowed), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]),
-                                                       _ptr(png_status), n, C.c_void_p(stream)))
-    return outs[0], outs[1], outs[2], outs[3], png_status
+    outs = _wanted(info, n, pix_size, types_size, prefix, file_size)
+    png_status = _i32(png_status, info, n)
+    _call("fdh_png_encode_plan_batch", info, colour, trns_len, summary, analyse_status, int(allowed), *outs, png_status, n)
+    return (*outs, png_status)
 
 
 def png_pack_mixed_batch(rgba, rgba_off, pix, pix_off, info, pal=None, colour=None, upstream=None, png_status=None):
     """png_pack_batch at every picture's own pair and width (fdh_png_pack_mixed_batch): the slots must be exactly the plan's
     sizes.  An image of colour type 3 without `pal` is status 10.
     -> png_status: 0 ok, 2 the slots do not fit, 3 not encodable, 13 not representable, or upstream[i]."""
-    import torch
     n = rgba_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=rgba.device)
-    with _OnDevice(rgba, rgba_off, pix, pix_off, info, pal, colour, upstream, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_pack_mixed_batch(_ptr(rgba), _ptr(rgba_off), _ptr(pix), _ptr(pix_off), _ptr(info), _ptr(pal),
-                                                      _ptr(colour), _ptr(upstream), _ptr(png_status), n, C.c_void_p(stream)))
+    png_status = _i32(png_status, rgba, n)
+    _call("fdh_png_pack_mixed_batch", rgba, rgba_off, pix, pix_off, info, pal, colour, upstream, png_status, n)
     return png_status
 
 
 def png_choose_filters_mixed_batch(pix, pix_off, types, types_off, info, upstream=None, png_status=None):
     """png_choose_filters_batch at every picture's own row_bytes and bpp (fdh_png_choose_filters_mixed_batch).
     -> png_status: 0 ok, 2 the slots are not the plan's, 3 not encodable, or upstream[i]."""
-    import torch
     n = pix_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
-    with _OnDevice(pix, pix_off, types, types_off, info, upstream, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_choose_filters_mixed_batch(_ptr(pix), _ptr(pix_off), _ptr(types), _ptr(types_off), _ptr(info),
-                                                                _ptr(upstream), _ptr(png_status), n, C.c_void_p(stream)))
+    png_status = _i32(png_status, pix, n)
+    _call("fdh_png_choose_filters_mixed_batch", pix, pix_off, types, types_off, info, upstream, png_status, n)
     return png_status
 
 
@@ -1098,16 +1003,10 @@ def png_filter_deflate_ultrafast_mixed_batch(pix, pix_off, types, types_off, out
     """png_filter_deflate_ultrafast_batch at every picture's own row_bytes and bpp
     (fdh_png_filter_deflate_ultrafast_mixed_batch) -> (out_len, png_status): 0 ok, 1 a filter type above 4, 2 the slots are
     not the plan's, 3 not encodable, or upstream[i]; out_len 0xFFFFFFFF (-1) where the out slot is too small."""
-    import torch
     n = pix_off.numel() - 1
-    if out_len is None:
-        out_len = torch.empty(n, dtype=torch.int32, device=pix.device)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=pix.device)
-    with _OnDevice(pix, pix_off, types, types_off, out, out_off, out_len, info, upstream, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_filter_deflate_ultrafast_mixed_batch(_ptr(pix), _ptr(pix_off), _ptr(types), _ptr(types_off),
-                                                                          _ptr(out), _ptr(out_off), _ptr(out_len), _ptr(info),
-                                                                          _ptr(upstream), _ptr(png_status), n, C.c_void_p(stream)))
+    out_len, png_status = _i32(out_len, pix, n), _i32(png_status, pix, n)
+    _call("fdh_png_filter_deflate_ultrafast_mixed_batch", pix, pix_off, types, types_off, out, out_off, out_len, info, upstream,
+          png_status, n)
     return out_len, png_status
 
 
@@ -1116,15 +1015,9 @@ def png_frame_mixed_batch(file, file_off, idat_len, info, pal=None, colour=None,
     colour[i, 0] entries and a tRNS of exactly trns_len[i] bytes (fdh_png_frame_mixed_batch); the zlib streams lie the plan's
     prefix into their file slots.  -> (file_len, png_status): 0 ok, 3 not encodable, 2, 10, 11 as the framing calls (nothing
     written, file_len 0)."""
-    import torch
     n = file_off.numel() - 1
-    if file_len is None:
-        file_len = torch.empty(n, dtype=torch.int32, device=file.device)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
-    with _OnDevice(file, file_off, idat_len, info, pal, colour, trns_len, file_len, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_frame_mixed_batch(_ptr(file), _ptr(file_off), _ptr(idat_len), _ptr(info), _ptr(pal), _ptr(colour),
-                                                       _ptr(trns_len), _ptr(file_len), _ptr(png_status), n, C.c_void_p(stream)))
+    file_len, png_status = _i32(file_len, file, n), _i32(png_status, file, n)
+    _call("fdh_png_frame_mixed_batch", file, file_off, idat_len, info, pal, colour, trns_len, file_len, png_status, n)
     return file_len, png_status
 
 
@@ -1173,13 +1066,11 @@ def png_encode_mixed_rgba_files_batch(rgba, rgba_off, width, height, allowed=0, 
         prefix = torch.minimum(prefix, slot)
     status = png_pack_mixed_batch(rgba, rgba_off, pix, offs[0], info, pal=pal, colour=colour, upstream=planned)
     status = png_choose_filters_mixed_batch(pix, offs[0], types, offs[1], info, upstream=status)
-    enc_off = file_off.clone()
-    enc_off[:n] += prefix
-    enc_off[n] = torch.maximum(file_off[n] - PNG_FILE_SUFFIX, enc_off[n - 1])
+    enc_off = _enc_off(file_off, prefix)
     idat_len, status = png_filter_deflate_ultrafast_mixed_batch(pix, offs[0], types, offs[1], file, enc_off, info, upstream=status)
     idat_len = torch.where(status != 0, torch.zeros_like(idat_len), idat_len)     # (the framing then writes nothing)
     file_len, framed = png_frame_mixed_batch(file, file_off, idat_len, info, pal, colour, trns_len)
-    return file, file_off, file_len, torch.where(status != 0, status, framed), info
+    return file, file_off, file_len, _first(status, framed), info
 
 
 # ------------------------------------------------------------------------------------------
@@ -1195,22 +1086,12 @@ def png_analyse_batch(rgba, rgba_off, width, max_colours=256, with_pal=True, pal
     summary int32 [n]: PNG_SUMMARY_OPAQUE, PNG_SUMMARY_GREY, bits 8 .. 15 the smallest sample depth of 1, 2, 4, 8 that
     loses nothing; png_status 0 ok, 2 the slot is not whole rows (nothing written for the image), PNG_TOO_MANY_COLOURS
     (12: more than max_colours distinct pixels; only summary is valid)."""
-    import torch
     n = rgba_off.numel() - 1
-    dev = rgba.device
-    if pal is None and with_pal:
-        pal = torch.empty((n, 256), dtype=torch.int32, device=dev)
-    if colour is None:
-        colour = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    if trns_len is None:
-        trns_len = torch.empty(n, dtype=torch.int32, device=dev)
-    if summary is None:
-        summary = torch.empty(n, dtype=torch.int32, device=dev)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=dev)
-    with _OnDevice(rgba, rgba_off, pal, colour, trns_len, summary, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_analyse_batch(_ptr(rgba), _ptr(rgba_off), _ptr(pal), _ptr(colour), _ptr(trns_len),
-                                                   _ptr(summary), _ptr(png_status), n, width, max_colours, C.c_void_p(stream)))
+    if with_pal:
+        pal = _i32(pal, rgba, n, 256)
+    colour, trns_len = _i32(colour, rgba, n, 4), _i32(trns_len, rgba, n)
+    summary, png_status = _i32(summary, rgba, n), _i32(png_status, rgba, n)
+    _call("fdh_png_analyse_batch", rgba, rgba_off, pal, colour, trns_len, summary, png_status, n, width, max_colours)
     return pal, colour, trns_len, summary, png_status
 
 
@@ -1222,14 +1103,10 @@ def png_pack_batch(rgba, rgba_off, pix, pix_off, width, bit_depth, colour_type, 
     is the lowest one whose word equals the pixel; without colour all 256 words count); upstream (int32 [n]): where not 0
     the image is skipped and its png_status is that value.  -> png_status: 0 ok, 2 the slots do not fit (nothing
     written), PNG_NOT_REPRESENTABLE (13: some pixel cannot be held by the pair without loss)."""
-    import torch
     n = rgba_off.numel() - 1
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=rgba.device)
-    with _OnDevice(rgba, rgba_off, pix, pix_off, pal, colour, upstream, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_pack_batch(_ptr(rgba), _ptr(rgba_off), _ptr(pix), _ptr(pix_off), _ptr(pal), _ptr(colour),
-                                                _ptr(upstream), _ptr(png_status), n, width, bit_depth, colour_type,
-                                                C.c_void_p(stream)))
+    png_status = _i32(png_status, rgba, n)
+    _call("fdh_png_pack_batch", rgba, rgba_off, pix, pix_off, pal, colour, upstream, png_status, n, width, bit_depth,
+          colour_type)
     return png_status
 
 
@@ -1249,16 +1126,10 @@ def png_frame_palette_batch(file, file_off, idat_len, height, pal, colour, trns_
     in front of the zlib streams that lie png_palette_file_prefix(plte_entries, trns_entries) bytes into their file slots;
     the IDAT's CRC and IEND behind them.  -> (file_len, png_status): 0 ok, 2 as png_frame_batch, 10 colour[i, 0] is 0 or
     above plte_entries, 11 trns_len[i] is above trns_entries (nothing written, file_len 0)."""
-    import torch
     n = file_off.numel() - 1
-    if file_len is None:
-        file_len = torch.empty(n, dtype=torch.int32, device=file.device)
-    if png_status is None:
-        png_status = torch.empty(n, dtype=torch.int32, device=file.device)
-    with _OnDevice(file, file_off, idat_len, height, pal, colour, trns_len, file_len, png_status) as stream:
-        _lib.check(_lib.lib().fdh_png_frame_palette_batch(_ptr(file), _ptr(file_off), _ptr(idat_len), _ptr(height), _ptr(pal),
-                                                         _ptr(colour), _ptr(trns_len), _ptr(file_len), _ptr(png_status), n, width,
-                                                         bit_depth, plte_entries, trns_entries, C.c_void_p(stream)))
+    file_len, png_status = _i32(file_len, file, n), _i32(png_status, file, n)
+    _call("fdh_png_frame_palette_batch", file, file_off, idat_len, height, pal, colour, trns_len, file_len, png_status, n, width,
+          bit_depth, plte_entries, trns_entries)
     return file_len, png_status
 
 
@@ -1309,17 +1180,16 @@ def png_encode_rgba_files_batch(rgba, rgba_off, file, file_off, width, bit_depth
     if colour_type == 3:
         pal, colour, trns_len, _, upstream = png_analyse_batch(rgba, rgba_off, width, max_colours=plte_entries)
     packed = png_pack_batch(rgba, rgba_off, pix, pix_off, width, bit_depth, colour_type, pal=pal, colour=colour, upstream=upstream)
-    enc_off = file_off + prefix
-    enc_off[n] = torch.maximum(file_off[n] - PNG_FILE_SUFFIX, enc_off[n - 1])
+    enc_off = _enc_off(file_off, prefix)
     idat_len, enc_status, _ = png_encode_ultrafast_batch(pix, pix_off, file, enc_off, row_bytes, bpp, types=types, types_off=types_off)
-    before = torch.where(packed != 0, packed, enc_status)
+    before = _first(packed, enc_status)
     idat_len = torch.where(before != 0, torch.zeros_like(idat_len), idat_len)     # (the framing then writes nothing)
     if colour_type == 3:
         file_len, framed = png_frame_palette_batch(file, file_off, idat_len, height, pal, colour, trns_len, width, bit_depth,
                                                    plte_entries, trns_entries)
     else:
         file_len, framed = png_frame_batch(file, file_off, idat_len, height, width, bit_depth, colour_type)
-    return file_len, torch.where(before != 0, before, framed)
+    return file_len, _first(before, framed)
 
 
 def inflate_batch_multi(shards, flags=0, gather=True):
@@ -1372,9 +1242,7 @@ def debug_build_tables(code_lengths, hlit):
     lit = torch.empty(4096, dtype=torch.int32, device="cuda")
     dist = torch.empty(512, dtype=torch.int32, device="cuda")
     st = torch.zeros(4, dtype=torch.int32, device="cuda")
-    with _OnDevice(cl, lit, dist, st) as stream:
-        _lib.check(_lib.lib().fdh_debug_build_tables(_ptr(cl), hlit, _ptr(lit), _ptr(dist), _ptr(st),
-                                                    C.c_void_p(stream)))
+    _call("fdh_debug_build_tables", cl, hlit, lit, dist, st)
     torch.cuda.synchronize()
     s = st.cpu().tolist()
     return s[0], lit.cpu().numpy().view("uint32"), dist.cpu().numpy().view("uint32"), tuple(s[1:])

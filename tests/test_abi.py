@@ -28,6 +28,73 @@ def test_library_exports_every_declared_symbol():
     assert L.fdh_ultrafast_bound(0) == 60 and L.fdh_ultrafast_bound(65536) == 98364
 
 
+_SCALARS = {"uint64_t": "u64", "uint32_t": "u32", "size_t": "size", "int": "int"}
+_POINTEE_BYTES = {"uint8_t": 1, "uint32_t": 4, "uint64_t": 8, "fdh_png_info": 4, "fdh_resume_point": 4}
+
+
+def _declared_prototypes():
+    """{symbol: (result, [parameter, ...])} as the header spells them, comments and preprocessor lines taken out."""
+    text = open(os.path.join(ROOT, "include", "fdeflate_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
+    protos = {}
+    for result, name, params in re.findall(r"([^;{}]*?)\b(fdh_\w+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in protos, name
+        params = [" ".join(p.split()) for p in params.split(",")]
+        protos[name] = (" ".join(result.split()), [] if params == ["void"] else params)
+    return protos
+
+
+def _pointee(param):
+    """The type a pointer parameter points to, or None for a scalar one."""
+    if "*" not in param and "[" not in param:
+        return None
+    return re.match(r"(?:const )?(\w+)", param).group(1)
+
+
+def test_signature_table_agrees_with_the_header():
+    """Parameter count, the class of every parameter and of the result, the element width of every device pointer and
+    the place of the stream: a miscounted table entry would be undefined behaviour at the call, not an error."""
+    from fdeflate_amd import _lib
+    protos = _declared_prototypes()
+    assert set(protos) == set(_declared_symbols()) == set(_lib.SIGNATURES) and len(protos) == 65
+    assert _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES)
+    for name, (result, params) in protos.items():
+        t_result, t_params = _lib.SIGNATURES[name]
+        if "*" in result:
+            assert t_result == ("str" if result == "const char *" else "host"), name
+        else:
+            assert t_result == ("void" if result == "void" else _SCALARS[result]), name
+        assert len(t_params) == len(params), name
+        for pos, (token, param) in enumerate(zip(t_params, params)):
+            where = "%s, parameter %d (%s)" % (name, pos, param)
+            pointee = _pointee(param)
+            if pointee is None:
+                assert token == _SCALARS[param.split()[0]], where
+            elif token in _lib.DEVICE_WIDTH:
+                assert param.count("*") == 1 and "[" not in param, where
+                assert _lib.DEVICE_WIDTH[token] == _POINTEE_BYTES[pointee], where
+            else:
+                assert token == ("stream" if param == "void *hip_stream" else "host"), where   # exempt from the widths
+        assert ("stream" in t_params) == (t_params[-1:] == ("stream",)) == (params[-1:] == ["void *hip_stream"]), name
+
+
+def test_library_prototypes_are_set_from_the_table():
+    from fdeflate_amd import _lib
+    L = _lib.lib()
+    assert L.fdh_free.restype is None and L.fdh_free.argtypes == [ctypes.c_void_p]
+    assert L.fdh_crc32_batch.restype is ctypes.c_int and len(L.fdh_crc32_batch.argtypes) == 8
+    assert L.fdh_png_adam7_size.argtypes == [ctypes.c_uint32] * 4 and L.fdh_png_adam7_size.restype is ctypes.c_uint64
+    assert L.fdh_decompress_to_vec_bounded.argtypes[1:3] == [ctypes.c_size_t] * 2
+    assert hasattr(L, "fdh_debug_lost_records") and "fdh_debug_lost_records" not in _lib.SIGNATURES
+
+
+def test_import_of_the_package_does_not_import_torch():
+    import subprocess
+    import sys
+    subprocess.run([sys.executable, "-c", "import sys, fdeflate_amd; assert 'torch' not in sys.modules"], cwd=ROOT, check=True)
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():

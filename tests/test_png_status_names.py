@@ -26,6 +26,17 @@ def test_header_and_api_name_the_same_png_status_values():
     assert (header["OTHER_GEOMETRY"], header["COMP_SLOT_TOO_SMALL"], header["INDEX_OUTSIDE_PALETTE"], header["BAD_PLTE"], header["BAD_TRNS"]) == (7, 8, 9, 10, 11)
 
 
+def test_api_flags_are_the_headers():
+    """Every FLAG_* / PNG_FLAG_* of api is the header's FDH_FLAG_* / FDH_PNG_FLAG_* of the same name (the header may
+    define flags that api does not name)."""
+    text = open(os.path.join(ROOT, "include", "fdeflate_hip.h")).read()
+    header = {name: int(value, 16) for name, value in re.findall(r"^#define FDH_((?:PNG_)?FLAG_[A-Z0-9_]+)\s+(0x[0-9A-Fa-f]+)u\b", text, flags=re.M)}
+    named = {k: v for k, v in vars(api).items() if re.fullmatch(r"(PNG_)?FLAG_[A-Z0-9_]+", k)}
+    assert len(named) >= 22 and {"FLAG_IGNORE_ADLER32", "FLAG_NO_LANES", "PNG_FLAG_IGNORE_CRC", "PNG_FLAG_ADAM7"} <= set(named)
+    for name, value in named.items():
+        assert header[name] == value, name
+
+
 def test_scan_status_names_list_the_scan_values_in_order():
     header = _header_statuses()
     names = api.PNG_SCAN_STATUS_NAMES
