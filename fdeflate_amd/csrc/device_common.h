@@ -88,6 +88,15 @@ __device__ __forceinline__ uint32_t wave_scan_add(uint32_t v) { return wave_scan
 __device__ __forceinline__ uint32_t wave_scan_max(uint32_t v) { return wave_scan_incl<true>(v); }
 
 constexpr uint32_t kAdlerMod = 65521u;
+// The lane kernel and the segment kernel (inflate_lanes.h, inflate_segments.h) keep a lane's Adler-32 sums in 32 bits and
+// reduce them every kAdlerFoldLines lines of 16 bytes.  Between two reductions, from a < 65521 and b < 65521 and over n
+// lines of 0xFF (a line adds at most 4 080 to a, and 16 a + 34 680 to b):
+//   a <= 65 520 + 4 080 n ;  b <= 65 520 + n (16 x 65 520 + 34 680) + 16 x 4 080 x n (n - 1) / 2
+// 669 285 360 at n = 128, 0.156 of 2^32 (uniform random bytes reach half of the quadratic term); past 2^32 from n = 348 on.
+// The tails behind the last reduction add fewer than 2 lines more: the bound is asked for n + 2.
+constexpr uint32_t kAdlerFoldLines = 128;
+constexpr uint64_t adler_fold_bound(uint64_t n) { return 65520 + n * (16 * 65520 + 34680) + 16 * 4080 * (n * (n - 1) / 2); }
+static_assert(adler_fold_bound(kAdlerFoldLines + 2) < (1ull << 32), "32-bit Adler-32 sums of a lane overflow on 0xFF bytes: reduce more often");
 
 // RFC-1951 length / distance symbol tables (reference src/tables.rs:68-88, data).
 __device__ static const uint16_t kLenBase[29] = {3,  4,  5,  6,  7,  8,  9,  10, 11,  13,

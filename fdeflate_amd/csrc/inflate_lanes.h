@@ -162,7 +162,7 @@ __device__ __forceinline__ void lanes_decode(const LaneArgs& a, LaneLds& L) {
                 u = bytedot4(q.w, 0x01020304u, u);
                 ad_b += 16 * ad_a + u;
                 ad_a += s;
-                if (++blocks == 128) {  // 2 KiB: sums stay far below 2^32
+                if (++blocks == kAdlerFoldLines) {  // 2 KiB: the sums stay below 0.16 of 2^32 (device_common.h)
                     ad_a %= kAdlerMod;
                     ad_b %= kAdlerMod;
                     blocks = 0;

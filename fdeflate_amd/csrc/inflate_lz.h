@@ -876,6 +876,10 @@ struct LzOut {
 #endif
 };
 
+constexpr uint64_t kLzFlushLines = (kLzRing + 16 * kWave - 1) / (16 * kWave);   // lines of one lane in one lz_flush
+static_assert(255ull * kLzRing < (1ull << 32) && 64 * ((kLzFlushLines * 4080 * kLzRing) >> 20) < (1ull << 32),
+              "lz_flush adds the lanes' Adler-32 sums up in 32 bits");
+
 // Stores [flushed, O) to the slot -- whole 16-B lines unless `final` -- and folds the bytes into the
 // Adler-32 (as flush_ring: order-independent per-line sums, weights from the line's place in its block).
 __device__ __forceinline__ void lz_flush(LzLds& L, LzOut& o, const bool final, const int lane) {
@@ -915,14 +919,16 @@ __device__ __forceinline__ void lz_flush(LzLds& L, LzOut& o, const bool final, c
                 }
             }
         }
-        // (per-lane partial sums; the wavefront adds them up and reduces modulo 65521 once per flush: an image
-        //  is a few KiB, the sums stay far below 2^64)
+        // (per-lane partial sums; the wavefront adds them up and reduces modulo 65521 once per flush.  A flush is less
+        //  than kLzRing bytes -- see `ri` above --, kLzFlushLines lines for a lane: acc_a <= 4 080 lines = 16 320,
+        //  acc_b <= 4 080 x kLzRing a line = 58 490 880 at kLzRing = 3 584)
         acc_a += s;
         acc_b += (uint64_t)t + (uint64_t)s * (q_hi - blk_hi);  // the bytes of this block weigh (q_hi - blk_hi) more, seen from the flush's end
         ri = lz_wrap(ri + kWave * 16);
     }
     {
-        // (lane sums fit 32 bits: at most 64 lines of 16 bytes per lane and flush; the weighted sum in two halves)
+        // (the wavefront's sums are taken in 32 bits: A <= 255 kLzRing = 913 920; the weighted sum in two halves, the low
+        //  one 64 x 2^20 at most, the high one 64 x (acc_b >> 20): both far below 2^32, asserted below)
         const uint64_t A = __builtin_amdgcn_readlane(wave_scan_add((uint32_t)acc_a), 63);
         const uint64_t Bv = (uint64_t)__builtin_amdgcn_readlane(wave_scan_add((uint32_t)(acc_b & 0xFFFFFu)), 63) +
                             ((uint64_t)__builtin_amdgcn_readlane(wave_scan_add((uint32_t)(acc_b >> 20)), 63) << 20);

@@ -58,6 +58,13 @@ constexpr uint32_t kS2Slots = 48;          // checkpoint slots per lane
 constexpr uint32_t kS2CkptPerWave = kS2Slots * kWave;  // uint2 entries of scratch per wavefront
 constexpr uint32_t kS2PosBits = 17;        // checkpoint: segment-relative bit position below 2^17, bulk lines below 2^15
 constexpr uint32_t kS2MaxBreaks = 64;
+// Slot gate of the interval kernel and the landing decoder (seg2_plan, seg3_plan).  Their writers keep a lane's byte sum
+// `ad_a` in 32 bits to the end of the stream, and one lane may account for nearly all of a stream (lane 0 takes every long
+// run chain of seg2_write; a round of 128 bytes is flushed by lanes 0 .. 7 alone): what holds is the byte sum of the WHOLE
+// stream, (2^24 - 1) x 255 = 4 278 189 825, 0.996 of 2^32.  seg2_write also casts `total + pad0 - v` to int32.
+constexpr uint64_t kS2MaxSlot = 1ull << 24;
+static_assert((kS2MaxSlot - 1) * 255 < (1ull << 32), "uint32 ad_a of seg2_write / seg3_write: the byte sum of a whole stream");
+static_assert(kS2MaxSlot + 15 < (1ull << 31), "seg2_write: (int32_t)(total + pad0 - v)");
 
 #ifdef FDH_S2_DEBUG
 __device__ uint32_t g_s2dbg[8 * 2048];
@@ -451,7 +458,7 @@ __device__ __forceinline__ bool seg2_plan(const SegArgs& a, const uint32_t* lit,
     const uint8_t* in = a.in + i0;
     const uint64_t ilen = i1 - i0, ocap = o1 - o0;
     // segments below 2^16 bits (their chains may run on a little) and slots below 16 MiB: what a checkpoint can hold
-    bool ours = ilen < (1ull << 19) && ocap < (1ull << 24) && ilen * 8 >= a.canon_bits + 44ull;
+    bool ours = ilen < (1ull << 19) && ocap < kS2MaxSlot && ilen * 8 >= a.canon_bits + 44ull;
     const uint32_t in_bits = (uint32_t)(ilen * 8);
     const uint32_t cap = (uint32_t)ocap;
     bool canonical = true;

@@ -151,7 +151,7 @@ __device__ __forceinline__ bool seg3_plan(const SegArgs& a, const uint32_t* lit,
     const uint8_t* in = a.in + i0;
     const uint64_t ilen = i1 - i0, ocap = o1 - o0;
     const uint8_t* const buf_hi = a.in + a.in_off[a.n];
-    bool ours = ilen < (1ull << 19) && ocap < (1ull << 24) && ilen * 8 >= (uint64_t)a.canon_bits + 44;
+    bool ours = ilen < (1ull << 19) && ocap < kS2MaxSlot && ilen * 8 >= (uint64_t)a.canon_bits + 44;
     // (uniform) a lane may load kS3TailGuard bytes past the end of its stream: the last stream(s) of the batch take the
     // range-checked loads
     const bool edge = in + ilen + kS3TailGuard > buf_hi;
@@ -563,6 +563,14 @@ __device__ __forceinline__ bool seg3_write(const SegArgs& a, const uint32_t* lit
     const uint32_t ldsA = lds_offset(imgA), ldsB = lds_offset(imgB);
     uint8_t* const imgB8 = reinterpret_cast<uint8_t*>(imgB);
     uint32_t f0 = 0, qa = 0;
+    // Adler-32 terms of a lane to the end of the stream: ad_a the sum of its bytes (kS2MaxSlot has the bound), ad_b the sum
+    // of (total - v) x (bytes of the piece at v), ad_u the sum of k x byte k over its whole pieces -- B's share is
+    // ad_b - ad_u, never negative: a whole piece has total - v >= 16 > k, the partial last piece is summed byte by byte
+    // with its exact weights and adds nothing to ad_u.  ad_u is 32 bits: a piece adds at most 255 x 120 = 30 600, and a
+    // lane gets at most every eighth piece -- a round flushes from the lane 0 on, 64 pieces a turn, and all rounds but the
+    // last flush whole 128-byte lines (qa_new is a multiple of 128): at most 8 of a round's pieces are lane 0's share of
+    // 1 -- so at most total / 128 + 1 pieces: 4 010 833 800 below the slot gate, 0.934 of 2^32.
+    static_assert((kS2MaxSlot / 128 + 1) * 30600 < (1ull << 32), "uint32 ad_u of seg3_write");
     uint32_t ad_a = 0, ad_u = 0;
     unsigned long long ad_b = 0;
     bool bad = false;

@@ -973,7 +973,7 @@ __device__ __forceinline__ void segments_write(const SegArgs& a, SegLds& L, cons
         u = bytedot4(q.w, 0x01020304u, u);
         ad_b += 16 * ad_a + u;
         ad_a += s;
-        if (++blocks == 128) {
+        if (++blocks == kAdlerFoldLines) {  // (device_common.h has the bound)
             ad_a %= kAdlerMod;
             ad_b %= kAdlerMod;
             blocks = 0;

@@ -105,6 +105,21 @@ def _drive(fd, comps, in_cuts, out_cuts, per_call=False):
                     assert hk[out_base[i]:out_base[i] + produced].tobytes() == buf[:produced].tobytes(), (k, i)
                 if est not in (2, 17):
                     assert not rk[i].any(), (k, i, est, rk[i])  # "all zero for every other status"
+                else:
+                    # the record names a place inside what the call delivered, and its Adler word is the Adler-32 of
+                    # the bytes in front of that place (the call that goes on there starts its sums from it)
+                    rec = rk[i].view(np.uint32)
+                    opos = int(rec[2])
+                    if rec[0] == 0:
+                        # "no resume point" (include/fdeflate_hip.h: header_bit 0, the record all zero: go on from the
+                        # first byte).  Only for a call that delivered nothing: these streams lie far below the one gate
+                        # of the records (bit position < 2^30, DESIGN.md "Size gates"), so in front of any delivered
+                        # byte there is the start of a decoding step to name -- a record cleared by mistake would
+                        # otherwise cost only time and go unnoticed
+                        assert not rec.any() and int(res[0][i]) == 0, (k, i, est, rec.tolist(), int(res[0][i]))
+                    else:
+                        assert opos <= int(res[0][i]), (k, i, est, rec.tolist(), int(res[0][i]))
+                        assert int(rec[3]) == zlib.adler32(hk[out_base[i]:out_base[i] + opos].tobytes()), (k, i, est, rec.tolist())
     h = d_out.cpu().numpy()
     outs = [h[out_base[i]:out_base[i] + cap[i]] for i in range(n)]
     guards = all((h[out_base[i] + cap[i]:out_base[i + 1]] == 0xA5).all() for i in range(n))
