@@ -94,6 +94,19 @@ SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
 }.items()}
 EXPORTED_SYMBOLS = list(SIGNATURES)
 
+# The prototypes of the extension headers, in the same notation (tests/test_abi_png16.py compares):
+# include/fdeflate_hip_png16.h, the calls behind fdeflate_amd.png16.
+EXTENSION_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
+    "fdh_png_expand16_batch": "int 1 8 1 8 4 4 4 4 u64 u32 u32 u32 stream",
+    "fdh_png_expand16_mixed_batch": "int 1 8 1 8 4 4 4 4 4 u64 stream",
+    "fdh_png_pack16_batch": "int 1 8 1 8 4 4 u64 u32 u32 stream",
+}.items()}
+
+
+def signature(symbol):
+    """(result, parameters) of a symbol of either table."""
+    return SIGNATURES.get(symbol) or EXTENSION_SIGNATURES[symbol]
+
 
 def lib():
     global _lib
@@ -104,7 +117,7 @@ def lib():
             "%s is missing: the HIP extension has not been built (make -C fdeflate_amd/csrc); "
             "fdeflate_amd has no CPU fallback" % SO_PATH)
     L = C.CDLL(SO_PATH)
-    for name, (result, params) in SIGNATURES.items():
+    for name, (result, params) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()):
         fn = getattr(L, name)
         fn.restype = _CTYPES[result]
         fn.argtypes = [_CTYPES[p] for p in params]

@@ -257,11 +257,12 @@ _PROTOTYPES = {}   # symbol -> (function, (position, dtypes a tensor may have th
 
 
 def _prototype(symbol):
-    """_lib.SIGNATURES[symbol] as _call wants it, worked out at a symbol's first call."""
+    """The entry of _lib.SIGNATURES or _lib.EXTENSION_SIGNATURES for `symbol` as _call wants it, worked out at a
+    symbol's first call."""
     import torch
     ints = {1: (torch.uint8, torch.int8), 4: (torch.int32, getattr(torch, "uint32", None)),
             8: (torch.int64, getattr(torch, "uint64", None))}
-    params = _lib.SIGNATURES[symbol][1]
+    params = _lib.signature(symbol)[1]
     pointers = tuple((pos, ints[_lib.DEVICE_WIDTH[p]]) for pos, p in enumerate(params) if p in _lib.DEVICE_WIDTH)
     _PROTOTYPES[symbol] = (getattr(_lib.lib(), symbol), pointers, params[-1:] == ("stream",))
     return _PROTOTYPES[symbol]
@@ -269,8 +270,8 @@ def _prototype(symbol):
 
 def _call(symbol, *args):
     """What every batched entry point does with its C function: `args` are the prototype's parameters without the
-    stream, tensors (or None) where _lib.SIGNATURES has a device pointer.  Every tensor must be contiguous and live on
-    ONE GPU; then each must have integer elements of the width the table records -- the kernel would read elements of
+    stream, tensors (or None) where its table entry (_lib.signature) has a device pointer.  Every tensor must be
+    contiguous and live on ONE GPU; then each must have integer elements of the width the table records -- the kernel would read elements of
     another width wrongly, or past the tensor's end.  That GPU is made current for the duration of the call: the C ABI
     launches on the current device (hipGetDevice) and on the stream it is handed, so both must belong to the tensors'
     device even when another one is current.  The tensors go in as pointers, torch's current stream of their device goes
@@ -645,19 +646,24 @@ def _png_uniform_steps(file, file_off, info, comp, comp_off, filt, filt_off, pix
     return status, _first(png_status, unfiltered), pal, colour
 
 
-def _png_pixels_to_rgba(decoded):
-    """The end of the two RGBA pipelines; `decoded` is what _png_files_to_pixels or _png_mixed_files_to_pixels returns.  The
+def _png_pixels_to_rgba(decoded, sample_bytes=1, expand=None, expand_mixed=None):
+    """The end of the RGBA pipelines; `decoded` is what _png_files_to_pixels or _png_mixed_files_to_pixels returns.  The
     RGBA buffer, then png_expand_batch at the batch's one geometry or png_expand_mixed_batch where there is none, with
-    everything found so far as upstream.  -> (rgba, rgba_off, info, status, png_status)."""
+    everything found so far as upstream.  sample_bytes 2 (fdeflate_amd.png16): the RGBA8 offsets and total doubled, the
+    offsets on the device, and `expand` / `expand_mixed` in the two calls' places.
+    -> (rgba, rgba_off, info, status, png_status)."""
     import torch
     pix, pix_off, info, status, png_status, rgba_off, pal, colour, _, total, geometry = decoded
+    if sample_bytes != 1:
+        rgba_off, total = rgba_off * sample_bytes, total * sample_bytes
     rgba = torch.empty(max(1, total), dtype=torch.uint8, device=pix.device)
     if pix_off.numel() > 1:
         upstream = _first(png_status, status)   # (a zlib status reaches expand as "not 0")
         if geometry is not None:
-            expanded = png_expand_batch(pix, pix_off, rgba, rgba_off, *geometry, pal=pal, colour=colour, upstream=upstream)
+            expanded = (expand or png_expand_batch)(pix, pix_off, rgba, rgba_off, *geometry, pal=pal, colour=colour, upstream=upstream)
         else:
-            expanded = png_expand_mixed_batch(pix, pix_off, rgba, rgba_off, info, pal=pal, colour=colour, upstream=upstream)
+            expanded = (expand_mixed or png_expand_mixed_batch)(pix, pix_off, rgba, rgba_off, info, pal=pal, colour=colour,
+                                                                upstream=upstream)
         png_status = _first(png_status, expanded)
     return rgba[:total], rgba_off, info, status, png_status
 
@@ -839,12 +845,14 @@ def _read_back(t):
     return t.tolist()
 
 
-def _png_mixed_files_to_pixels(file, file_off, file_len, flags, max_bytes, route, rgba):
+def _png_mixed_files_to_pixels(file, file_off, file_len, flags, max_bytes, route, rgba, sample_bytes=1):
     """What png_decode_mixed_files_batch and png_decode_mixed_files_rgba_batch share: scan, plan, the four cumulative
     sums on the device, ONE read-back of six 64-bit words (the four totals, and the smallest and largest of the keys
     width | depth << 32 | colour << 40 | interlace << 48 over the images the plan accepts), then gather, colour,
     inflate and reconstruction.  A batch whose keys are all the same and not interlaced takes the calls of
-    png_decode_files_batch with that geometry, any other the mixed calls; `route` forces one.
+    png_decode_files_batch with that geometry, any other the mixed calls; `route` forces one.  sample_bytes 2
+    (fdeflate_amd.png16) with max_bytes: a file whose RGBA16 picture exceeds max_bytes is refused like one the plan
+    refuses (status 2, empty slots), on the device and in front of the sums.
     -> (pix, pix_off, info, status, png_status, rgba_off, pal, colour, total pixel bytes, total RGBA bytes, geometry of
     the uniform route or None)."""
     import torch
@@ -854,6 +862,11 @@ def _png_mixed_files_to_pixels(file, file_off, file_len, flags, max_bytes, route
     dev = file.device
     info = png_scan_files_batch(file, file_off, file_len, flags=flags)
     comp_size, filt_size, pix_size, rgba_size, png_status = png_plan_batch(info, max_bytes)
+    if sample_bytes != 1 and max_bytes:
+        # the plan's limit held against the picture the caller gets (rgba_size stays the RGBA8 size: the caller scales it)
+        over = (png_status == 0) & (rgba_size * sample_bytes > max_bytes)
+        comp_size, filt_size, pix_size, rgba_size = (torch.where(over, 0, s) for s in (comp_size, filt_size, pix_size, rgba_size))
+        png_status = torch.where(over, PNG_BAD_SIZES, png_status)
     offs = torch.zeros((4, n + 1), dtype=torch.int64, device=dev)
     torch.cumsum(torch.stack((comp_size, filt_size, pix_size, rgba_size)), 1, out=offs[:, 1:])
     words = info.view(-1, PNG_INFO_WORDS).to(torch.int64)

@@ -359,6 +359,39 @@ int fdh_png_expand_mixed_batch(const uint8_t* pix, const uint64_t* pix_off, uint
                     upstream, png_status, n, stream_of(hip_stream)));
 }
 
+// ---- PNG at 16 bits per sample (include/fdeflate_hip_png16.h): png_expand16.hip, png_mixed.hip, png_pack16.hip ----
+int fdh_png_expand16_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba16, const uint64_t* rgba16_off,
+                           const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream, uint32_t* png_status,
+                           uint64_t n, uint32_t width, uint32_t bit_depth, uint32_t colour_type, void* hip_stream) {
+    if (int rc = png_geometry_ok(width, bit_depth, colour_type)) return rc;
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({pix, pix_off, rgba16, rgba16_off, png_status, colour_type == 3 ? pal : png_status}, "null pointer", n, "images")) return rc;
+    const uint64_t row_bytes = fdh::png_row_bytes(width, fdh::png_pixel_bits(bit_depth, colour_type));
+    return launched("RGBA16 expansion kernel launch", fdh_launch_png_expand16(pix, pix_off, rgba16, rgba16_off, pal, colour, upstream,
+                    png_status, n, width, row_bytes, bit_depth, colour_type, stream_of(hip_stream)));
+}
+
+int fdh_png_expand16_mixed_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba16, const uint64_t* rgba16_off,
+                                 const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
+                                 uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({pix, pix_off, rgba16, rgba16_off, info, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed RGBA16 expansion kernel launch", fdh_launch_png_expand16_mixed(pix, pix_off, rgba16, rgba16_off, info, pal,
+                    colour, upstream, png_status, n, stream_of(hip_stream)));
+}
+
+int fdh_png_pack16_batch(const uint8_t* rgba16, const uint64_t* rgba16_off, uint8_t* pix, const uint64_t* pix_off,
+                         const uint32_t* upstream, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t colour_type,
+                         void* hip_stream) {
+    if (colour_type == 3 || !fdh::png_pair_ok(16, colour_type))
+        return fail(FDH_ERR_INVALID_ARGUMENT, "colour type must be 0, 2, 4 or 6 (the pairs of depth 16; there is no palette of 16-bit entries)");
+    if (int rc = png_geometry_ok(width, 16, colour_type)) return rc;
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({rgba16, rgba16_off, pix, pix_off, png_status}, "null pointer", n, "images")) return rc;
+    return launched("RGBA16 packing kernel launch", fdh_launch_png_pack16(rgba16, rgba16_off, pix, pix_off, upstream, png_status, n, width,
+                    colour_type, stream_of(hip_stream)));
+}
+
 // ---- PNG encode from RGBA8: analysis and packing (png_pack.hip), palette framing (png_file.hip) ----
 int fdh_png_analyse_batch(const uint8_t* rgba, const uint64_t* rgba_off, uint32_t* pal, uint32_t* colour, uint32_t* trns_len,
                           uint32_t* summary, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t max_colours, void* hip_stream) {

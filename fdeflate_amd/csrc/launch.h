@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "../../include/fdeflate_hip.h"
+#include "../../include/fdeflate_hip_png16.h"
 
 namespace fdh { struct SegArgs; }
 int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);  // inflate_seg3.hip, for inflate.hip
@@ -111,6 +112,16 @@ int fdh_launch_png_pack_mixed(const uint8_t* rgba, const uint64_t* rgba_off, uin
                               hipStream_t stream);
 int fdh_launch_png_choose_mixed(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off,
                                 const fdh_png_info* info, const uint32_t* upstream, uint32_t* status, uint64_t n, hipStream_t stream);
+// png_expand16.hip, png_mixed.hip, png_pack16.hip (include/fdeflate_hip_png16.h)
+int fdh_launch_png_expand16(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba16, const uint64_t* rgba16_off, const uint32_t* pal,
+                            const uint32_t* colour, const uint32_t* upstream, uint32_t* status, uint64_t n, uint32_t width,
+                            uint64_t row_bytes, uint32_t bit_depth, uint32_t colour_type, hipStream_t stream);
+int fdh_launch_png_expand16_mixed(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba16, const uint64_t* rgba16_off,
+                                  const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
+                                  uint32_t* status, uint64_t n, hipStream_t stream);
+int fdh_launch_png_pack16(const uint8_t* rgba16, const uint64_t* rgba16_off, uint8_t* pix, const uint64_t* pix_off,
+                          const uint32_t* upstream, uint32_t* status, uint64_t n, uint32_t width, uint32_t colour_type,
+                          hipStream_t stream);
 }
 
 namespace fdh {

@@ -156,8 +156,9 @@ struct MixedExpandArgs {
     const PngInfo* info;
 };
 
-__global__ __launch_bounds__(kWave) void png_mixed_expand_kernel(MixedExpandArgs m) {
-    __shared__ uint32_t pal[256];
+// Image blockIdx.x at OPX bytes per output pixel: 4 RGBA8, 8 RGBA16 (png_expand_body.h)
+template <int OPX>
+__device__ __forceinline__ void mixed_expand_image(const MixedExpandArgs& m, uint32_t* pal) {
     const uint64_t i = blockIdx.x;
     const uint32_t lane = threadIdx.x;
     const bool first = blockIdx.y == 0 && lane == 0;
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(kWave) void png_mixed_expand_kernel(MixedExpandArgs
     a.width = r.width;
     a.row_bytes = png_row_bytes(r.width, png_pixel_bits(r.bit_depth, r.colour_type));
 #define FDH_MIXED_EXPAND_CASE(D, C) \
-    case (D) * 8 + (C): png_expand_image<D, C>(a, i, lane, pal); break;
+    case (D) * 8 + (C): png_expand_image<D, C, OPX>(a, i, lane, pal); break;
     switch ((uint32_t)r.bit_depth * 8 + r.colour_type) {
         FDH_MIXED_EXPAND_CASE(1, 0)
         FDH_MIXED_EXPAND_CASE(2, 0)
@@ -193,6 +194,17 @@ __global__ __launch_bounds__(kWave) void png_mixed_expand_kernel(MixedExpandArgs
         default: break;  // (png_decodable has let none but the fifteen through)
     }
 #undef FDH_MIXED_EXPAND_CASE
+}
+
+__global__ __launch_bounds__(kWave) void png_mixed_expand_kernel(MixedExpandArgs m) {
+    __shared__ uint32_t pal[256];
+    mixed_expand_image<4>(m, pal);
+}
+
+// ---- fdh_png_expand16_mixed_batch (include/fdeflate_hip_png16.h) ----
+__global__ __launch_bounds__(kWave) void png_mixed_expand16_kernel(MixedExpandArgs m) {
+    __shared__ uint32_t pal[256];
+    mixed_expand_image<8>(m, pal);
 }
 
 }  // namespace fdh
@@ -249,5 +261,18 @@ extern "C" int fdh_launch_png_expand_mixed(const uint8_t* pix, const uint64_t* p
     const uint32_t waves = fdh::png_waves_per_image(n, "FDH_PNG_EXPAND_WAVES");
     fdh::MixedExpandArgs a{{pix, pix_off, rgba, rgba_off, pal, colour, upstream, status, n, 0, 0}, info};
     hipLaunchKernelGGL(fdh::png_mixed_expand_kernel, dim3((unsigned)n, waves), dim3(fdh::kWave), 0, stream, a);
+    return (int)hipGetLastError();
+}
+
+// (FDH_PNG_EXPAND16_WAVES, as fdh_launch_png_expand16)
+extern "C" int fdh_launch_png_expand16_mixed(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba16, const uint64_t* rgba16_off,
+                                             const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour,
+                                             const uint32_t* upstream, uint32_t* status, uint64_t n, hipStream_t stream) {
+    if (n == 0) return 0;
+    hipError_t e = hipMemsetAsync(status, 0, n * 4, stream);
+    if (e != hipSuccess) return (int)e;
+    const uint32_t waves = fdh::png_waves_per_image(n, "FDH_PNG_EXPAND16_WAVES");
+    fdh::MixedExpandArgs a{{pix, pix_off, rgba16, rgba16_off, pal, colour, upstream, status, n, 0, 0}, info};
+    hipLaunchKernelGGL(fdh::png_mixed_expand16_kernel, dim3((unsigned)n, waves), dim3(fdh::kWave), 0, stream, a);
     return (int)hipGetLastError();
 }
