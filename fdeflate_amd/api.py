@@ -1146,6 +1146,36 @@ def png_frame_palette_batch(file, file_off, idat_len, height, pal, colour, trns_
     return file_len, png_status
 
 
+def _png_rgba_to_files(rgba, rgba_off, file, file_off, width, pixel_bytes, row_bytes, bpp, prefix, pack, frame):
+    """The steps that png_encode_rgba_files_batch and png16.png_encode_rgba16_files_batch share, for pictures of
+    `pixel_bytes` per pixel: pack(pix, pix_off) -> png_status fills the packed rows, the fused filter + ultra-fast encode
+    writes the streams at file_off + prefix, and frame(idat_len, height) -> (file_len, png_status) writes the chunks
+    around them.  -> (file_len, png_status)."""
+    import torch
+    n = rgba_off.numel() - 1
+    dev = rgba.device
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=dev)
+        return e, e.clone()
+    rows = (rgba_off[1:] - rgba_off[:-1]) // (width * pixel_bytes)
+    height = rows.clamp(max=0xFFFFFFFF).to(torch.int32)                       # (bit pattern of the u32)
+    # packed rows and one filter type per row; both buffers are sized by what `rgba` could hold at most: no read-back
+    pix_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(rows * row_bytes, 0, out=pix_off[1:])
+    types_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(rows, 0, out=types_off[1:])
+    most = max(1, rgba.numel() // (width * pixel_bytes))
+    pix = torch.empty(most * row_bytes, dtype=torch.uint8, device=dev)
+    types = torch.empty(most, dtype=torch.uint8, device=dev)
+    packed = pack(pix, pix_off)
+    enc_off = _enc_off(file_off, prefix)
+    idat_len, enc_status, _ = png_encode_ultrafast_batch(pix, pix_off, file, enc_off, row_bytes, bpp, types=types, types_off=types_off)
+    before = _first(packed, enc_status)
+    idat_len = torch.where(before != 0, torch.zeros_like(idat_len), idat_len)     # (the framing then writes nothing)
+    file_len, framed = frame(idat_len, height)
+    return file_len, _first(before, framed)
+
+
 def png_encode_rgba_files_batch(rgba, rgba_off, file, file_off, width, bit_depth, colour_type, plte_entries=None, trns_entries=None):
     """RGBA8 pictures in, PNG files of the given depth / colour type out, on torch's current stream and without a read-back:
     for colour type 3 png_analyse_batch (max_colours = plte_entries, by default min(256, 2^bit_depth); trns_entries is
@@ -1162,10 +1192,7 @@ def png_encode_rgba_files_batch(rgba, rgba_off, file, file_off, width, bit_depth
     last one ends 16 bytes in front of its slot's end): the bytes that image i + 1's own prefix is written to afterwards.
     A stream that does not fit its file slot can therefore leave bytes in the first `prefix` of the next slot; they stay
     there only if that next image fails as well."""
-    import torch
     row_bytes, bpp = png_geometry(width, bit_depth, colour_type)
-    n = rgba_off.numel() - 1
-    dev = rgba.device
     if colour_type == 3:
         if plte_entries is None:
             plte_entries = min(256, 1 << bit_depth)
@@ -1176,33 +1203,22 @@ def png_encode_rgba_files_batch(rgba, rgba_off, file, file_off, width, bit_depth
         prefix = png_palette_file_prefix(plte_entries, trns_entries)
     else:
         prefix = PNG_FILE_PREFIX
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=dev)
-        return e, e.clone()
-    rows = (rgba_off[1:] - rgba_off[:-1]) // (width * 4)
-    height = rows.clamp(max=0xFFFFFFFF).to(torch.int32)                       # (bit pattern of the u32)
-    # packed rows and one filter type per row; both buffers are sized by what `rgba` could hold at most: no read-back
-    pix_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(rows * row_bytes, 0, out=pix_off[1:])
-    types_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(rows, 0, out=types_off[1:])
-    most = max(1, rgba.numel() // (width * 4))
-    pix = torch.empty(most * row_bytes, dtype=torch.uint8, device=dev)
-    types = torch.empty(most, dtype=torch.uint8, device=dev)
-    pal = colour = trns_len = upstream = None
-    if colour_type == 3:
-        pal, colour, trns_len, _, upstream = png_analyse_batch(rgba, rgba_off, width, max_colours=plte_entries)
-    packed = png_pack_batch(rgba, rgba_off, pix, pix_off, width, bit_depth, colour_type, pal=pal, colour=colour, upstream=upstream)
-    enc_off = _enc_off(file_off, prefix)
-    idat_len, enc_status, _ = png_encode_ultrafast_batch(pix, pix_off, file, enc_off, row_bytes, bpp, types=types, types_off=types_off)
-    before = _first(packed, enc_status)
-    idat_len = torch.where(before != 0, torch.zeros_like(idat_len), idat_len)     # (the framing then writes nothing)
-    if colour_type == 3:
-        file_len, framed = png_frame_palette_batch(file, file_off, idat_len, height, pal, colour, trns_len, width, bit_depth,
-                                                   plte_entries, trns_entries)
-    else:
-        file_len, framed = png_frame_batch(file, file_off, idat_len, height, width, bit_depth, colour_type)
-    return file_len, _first(before, framed)
+    pal = colour = trns_len = None
+
+    def pack(pix, pix_off):
+        nonlocal pal, colour, trns_len
+        upstream = None
+        if colour_type == 3:
+            pal, colour, trns_len, _, upstream = png_analyse_batch(rgba, rgba_off, width, max_colours=plte_entries)
+        return png_pack_batch(rgba, rgba_off, pix, pix_off, width, bit_depth, colour_type, pal=pal, colour=colour, upstream=upstream)
+
+    def frame(idat_len, height):
+        if colour_type == 3:
+            return png_frame_palette_batch(file, file_off, idat_len, height, pal, colour, trns_len, width, bit_depth, plte_entries,
+                                           trns_entries)
+        return png_frame_batch(file, file_off, idat_len, height, width, bit_depth, colour_type)
+
+    return _png_rgba_to_files(rgba, rgba_off, file, file_off, width, 4, row_bytes, bpp, prefix, pack, frame)
 
 
 def inflate_batch_multi(shards, flags=0, gather=True):

@@ -35,7 +35,10 @@ static_assert(kPngOk == FDH_PNG_STATUS_OK && kPngBadFilterType == FDH_PNG_STATUS
               kPngTooManyColours == FDH_PNG_STATUS_TOO_MANY_COLOURS && kPngNotRepresentable == FDH_PNG_STATUS_NOT_REPRESENTABLE, "the public header names the same values");
 
 // ---- geometry ----
-// the fifteen depth / colour-type pairs of the PNG specification (11.2.2, table 11.1)
+// the fifteen depth / colour-type pairs of the PNG specification (11.2.2, table 11.1): X(depth, colour) for each, in the order of
+// every switch over them
+#define FDH_PNG_FOR_EACH_PAIR(X) X(1, 0) X(2, 0) X(4, 0) X(8, 0) X(16, 0) X(8, 2) X(16, 2) \
+                                 X(1, 3) X(2, 3) X(4, 3) X(8, 3) X(8, 4) X(16, 4) X(8, 6) X(16, 6)
 FDH_PNG_FN bool png_pair_ok(uint32_t depth, uint32_t colour) {
     switch (colour) {
         case 0: return depth == 1 || depth == 2 || depth == 4 || depth == 8 || depth == 16;
@@ -210,10 +213,9 @@ FDH_PNG_FN uint32_t png_encode_plan(uint32_t status, uint32_t width, uint32_t he
 static_assert(png_encode_prefix(0, 7, 7) == 41 && png_encode_prefix(3, 1, 0) == 56 && png_encode_prefix(3, 256, 256) == 41 + 12 + 768 + 12 + 256,
               "the exact-palette prefix");
 static_assert(png_ultrafast_bound(0) == 60 && png_ultrafast_bound(65536) == 98364, "fdh_ultrafast_bound");
-static_assert(png_pair_ok(1, 0) && png_pair_ok(2, 0) && png_pair_ok(4, 0) && png_pair_ok(8, 0) && png_pair_ok(16, 0) &&
-              png_pair_ok(8, 2) && png_pair_ok(16, 2) && png_pair_ok(1, 3) && png_pair_ok(2, 3) && png_pair_ok(4, 3) &&
-              png_pair_ok(8, 3) && png_pair_ok(8, 4) && png_pair_ok(16, 4) && png_pair_ok(8, 6) && png_pair_ok(16, 6),
-              "the fifteen pairs");
+#define FDH_PNG_PAIR_OK(D, C) && png_pair_ok(D, C)
+static_assert(true FDH_PNG_FOR_EACH_PAIR(FDH_PNG_PAIR_OK), "the fifteen pairs");
+#undef FDH_PNG_PAIR_OK
 static_assert(!png_pair_ok(16, 3) && !png_pair_ok(8, 1) && !png_pair_ok(4, 2) && !png_pair_ok(0, 0) && !png_pair_ok(8, 7), "and no others");
 static_assert(png_bpp(1) == 1 && png_bpp(24) == 3 && png_bpp(64) == 8, "filter pixel sizes");
 static_assert(png_row_bytes(1, 1) == 1 && png_row_bytes(9, 1) == 2 && png_row_bytes(341, 24) == 1023 &&

@@ -115,21 +115,7 @@ __global__ __launch_bounds__(kWave) void png_mixed_pack_kernel(MixedPackArgs m) 
 #define FDH_MIXED_PACK_CASE(D, C) \
     case (D) * 8 + (C): png_pack_image<D, C>(a, i, lane, pal, slot); break;
     switch ((uint32_t)r.bit_depth * 8 + r.colour_type) {
-        FDH_MIXED_PACK_CASE(1, 0)
-        FDH_MIXED_PACK_CASE(2, 0)
-        FDH_MIXED_PACK_CASE(4, 0)
-        FDH_MIXED_PACK_CASE(8, 0)
-        FDH_MIXED_PACK_CASE(16, 0)
-        FDH_MIXED_PACK_CASE(8, 2)
-        FDH_MIXED_PACK_CASE(16, 2)
-        FDH_MIXED_PACK_CASE(1, 3)
-        FDH_MIXED_PACK_CASE(2, 3)
-        FDH_MIXED_PACK_CASE(4, 3)
-        FDH_MIXED_PACK_CASE(8, 3)
-        FDH_MIXED_PACK_CASE(8, 4)
-        FDH_MIXED_PACK_CASE(16, 4)
-        FDH_MIXED_PACK_CASE(8, 6)
-        FDH_MIXED_PACK_CASE(16, 6)
+        FDH_PNG_FOR_EACH_PAIR(FDH_MIXED_PACK_CASE)
         default: break;  // (png_encodable has let none but the fifteen through)
     }
 #undef FDH_MIXED_PACK_CASE

@@ -45,21 +45,7 @@ extern "C" int fdh_launch_png_expand(const uint8_t* pix, const uint64_t* pix_off
         hipLaunchKernelGGL((fdh::png_expand_kernel<D, C>), grid, block, 0, stream, a);         \
         break;
     switch (bit_depth * 8 + colour_type) {
-        FDH_EXPAND_CASE(1, 0)
-        FDH_EXPAND_CASE(2, 0)
-        FDH_EXPAND_CASE(4, 0)
-        FDH_EXPAND_CASE(8, 0)
-        FDH_EXPAND_CASE(16, 0)
-        FDH_EXPAND_CASE(8, 2)
-        FDH_EXPAND_CASE(16, 2)
-        FDH_EXPAND_CASE(1, 3)
-        FDH_EXPAND_CASE(2, 3)
-        FDH_EXPAND_CASE(4, 3)
-        FDH_EXPAND_CASE(8, 3)
-        FDH_EXPAND_CASE(8, 4)
-        FDH_EXPAND_CASE(16, 4)
-        FDH_EXPAND_CASE(8, 6)
-        FDH_EXPAND_CASE(16, 6)
+        FDH_PNG_FOR_EACH_PAIR(FDH_EXPAND_CASE)
         default: return -1;
     }
 #undef FDH_EXPAND_CASE

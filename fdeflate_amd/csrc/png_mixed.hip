@@ -176,21 +176,7 @@ __device__ __forceinline__ void mixed_expand_image(const MixedExpandArgs& m, uin
 #define FDH_MIXED_EXPAND_CASE(D, C) \
     case (D) * 8 + (C): png_expand_image<D, C, OPX>(a, i, lane, pal); break;
     switch ((uint32_t)r.bit_depth * 8 + r.colour_type) {
-        FDH_MIXED_EXPAND_CASE(1, 0)
-        FDH_MIXED_EXPAND_CASE(2, 0)
-        FDH_MIXED_EXPAND_CASE(4, 0)
-        FDH_MIXED_EXPAND_CASE(8, 0)
-        FDH_MIXED_EXPAND_CASE(16, 0)
-        FDH_MIXED_EXPAND_CASE(8, 2)
-        FDH_MIXED_EXPAND_CASE(16, 2)
-        FDH_MIXED_EXPAND_CASE(1, 3)
-        FDH_MIXED_EXPAND_CASE(2, 3)
-        FDH_MIXED_EXPAND_CASE(4, 3)
-        FDH_MIXED_EXPAND_CASE(8, 3)
-        FDH_MIXED_EXPAND_CASE(8, 4)
-        FDH_MIXED_EXPAND_CASE(16, 4)
-        FDH_MIXED_EXPAND_CASE(8, 6)
-        FDH_MIXED_EXPAND_CASE(16, 6)
+        FDH_PNG_FOR_EACH_PAIR(FDH_MIXED_EXPAND_CASE)
         default: break;  // (png_decodable has let none but the fifteen through)
     }
 #undef FDH_MIXED_EXPAND_CASE

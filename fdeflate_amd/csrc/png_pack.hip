@@ -82,21 +82,7 @@ extern "C" int fdh_launch_png_pack(const uint8_t* rgba, const uint64_t* rgba_off
         hipLaunchKernelGGL((fdh::png_pack_kernel<D, C>), grid, block, 0, stream, a);       \
         break;
     switch (bit_depth * 8 + colour_type) {
-        FDH_PACK_CASE(1, 0)
-        FDH_PACK_CASE(2, 0)
-        FDH_PACK_CASE(4, 0)
-        FDH_PACK_CASE(8, 0)
-        FDH_PACK_CASE(16, 0)
-        FDH_PACK_CASE(8, 2)
-        FDH_PACK_CASE(16, 2)
-        FDH_PACK_CASE(1, 3)
-        FDH_PACK_CASE(2, 3)
-        FDH_PACK_CASE(4, 3)
-        FDH_PACK_CASE(8, 3)
-        FDH_PACK_CASE(8, 4)
-        FDH_PACK_CASE(16, 4)
-        FDH_PACK_CASE(8, 6)
-        FDH_PACK_CASE(16, 6)
+        FDH_PNG_FOR_EACH_PAIR(FDH_PACK_CASE)
         default: return -1;
     }
 #undef FDH_PACK_CASE

@@ -8,7 +8,7 @@ The calls go through api._call: the same device, dtype and stream checks as ever
 fallback where the library or the GPU is missing.
 """
 from . import api
-from .api import PNG_FILE_PREFIX, _call, _enc_off, _first, _i32
+from .api import PNG_FILE_PREFIX, _call, _i32
 
 __all__ = ["png_expand16_batch", "png_expand16_mixed_batch", "png_pack16_batch", "png_decode_files_rgba16_batch",
            "png_decode_mixed_files_rgba16_batch", "png_encode_rgba16_files_batch"]
@@ -94,29 +94,10 @@ def png_encode_rgba16_files_batch(rgba16, rgba16_off, file, file_off, width, col
     one ends 16 bytes in front of its slot's end): the bytes that image i + 1's own prefix is written to afterwards.  A
     stream that does not fit its file slot can therefore leave bytes in the first 41 of the next slot; they stay there
     only if that next image fails as well."""
-    import torch
     if colour_type not in (0, 2, 4, 6):
         raise ValueError("colour_type must be 0, 2, 4 or 6 (the pairs of depth 16)")
     row_bytes, bpp = api.png_geometry(width, 16, colour_type)
-    n = rgba16_off.numel() - 1
-    dev = rgba16.device
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=dev)
-        return e, e.clone()
-    rows = (rgba16_off[1:] - rgba16_off[:-1]) // (width * 8)
-    height = rows.clamp(max=0xFFFFFFFF).to(torch.int32)                       # (bit pattern of the u32)
-    # packed rows and one filter type per row; both buffers are sized by what `rgba16` could hold at most: no read-back
-    pix_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(rows * row_bytes, 0, out=pix_off[1:])
-    types_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(rows, 0, out=types_off[1:])
-    most = max(1, rgba16.numel() // (width * 8))
-    pix = torch.empty(most * row_bytes, dtype=torch.uint8, device=dev)
-    types = torch.empty(most, dtype=torch.uint8, device=dev)
-    packed = png_pack16_batch(rgba16, rgba16_off, pix, pix_off, width, colour_type)
-    enc_off = _enc_off(file_off, PNG_FILE_PREFIX)
-    idat_len, enc_status, _ = api.png_encode_ultrafast_batch(pix, pix_off, file, enc_off, row_bytes, bpp, types=types, types_off=types_off)
-    before = _first(packed, enc_status)
-    idat_len = torch.where(before != 0, torch.zeros_like(idat_len), idat_len)     # (the framing then writes nothing)
-    file_len, framed = api.png_frame_batch(file, file_off, idat_len, height, width, 16, colour_type)
-    return file_len, _first(before, framed)
+    return api._png_rgba_to_files(
+        rgba16, rgba16_off, file, file_off, width, 8, row_bytes, bpp, PNG_FILE_PREFIX,
+        lambda pix, pix_off: png_pack16_batch(rgba16, rgba16_off, pix, pix_off, width, colour_type),
+        lambda idat_len, height: api.png_frame_batch(file, file_off, idat_len, height, width, 16, colour_type))

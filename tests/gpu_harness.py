@@ -1,5 +1,7 @@
 """Helpers for the -m gpu parity tests: pack streams, run the HIP path through the C ABI
 (fdeflate_amd.inflate_batch / deflate_ultrafast_batch) and the oracle on the same bytes."""
+import zlib
+
 import numpy as np
 
 import oracle_binding as ob
@@ -226,3 +228,85 @@ def gpu_deflate(raws, guard=3, slack=0, fill=0x5A):
         if not np.all(h[o0 + int(ln[2 * i]):o1] == fill):
             ok = False  # wrote past its own length inside the slot
     return res, ok
+
+
+# ---- fdh_inflate_batch_resumable ----
+
+def drive_resumable(fd, comps, in_cuts, out_cuts, per_call=False):
+    """All streams side by side in one batch; call k sees input up to in_cuts[i][k] and room up to out_cuts[i][k].
+    A slot is [out_off[j], out_off[j + 1]): the room a stream does not have yet is the slot of an empty stream
+    behind it (2n streams per call, every other one of length zero: InsufficientInput, nothing written).  The
+    input is packed anew for every call -- only the output has to stay where it is."""
+    import torch
+    n = len(comps)
+    cap = [oc[-1] for oc in out_cuts]
+    out_base = np.zeros(n + 1, dtype=np.int64)
+    out_base[1:] = np.cumsum([c + 16 for c in cap])
+    d_out = torch.full((int(out_base[-1]),), 0xA5, dtype=torch.uint8, device="cuda")
+    resume = torch.zeros((n, 4), dtype=torch.int32, device="cuda")
+    steps = max(max(len(x) for x in in_cuts), max(len(x) for x in out_cuts))
+    res = None
+    for k in range(steps):
+        io = np.zeros(2 * n + 1, dtype=np.int64)
+        oo = np.zeros(2 * n + 1, dtype=np.int64)
+        parts = []
+        pos = 0
+        for i in range(n):
+            cut = in_cuts[i][min(k, len(in_cuts[i]) - 1)]
+            parts.append(comps[i][:cut])
+            io[2 * i] = pos
+            pos += cut
+            io[2 * i + 1] = pos
+            oo[2 * i] = out_base[i]
+            oo[2 * i + 1] = out_base[i] + out_cuts[i][min(k, len(out_cuts[i]) - 1)]
+        io[2 * n] = pos
+        oo[2 * n] = out_base[n]
+        d_in = torch.from_numpy(np.frombuffer(b"".join(parts) + bytes(16), dtype=np.uint8).copy()).cuda()
+        r2 = torch.zeros((2 * n, 4), dtype=torch.int32, device="cuda")
+        r2[0::2] = resume
+        ln, st, ad = fd.inflate_batch_resumable(d_in, torch.from_numpy(io).cuda(), d_out, torch.from_numpy(oo).cuda(), r2,
+                                                resume_in=(k > 0))
+        torch.cuda.synchronize()
+        resume = r2[0::2].contiguous()
+        res = (ln.cpu().numpy().view(np.uint32)[0::2].copy(), st.cpu().numpy().view(np.uint32)[0::2].copy(),
+               ad.cpu().numpy().view(np.uint32)[0::2].copy())
+        if per_call:
+            # every call on its own: status, length and bytes so far are those of the reference's streaming `read`
+            # given the same input prefix and the same room in one go (src/decompress.rs:158-219 through the
+            # one-shot classification of :1111-1144), and a record is left exactly where the stream can go on
+            hk = d_out.cpu().numpy()
+            rk = resume.cpu().numpy()
+            for i in range(n):
+                cut = in_cuts[i][min(k, len(in_cuts[i]) - 1)]
+                room = out_cuts[i][min(k, len(out_cuts[i]) - 1)]
+                est, eout, _ = ob.decompress_bounded(comps[i][:cut], room)
+                assert int(res[1][i]) == est, (k, i, int(res[1][i]), est)
+                if est in (0, 17):
+                    assert int(res[0][i]) == len(eout) and hk[out_base[i]:out_base[i] + len(eout)].tobytes() == eout, (k, i)
+                if est == 2:
+                    d = ob.Decompressor()
+                    buf = np.zeros(max(room, 1), dtype=np.uint8)
+                    _, _, produced = d.read(comps[i][:cut], buf[:room], 0)
+                    assert int(res[0][i]) == produced, (k, i, int(res[0][i]), produced)
+                    assert hk[out_base[i]:out_base[i] + produced].tobytes() == buf[:produced].tobytes(), (k, i)
+                if est not in (2, 17):
+                    assert not rk[i].any(), (k, i, est, rk[i])  # "all zero for every other status"
+                else:
+                    # the record names a place inside what the call delivered, and its Adler word is the Adler-32 of
+                    # the bytes in front of that place (the call that goes on there starts its sums from it)
+                    rec = rk[i].view(np.uint32)
+                    opos = int(rec[2])
+                    if rec[0] == 0:
+                        # "no resume point" (include/fdeflate_hip.h: header_bit 0, the record all zero: go on from the
+                        # first byte).  Only for a call that delivered nothing: these streams lie far below the one gate
+                        # of the records (bit position < 2^30, DESIGN.md "Size gates"), so in front of any delivered
+                        # byte there is the start of a decoding step to name -- a record cleared by mistake would
+                        # otherwise cost only time and go unnoticed
+                        assert not rec.any() and int(res[0][i]) == 0, (k, i, est, rec.tolist(), int(res[0][i]))
+                    else:
+                        assert opos <= int(res[0][i]), (k, i, est, rec.tolist(), int(res[0][i]))
+                        assert int(rec[3]) == zlib.adler32(hk[out_base[i]:out_base[i] + opos].tobytes()), (k, i, est, rec.tolist())
+    h = d_out.cpu().numpy()
+    outs = [h[out_base[i]:out_base[i] + cap[i]] for i in range(n)]
+    guards = all((h[out_base[i] + cap[i]:out_base[i + 1]] == 0xA5).all() for i in range(n))
+    return res, outs, guards, resume.cpu().numpy()

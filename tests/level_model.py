@@ -25,6 +25,7 @@ the last call are in `last_counters` (a dict, empty for level 1 and RLE):
   maxsteps  the longest walk
 """
 import bisect
+import functools
 import zlib
 
 import numpy as np
@@ -547,3 +548,19 @@ def compress(data, level):
 def compress_rle(data):
     """compress_to_vec_rle(data) (compress/mod.rs:107-123, :306-310)."""
     return _compress(data, 5, Null(), True)
+
+
+@functools.lru_cache(maxsize=None)
+def model_results():
+    """level -> (list of (input, stream, counters)) over the encoder inputs and the chain inputs of tests/streams.py;
+    computed once per process (the GPU tests use the same streams as expected bytes)."""
+    import streams
+    inputs = streams.encoder_inputs() + streams.chain_inputs()
+    res = {}
+    for level in (2, 3):
+        rows = []
+        for x in inputs:
+            out = compress(x, level)
+            rows.append((x, out, dict(last_counters)))
+        res[level] = rows
+    return res

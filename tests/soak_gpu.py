@@ -271,7 +271,6 @@ def cut_round(seed):
 def resume_round(seed):
     """fdh_inflate_batch_resumable: random streams, the input and the slot growing in random steps, some of them
     damaged: the last call's status, length, checksum and bytes are those of one call on the whole stream."""
-    import test_gpu_resume as tr
     import gpu_harness
     r = np.random.default_rng(seed)
     comps, caps = [], []
@@ -286,7 +285,7 @@ def resume_round(seed):
     steps = int(r.integers(2, 7))
     in_cuts = [sorted(int(x) for x in r.integers(1, len(c) + 1, steps - 1)) + [len(c)] for c in comps]
     out_cuts = [sorted(int(x) for x in r.integers(1, cap + 1, steps - 1)) + [cap] for cap in caps]
-    (ln, st, ad), outs, guards, _ = tr._drive(fd, comps, in_cuts, out_cuts)
+    (ln, st, ad), outs, guards, _ = gpu_harness.drive_resumable(fd, comps, in_cuts, out_cuts)
     assert guards, (seed, "guard")
     for i, c in enumerate(comps):
         est, eout, ead = ob.decompress_bounded(c, caps[i])

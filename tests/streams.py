@@ -439,3 +439,67 @@ def pack_exact(blobs):
     for i, b in enumerate(blobs):
         buf[int(off[i]):int(off[i + 1])] = np.frombuffer(b, dtype=np.uint8)
     return buf, off
+
+
+# ---- inputs of the encoders ----
+
+def encoder_inputs():
+    """The inputs of the general encoder's tests (level 1, RLE, and the levels above them)."""
+    r = np.random.default_rng(7)
+    out = [b"", b"a", b"Hello world!", bytes(2048), bytes([5]) * 2048, bytes([128]) * 2048, bytes([254]) * 2048,
+           bytes(r.integers(0, 256, 2048, dtype=np.uint8)), bytes(r.integers(0, 5, 50000, dtype=np.uint8)),
+           b"abcdefgh" * 5000, bytes(range(256)) * 300, bytes(7), bytes(8), bytes(9), bytes(265), bytes(266), bytes(267)]
+    for i in (0, 7, 15):
+        out.append(synth.gen_stream_np(i, 65536).tobytes())
+    out.append(bytes(r.integers(0, 3, 300000, dtype=np.uint8)))      # > 16384 symbols: several blocks
+    out.append(bytes(r.integers(0, 256, 70000, dtype=np.uint8)))     # incompressible, skip-ahead path
+    out.extend(length_limited_inputs())
+    return out
+
+
+def length_limited_inputs():
+    """Inputs whose Huffman trees come out deeper than the format allows, so that
+    build_huffman_tree has to shorten them (bitstream.rs:262-305): [0] the literal/length tree
+    (Fibonacci frequencies, interleaved with other bytes so that nothing repeats into a match),
+    [1] the code-length tree (counts per code length that are Fibonacci-like)."""
+    fib = [1, 1]
+    while len(fib) < 20:
+        fib.append(fib[-1] + fib[-2])
+    r = np.random.default_rng(11)
+    a = np.concatenate([np.full(f, k, dtype=np.uint8) for k, f in enumerate(fib)])
+    r.shuffle(a)
+    both = np.empty(2 * a.size, dtype=np.uint8)
+    both[0::2] = a
+    both[1::2] = r.integers(100, 104, a.size, dtype=np.uint8)
+    parts, sym = [], 0
+    for count, freq in ((34, 256), (21, 128), (13, 64), (8, 32), (5, 16), (3, 8), (2, 4), (1, 2), (1, 1)):
+        for _ in range(count):
+            parts.append(np.full(freq, sym, dtype=np.uint8))
+            sym += 1
+    cl = np.concatenate(parts)
+    np.random.default_rng(5).shuffle(cl)
+    return [both.tobytes(), cl.tobytes()]
+
+
+def chain_inputs():
+    """Inputs that drive the hash-chain search through all of its exits (seeds fixed): low-entropy noise
+    over 3 and 4 symbols (long chains, the depth exit, candidates at exactly ip - 32768; the 300 000-byte
+    ones also write more than 32 KiB in the first pass, so the second pass starts past 0), words with
+    short gaps (nice_length at level 3), the same cut short behind two words (end of data), and two
+    periodic streams (nice_length at level 2)."""
+    out = []
+    for seed in (5, 9):
+        r = np.random.default_rng(seed)
+        for a in (3, 4):
+            for n in (120000, 300000):
+                out.append(bytes(r.integers(0, a, n, dtype=np.uint8)))
+    r = np.random.default_rng(9)
+    w = [bytes(r.integers(0, 256, 12, dtype=np.uint8)) for _ in range(6)]
+    bb = bytearray()
+    for _ in range(9000):
+        bb += w[int(r.integers(0, 6))] + bytes(r.integers(0, 256, int(r.integers(0, 3)), dtype=np.uint8))
+    out.append(bytes(bb))
+    out.append(bytes(bb[:5000]) + w[0] + w[1])
+    out.append(b"abcdefgh" * 5000)
+    out.append(bytes(range(256)) * 300)
+    return out

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+import abi_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -28,10 +30,6 @@ def test_library_exports_every_declared_symbol():
     assert L.fdh_ultrafast_bound(0) == 60 and L.fdh_ultrafast_bound(65536) == 98364
 
 
-_SCALARS = {"uint64_t": "u64", "uint32_t": "u32", "size_t": "size", "int": "int"}
-_POINTEE_BYTES = {"uint8_t": 1, "uint32_t": 4, "uint64_t": 8, "fdh_png_info": 4, "fdh_resume_point": 4}
-
-
 def _declared_prototypes():
     """{symbol: (result, [parameter, ...])} as the header spells them, comments and preprocessor lines taken out."""
     text = open(os.path.join(ROOT, "include", "fdeflate_hip.h")).read()
@@ -43,13 +41,6 @@ def _declared_prototypes():
         params = [" ".join(p.split()) for p in params.split(",")]
         protos[name] = (" ".join(result.split()), [] if params == ["void"] else params)
     return protos
-
-
-def _pointee(param):
-    """The type a pointer parameter points to, or None for a scalar one."""
-    if "*" not in param and "[" not in param:
-        return None
-    return re.match(r"(?:const )?(\w+)", param).group(1)
 
 
 def test_signature_table_agrees_with_the_header():
@@ -64,16 +55,16 @@ def test_signature_table_agrees_with_the_header():
         if "*" in result:
             assert t_result == ("str" if result == "const char *" else "host"), name
         else:
-            assert t_result == ("void" if result == "void" else _SCALARS[result]), name
+            assert t_result == ("void" if result == "void" else abi_header.SCALARS[result]), name
         assert len(t_params) == len(params), name
         for pos, (token, param) in enumerate(zip(t_params, params)):
             where = "%s, parameter %d (%s)" % (name, pos, param)
-            pointee = _pointee(param)
+            pointee = abi_header.pointee(param)
             if pointee is None:
-                assert token == _SCALARS[param.split()[0]], where
+                assert token == abi_header.SCALARS[param.split()[0]], where
             elif token in _lib.DEVICE_WIDTH:
                 assert param.count("*") == 1 and "[" not in param, where
-                assert _lib.DEVICE_WIDTH[token] == _POINTEE_BYTES[pointee], where
+                assert _lib.DEVICE_WIDTH[token] == abi_header.POINTEE_BYTES[pointee], where
             else:
                 assert token == ("stream" if param == "void *hip_stream" else "host"), where   # exempt from the widths
         assert ("stream" in t_params) == (t_params[-1:] == ("stream",)) == (params[-1:] == ["void *hip_stream"]), name

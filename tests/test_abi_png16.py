@@ -6,9 +6,9 @@ import re
 import subprocess
 import sys
 
-import test_abi as ta
+import abi_header
 
-ROOT = ta.ROOT
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fdeflate_hip_png16.h")
 SYMBOLS = ("fdh_png_expand16_batch", "fdh_png_expand16_mixed_batch", "fdh_png_pack16_batch")
 
@@ -39,16 +39,16 @@ def test_extension_table_agrees_with_the_header():
     assert set(protos) == set(_lib.EXTENSION_SIGNATURES) == set(SYMBOLS)
     for name, (result, params) in protos.items():
         t_result, t_params = _lib.EXTENSION_SIGNATURES[name]
-        assert "*" not in result and t_result == ta._SCALARS[result], name
+        assert "*" not in result and t_result == abi_header.SCALARS[result], name
         assert len(t_params) == len(params), name
         for pos, (token, param) in enumerate(zip(t_params, params)):
             where = "%s, parameter %d (%s)" % (name, pos, param)
-            pointee = ta._pointee(param)
+            pointee = abi_header.pointee(param)
             if pointee is None:
-                assert token == ta._SCALARS[param.split()[0]], where
+                assert token == abi_header.SCALARS[param.split()[0]], where
             elif token in _lib.DEVICE_WIDTH:
                 assert param.count("*") == 1 and "[" not in param, where
-                assert _lib.DEVICE_WIDTH[token] == ta._POINTEE_BYTES[pointee], where
+                assert _lib.DEVICE_WIDTH[token] == abi_header.POINTEE_BYTES[pointee], where
             else:
                 assert token == ("stream" if param == "void *hip_stream" else "host"), where
         assert ("stream" in t_params) == (t_params[-1:] == ("stream",)) == (params[-1:] == ["void *hip_stream"]), name

@@ -1,7 +1,7 @@
 """-m gpu: encoder levels 2 and 3 (GreedyParser + HashChainMatchFinder) on the GPU against
 tests/level_model.py, bit-exact.  The oracle has no chain finder; the model is pinned against the oracle at
-level 1 and RLE by tests/test_level_model.py, whose input set (and model results, computed once per process)
-this file shares."""
+level 1 and RLE by tests/test_level_model.py; the input set (tests/streams.py) and the model's results
+(level_model.model_results, computed once per process) are the ones that file checks."""
 import ctypes as C
 import os
 import time
@@ -12,7 +12,6 @@ import pytest
 import level_model as lm
 import oracle_binding as ob
 import streams
-from test_level_model import chain_inputs, model_results
 
 pytestmark = pytest.mark.gpu
 
@@ -47,7 +46,7 @@ def cases():
     ragged = _ragged()
     res = {}
     for level in (2, 3):
-        rows = model_results()[level]
+        rows = lm.model_results()[level]
         res[level] = ([x for x, _, _ in rows] + ragged, [o for _, o, _ in rows] + [lm.compress(x, level) for x in ragged])
     return res
 

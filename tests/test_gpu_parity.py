@@ -1045,8 +1045,7 @@ def test_general_encoder_level1_and_rle_bit_exact(harness):
     picks by batch size otherwise)."""
     import torch
     import fdeflate_amd as fd
-    from test_oracle_golden import _encoder_inputs
-    raws = _encoder_inputs()
+    raws = streams.encoder_inputs()
     r = np.random.default_rng(17)
     for k in range(70):   # more than one wavefront of streams, ragged sizes
         n = int(r.integers(0, 9000))

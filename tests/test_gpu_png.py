@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import oracle_binding as ob
+import png_gpu_harness as gh
 import png_model
 import streams
 
@@ -36,39 +37,8 @@ FILL = 0xEE
 ENV = ("FDH_PNG_LANE_PER_IMAGE", "FDH_PNG_NO_PIPELINE", "FDH_PNG_IMAGES_PER_WAVE")
 
 
-def widths_of(bpp, n):
-    """The smallest and the largest multiple of bpp in (16 (n - 1), 16 n]: a partial and a full(est) last chunk."""
-    lo, hi = 16 * (n - 1), 16 * n
-    small, large = (lo // bpp + 1) * bpp, hi // bpp * bpp
-    assert lo < small < large <= hi and (small + 15) // 16 == n == (large + 15) // 16
-    return small, large
-
-
-def widths_above(bpp):
-    first = (GATE // bpp + 1) * bpp
-    assert first > GATE and first - bpp <= GATE
-    return first, 5760, 15360
-
-
 def _choose(monkeypatch, per_lane=None, no_pipe=None, per_wave=None):
-    for name, val in zip(ENV, (per_lane, no_pipe, per_wave)):
-        if val is None:
-            monkeypatch.delenv(name, raising=False)
-        else:
-            monkeypatch.setenv(name, str(val))
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _offsets(sizes, front, slack):
-    """Slot i holds sizes[i] + slack[i] bytes; the first one starts `front` bytes into the buffer."""
-    off = np.zeros(len(sizes) + 1, dtype=np.int64)
-    off[0] = front
-    off[1:] = front + np.cumsum(np.asarray(sizes, dtype=np.int64) + np.asarray(slack, dtype=np.int64))
-    return off
+    gh.set_env(monkeypatch, **dict(zip(ENV, (per_lane, no_pipe, per_wave))))
 
 
 class Batch:
@@ -93,10 +63,10 @@ class Batch:
         n = self.n
         slack = [2 * (i % 5) + 1 for i in range(n)]
         zero = [0] * n
-        self.src_p_off = _offsets([len(p) for p in self.pix], 3, zero)
-        self.src_f_off = _offsets([len(f) for f in self.filt], 5, zero)
-        self.dst_p_off = _offsets([len(p) for p in self.pix], 7, slack)
-        self.dst_f_off = _offsets([len(f) for f in self.filt], 9, slack)
+        self.src_p_off = gh.offsets([len(p) for p in self.pix], 3, zero)
+        self.src_f_off = gh.offsets([len(f) for f in self.filt], 5, zero)
+        self.dst_p_off = gh.offsets([len(p) for p in self.pix], 7, slack)
+        self.dst_f_off = gh.offsets([len(f) for f in self.filt], 9, slack)
         tbuf, toff = streams.pack_exact(self.types)
         self.tbuf = tbuf if tbuf.size else np.zeros(1, dtype=np.uint8)
         self.toff = toff.astype(np.int64)
@@ -123,7 +93,7 @@ def _first_diff(got, want, off):
 def _run_unfilter(fd, b, faults, what, status=None):
     import torch
     d_p = torch.full((b.want_p.size,), FILL, dtype=torch.uint8, device="cuda")
-    st = fd.png_unfilter_batch(_dev(b.src_f), _dev(b.src_f_off), d_p, _dev(b.dst_p_off), b.rb, b.bpp)
+    st = fd.png_unfilter_batch(gh.dev(b.src_f), gh.dev(b.src_f_off), d_p, gh.dev(b.dst_p_off), b.rb, b.bpp)
     torch.cuda.synchronize()
     got = d_p.cpu().numpy()
     if st.cpu().tolist() != (status or [0] * b.n):
@@ -136,7 +106,7 @@ def _run_unfilter(fd, b, faults, what, status=None):
 def _run_filter(fd, b, faults, what):
     import torch
     d_f = torch.full((b.want_f.size,), FILL, dtype=torch.uint8, device="cuda")
-    st = fd.png_filter_batch(_dev(b.src_p), _dev(b.src_p_off), _dev(b.tbuf), _dev(b.toff), d_f, _dev(b.dst_f_off), b.rb, b.bpp)
+    st = fd.png_filter_batch(gh.dev(b.src_p), gh.dev(b.src_p_off), gh.dev(b.tbuf), gh.dev(b.toff), d_f, gh.dev(b.dst_f_off), b.rb, b.bpp)
     torch.cuda.synchronize()
     got = d_f.cpu().numpy()
     if st.cpu().tolist() != [0] * b.n:
@@ -161,7 +131,7 @@ def test_row_width_classes_through_every_kernel(bpp, monkeypatch):
     assert torch.cuda.is_available()
     t0 = time.time()
     r = np.random.default_rng(4100 + bpp)
-    widths = [(n, w) for n in PIPE_CHUNKS for w in widths_of(bpp, n)] + [(0, w) for w in widths_above(bpp)]
+    widths = [(n, w) for n in PIPE_CHUNKS for w in gh.widths_of(bpp, n)] + [(0, w) for w in gh.widths_above(bpp, GATE)]
     assert max(w for n, w in widths if n) == GATE // bpp * bpp       # the pipeline's last width
     faults, runs = [], 0
     for k, (n, rb) in enumerate(widths):
@@ -243,8 +213,8 @@ def test_fused_decode_of_mixed_streams_at_real_widths(bpp, monkeypatch):
             _choose(monkeypatch, per_wave=per_wave)
             d_f = torch.zeros(int(foff[-1]), dtype=torch.uint8, device="cuda")
             d_p = torch.full((b.want_p.size,), FILL, dtype=torch.uint8, device="cuda")
-            out_len, status, adler, pst = fd.inflate_png_batch(_dev(cbuf), _dev(coff.astype(np.int64)), d_f, _dev(foff),
-                                                               d_p, _dev(b.dst_p_off), rb, bpp)
+            out_len, status, adler, pst = fd.inflate_png_batch(gh.dev(cbuf), gh.dev(coff.astype(np.int64)), d_f, gh.dev(foff),
+                                                               d_p, gh.dev(b.dst_p_off), rb, bpp)
             torch.cuda.synchronize()
             stl, psl = status.cpu().numpy().view(np.uint32), pst.cpu().tolist()
             oll, adl = out_len.cpu().numpy().view(np.uint32), adler.cpu().numpy().view(np.uint32)
@@ -275,7 +245,7 @@ def test_fused_encoder_at_real_widths(bpp):
     import fdeflate_amd as fd
     t0 = time.time()
     r = np.random.default_rng(4400 + bpp)
-    widths = [w for n in (1, 2, 8, 9, 64, 65, 128, 256) for w in widths_of(bpp, n)] + [5760, 15360, 131072]
+    widths = [w for n in (1, 2, 8, 9, 64, 65, 128, 256) for w in gh.widths_of(bpp, n)] + [5760, 15360, 131072]
     row_counts = (1, 2, 5, 64, 130)
     for rb in widths:
         pixs, types, want = [], [], []
@@ -294,11 +264,11 @@ def test_fused_encoder_at_real_widths(bpp):
         pbuf, poff = streams.pack_exact(pixs)
         tbuf, toff = streams.pack_exact(types)
         caps = [int(fd.ultrafast_bound(rows * (rb + 1))) for rows in row_counts]
-        ooff = _offsets(caps, 7, [2 * i + 1 for i in range(len(caps))])
+        ooff = gh.offsets(caps, 7, [2 * i + 1 for i in range(len(caps))])
         expect = Batch._image(ooff, want, FILL, 33)
         d_out = torch.full((expect.size,), FILL, dtype=torch.uint8, device="cuda")
-        ol, st = fd.png_filter_deflate_ultrafast_batch(_dev(pbuf), _dev(poff.astype(np.int64)), _dev(tbuf), _dev(toff.astype(np.int64)),
-                                                       d_out, _dev(ooff), rb, bpp)
+        ol, st = fd.png_filter_deflate_ultrafast_batch(gh.dev(pbuf), gh.dev(poff.astype(np.int64)), gh.dev(tbuf), gh.dev(toff.astype(np.int64)),
+                                                       d_out, gh.dev(ooff), rb, bpp)
         torch.cuda.synchronize()
         assert st.cpu().tolist() == [0] * len(caps), (bpp, rb, st.cpu().tolist())
         assert ol.cpu().tolist() == [len(w) for w in want], (bpp, rb, ol.cpu().tolist(), [len(w) for w in want])
@@ -327,7 +297,7 @@ def _triple_of(at, row):
 
 
 def _same_on_device(torch, d, expected, row):
-    e = _dev(expected.reshape(-1))
+    e = gh.dev(expected.reshape(-1))
     if torch.equal(d, e):
         return None
     return _triple_of(int((d != e).nonzero()[0]), row)
@@ -356,11 +326,11 @@ def test_every_predictor_triple(ftype, monkeypatch):
         assert ob.png_unfilter(filt[i].tobytes(), rb, 1) == (0, pix[i].tobytes()), i
     # left = a, up = b, up-left = c at the odd bytes of row 1: every triple is there
     assert np.array_equal(filt[:, 1, 2::2].reshape(256, 256, 256)[7, 9], (7 - png_model.predictor(ftype, 7, np.arange(256), 9)) & 0xFF)
-    poff = _dev(np.arange(n + 1, dtype=np.int64) * (2 * rb))
-    foff = _dev(np.arange(n + 1, dtype=np.int64) * (2 * (rb + 1)))
-    toff = _dev(np.arange(n + 1, dtype=np.int64) * 2)
-    d_types = _dev(np.tile(types, n))
-    d_pix, d_filt = _dev(pix.reshape(-1)), _dev(filt.reshape(-1))
+    poff = gh.dev(np.arange(n + 1, dtype=np.int64) * (2 * rb))
+    foff = gh.dev(np.arange(n + 1, dtype=np.int64) * (2 * (rb + 1)))
+    toff = gh.dev(np.arange(n + 1, dtype=np.int64) * 2)
+    d_types = gh.dev(np.tile(types, n))
+    d_pix, d_filt = gh.dev(pix.reshape(-1)), gh.dev(filt.reshape(-1))
     # filter
     out = torch.full((n * 2 * (rb + 1),), FILL, dtype=torch.uint8, device="cuda")
     st = fd.png_filter_batch(d_pix, poff, d_types, toff, out, foff, rb, 1)
@@ -373,7 +343,7 @@ def test_every_predictor_triple(ftype, monkeypatch):
     assert torch.equal(out, d_pix), ("unfilter", _same_on_device(torch, out, pix, rb))
     # the fused encoder, decoded again
     bound = (int(fd.ultrafast_bound(2 * (rb + 1))) + 15) & ~15
-    coff = _dev(np.arange(n + 1, dtype=np.int64) * bound)
+    coff = gh.dev(np.arange(n + 1, dtype=np.int64) * bound)
     comp = torch.zeros(n * bound, dtype=torch.uint8, device="cuda")
     clen, pst = fd.png_filter_deflate_ultrafast_batch(d_pix, poff, d_types, toff, comp, coff, rb, 1)
     assert int(pst.abs().sum()) == 0

@@ -17,11 +17,12 @@ import pytest
 
 import png16_model as m16
 import png_adam7_model as am
+import png_corpus as pc
 import png_expand_model as em
 import png_file_model as fm
+import png_gpu_harness as gh
 import png_mixed_model as mm
-import test_png_expand_model as xm
-from test_gpu_png_expand import BAND, GUARD, HEIGHTS, PASSED_ON, WIDTHS, _batch_of, _dev, _words
+from png_gpu_harness import GUARD, HEIGHTS, PASSED_ON
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +33,6 @@ DEPTH16 = (0, 2, 4, 6)
 def _p16():
     import fdeflate_amd.png16 as p16
     return p16
-
-
-def _waves(monkeypatch, name, waves):
-    monkeypatch.setenv(name, str(waves))
 
 
 def _slots(sizes, starts=STARTS):
@@ -82,14 +79,14 @@ class Batch16:
 
     def check(self, what):
         import torch
-        d_pix = _dev(self.pix)
+        d_pix = gh.dev(self.pix)
         rgba = torch.full((self.expect.size,), GUARD, dtype=torch.uint8, device="cuda")
         assert rgba.data_ptr() % 16 == 0
         st = torch.full((self.n + 16,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-        _p16().png_expand16_batch(d_pix, _dev(self.p_off), rgba, _dev(self.r_off), *self.geometry,
-                                  pal=None if self.pal is None else _words(self.pal),
-                                  colour=None if self.colour is None else _words(self.colour),
-                                  upstream=_words(self.upstream), png_status=st[8:8 + self.n])
+        _p16().png_expand16_batch(d_pix, gh.dev(self.p_off), rgba, gh.dev(self.r_off), *self.geometry,
+                                  pal=None if self.pal is None else gh.words(self.pal),
+                                  colour=None if self.colour is None else gh.words(self.colour),
+                                  upstream=gh.words(self.upstream), png_status=st[8:8 + self.n])
         torch.cuda.synchronize()
         assert np.array_equal(d_pix.cpu().numpy(), self.pix)
         st = st.cpu().numpy()
@@ -105,17 +102,17 @@ class Batch16:
 
 @pytest.mark.parametrize("pair", fm.PAIRS, ids=["depth%d-colour%d" % p for p in fm.PAIRS])
 def test_expand16_every_width_and_height(pair, monkeypatch):
-    """Every width of WIDTHS at heights 1, 2, 3 and one more than a band, one batch per width: the output buffer equals
+    """Every width of gh.EXPAND_WIDTHS at heights 1, 2, 3 and one more than a band, one batch per width: the output buffer equals
     the model's byte for byte, guard slots and the bytes behind the last slot included, and every status is right.  The
     slots start at 0, 2, 8 and 10 mod 16.  Each batch runs with one wavefront per image (a wavefront takes two bands)
     and with seven (more wavefronts than bands)."""
     depth, colour = pair
     r = np.random.default_rng(16500 + 64 * colour + depth)
-    for width in WIDTHS:
-        b = Batch16([xm.random_case(r, width, h, depth, colour, colour == 3) for h in HEIGHTS], width, depth, colour)
+    for width in gh.EXPAND_WIDTHS:
+        b = Batch16([pc.random_case(r, width, h, depth, colour, colour == 3) for h in HEIGHTS], width, depth, colour)
         assert [int(o) % 16 for o in b.r_off[0::2][:4]] == [0, 2, 8, 10]
         for waves in (1, 7):
-            _waves(monkeypatch, "FDH_PNG_EXPAND16_WAVES", waves)
+            gh.set_env(monkeypatch, FDH_PNG_EXPAND16_WAVES=waves)
             b.check((pair, width, waves))
 
 
@@ -126,7 +123,7 @@ def test_keys_present_and_absent(pair, monkeypatch):
     depth, colour = pair
     r = np.random.default_rng(16600 + 64 * colour + depth)
     for width in (1, 2, 5, 33, 64, 257):
-        images = [xm.random_case(r, width, h, depth, colour, k % 2 == 0) for k, h in enumerate((3, 3, BAND + 1, 2, 5))]
+        images = [pc.random_case(r, width, h, depth, colour, k % 2 == 0) for k, h in enumerate((3, 3, gh.BAND + 1, 2, 5))]
         b = Batch16(images, width, depth, colour)
         for k, w in enumerate(b.want):
             alpha = w.view("<u2")[3::4]
@@ -139,7 +136,7 @@ def test_keys_present_and_absent(pair, monkeypatch):
             alpha = b.want[2].view("<u2")[3::4]
             assert all(alpha[j] == 65535 for j, hit in enumerate(near) if hit)
         for waves in (1, 7):
-            _waves(monkeypatch, "FDH_PNG_EXPAND16_WAVES", waves)
+            gh.set_env(monkeypatch, FDH_PNG_EXPAND16_WAVES=waves)
             b.check((pair, width, waves))
 
 
@@ -169,7 +166,7 @@ def test_palette_sizes_and_an_index_outside(depth, monkeypatch):
         b = Batch16(images, width, depth, 3)
         assert b.want_status[0::2] == [9 if outside else 0 for _, outside in cases]
         for waves in (1, 7):
-            _waves(monkeypatch, "FDH_PNG_EXPAND16_WAVES", waves)
+            gh.set_env(monkeypatch, FDH_PNG_EXPAND16_WAVES=waves)
             b.check((depth, width, waves))
 
 
@@ -213,10 +210,10 @@ def test_slots_that_do_not_fit_misaligned_slots_and_upstream():
         assert odd == 1
         rgba = torch.full((expect.size,), GUARD, dtype=torch.uint8, device="cuda")
         n = len(entries)
-        st = _p16().png_expand16_batch(_dev(pix), _dev(p_off), rgba, _dev(r_off), width, depth, colour,
-                                       pal=_words([em.pal_words(pal)] * n) if pal else None,
-                                       colour=_words([em.colour_words(256, None)] * n) if pal else None,
-                                       upstream=_words([e[2] for e in entries]))
+        st = _p16().png_expand16_batch(gh.dev(pix), gh.dev(p_off), rgba, gh.dev(r_off), width, depth, colour,
+                                       pal=gh.words([em.pal_words(pal)] * n) if pal else None,
+                                       colour=gh.words([em.colour_words(256, None)] * n) if pal else None,
+                                       upstream=gh.words([e[2] for e in entries]))
         torch.cuda.synchronize()
         assert st.cpu().numpy().view(np.uint32).tolist() == [e[3] for e in entries], (depth, colour)
         assert np.array_equal(rgba.cpu().numpy(), expect), (depth, colour)
@@ -238,9 +235,9 @@ def test_more_images_than_wavefronts_fill():
         per = [em.expand(pix[p_off[k]:p_off[k + 1]], width, depth, colour, None, pal)[1] for k in range(n)]   # (statuses: the same in both models)
         assert (want_st == 9) == (colour == 3) and (colour != 3 or 0 in per)
         rgba = torch.full((int(r_off[-1]) + 16,), GUARD, dtype=torch.uint8, device="cuda")
-        st = _p16().png_expand16_batch(_dev(pix), _dev(p_off), rgba, _dev(r_off), width, depth, colour,
-                                       pal=_words([em.pal_words(pal)] * n) if pal else None,
-                                       colour=_words([em.colour_words(3, None)] * n) if pal else None)
+        st = _p16().png_expand16_batch(gh.dev(pix), gh.dev(p_off), rgba, gh.dev(r_off), width, depth, colour,
+                                       pal=gh.words([em.pal_words(pal)] * n) if pal else None,
+                                       colour=gh.words([em.colour_words(3, None)] * n) if pal else None)
         torch.cuda.synchronize()
         got = rgba.cpu().numpy()
         assert st.cpu().tolist() == per
@@ -282,7 +279,7 @@ def _mixed_call(images, with_pal=True, short=()):
     for k, (_, pix, _, _) in enumerate(images):
         host[p_off[2 * k]:p_off[2 * k + 1]] = pix
     guard_rec = mm.record(3, 2, 8, 0)
-    info = _words([w for rec, _, _, _ in images for w in (mm.words(rec), mm.words(guard_rec))]).view(-1, 8)
+    info = gh.words([w for rec, _, _, _ in images for w in (mm.words(rec), mm.words(guard_rec))]).view(-1, 8)
     pal = np.full((2 * n, 256), 0x5A5A5A5A, dtype=np.uint32)
     col = np.zeros((2 * n, 4), dtype=np.uint32)
     for k, (_, _, c, p) in enumerate(images):
@@ -291,8 +288,8 @@ def _mixed_call(images, with_pal=True, short=()):
             pal[2 * k] = p
     rgba = torch.full((int(r_off[-1]) + 48,), GUARD, dtype=torch.uint8, device="cuda")
     st = torch.full((2 * n + 16,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-    _p16().png_expand16_mixed_batch(_dev(host), _dev(p_off), rgba, _dev(r_off), info, pal=_dev(pal.view(np.int32)) if with_pal else None,
-                                    colour=_dev(col.view(np.int32)), upstream=_words([0, PASSED_ON] * n), png_status=st[8:8 + 2 * n])
+    _p16().png_expand16_mixed_batch(gh.dev(host), gh.dev(p_off), rgba, gh.dev(r_off), info, pal=gh.dev(pal.view(np.int32)) if with_pal else None,
+                                    colour=gh.dev(col.view(np.int32)), upstream=gh.words([0, PASSED_ON] * n), png_status=st[8:8 + 2 * n])
     torch.cuda.synchronize()
     st, got = st.cpu().numpy(), rgba.cpu().numpy()
     assert (st[:8] == 0x5A5A5A5A).all() and (st[8 + 2 * n:] == 0x5A5A5A5A).all()
@@ -306,7 +303,7 @@ def _mixed_call(images, with_pal=True, short=()):
 
 def _mixed_image(r, width, height, depth, colour, k):
     rec = mm.record(width, height, depth, colour, idat_bytes=9)
-    pix, key, pal = xm.random_case(r, width, height, depth, colour, k % 2 == 0, entries=(1, 2, 1 << depth)[k % 3] if colour == 3 else None)
+    pix, key, pal = pc.random_case(r, width, height, depth, colour, k % 2 == 0, entries=(1, 2, 1 << depth)[k % 3] if colour == 3 else None)
     if colour == 3:
         return rec, pix, em.colour_words(len(pal), None), np.array(em.pal_words(pal), dtype=np.uint32)
     return rec, pix, em.colour_words(0, key), None
@@ -319,12 +316,12 @@ def test_mixed_batch_every_pair_shuffled(monkeypatch):
     r = np.random.default_rng(17000)
     images, k = [], 0
     for depth, colour in fm.PAIRS:
-        for width, height in ((1, 1), (3, 2), (7, BAND + 1), (33, 3), (64, 2), (257, 1)):
+        for width, height in ((1, 1), (3, 2), (7, gh.BAND + 1), (33, 3), (64, 2), (257, 1)):
             images.append(_mixed_image(r, width, height, depth, colour, k))
             k += 1
     images = [images[j] for j in r.permutation(len(images))]
     for waves in (1, 7):
-        _waves(monkeypatch, "FDH_PNG_EXPAND16_WAVES", waves)
+        gh.set_env(monkeypatch, FDH_PNG_EXPAND16_WAVES=waves)
         st, slots, want = _mixed_call(images)
         for j, (w, s, got) in enumerate(zip(want, st, slots)):
             assert s == w[1] and got == w[0], (j, images[j][0])
@@ -333,8 +330,8 @@ def test_mixed_batch_every_pair_shuffled(monkeypatch):
     for j, (rec, pix, col, pal) in enumerate(images):
         out = torch.full((len(slots[j]) + 16,), GUARD, dtype=torch.uint8, device="cuda")
         off = np.array([0, len(slots[j])], dtype=np.int64)
-        alone = _p16().png_expand16_batch(_dev(pix), _dev(np.array([0, pix.size], dtype=np.int64)), out, _dev(off), rec["width"], rec["bit_depth"],
-                                          rec["colour_type"], pal=_words([pal.tolist()]) if pal is not None else None, colour=_words([col]))
+        alone = _p16().png_expand16_batch(gh.dev(pix), gh.dev(np.array([0, pix.size], dtype=np.int64)), out, gh.dev(off), rec["width"], rec["bit_depth"],
+                                          rec["colour_type"], pal=gh.words([pal.tolist()]) if pal is not None else None, colour=gh.words([col]))
         assert alone.cpu().tolist() == [st[j]] and out.cpu().numpy()[:len(slots[j])].tobytes() == slots[j], (j, rec)
 
 
@@ -392,12 +389,12 @@ def _pack_call(pictures, width, colour, upstream=None, starts=STARTS, slack=0):
     for k, s in enumerate(sizes):
         o_off += [o_off[-1] + s, o_off[-1] + s + 3 + k % 4]
     o_off = np.asarray(o_off, dtype=np.int64)
-    d_in = _dev(host)
+    d_in = gh.dev(host)
     assert d_in.data_ptr() % 16 == 0
     out = torch.full((int(o_off[-1]) + 32,), GUARD, dtype=torch.uint8, device="cuda")
     st = torch.full((2 * n + 16,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     up = [v for u in (upstream or [0] * n) for v in (u, PASSED_ON)]
-    _p16().png_pack16_batch(d_in, _dev(s_off), out, _dev(o_off), width, colour, upstream=_words(up), png_status=st[8:8 + 2 * n])
+    _p16().png_pack16_batch(d_in, gh.dev(s_off), out, gh.dev(o_off), width, colour, upstream=gh.words(up), png_status=st[8:8 + 2 * n])
     torch.cuda.synchronize()
     assert np.array_equal(d_in.cpu().numpy(), host)
     st, got = st.cpu().numpy(), out.cpu().numpy()
@@ -412,17 +409,17 @@ def _pack_call(pictures, width, colour, upstream=None, starts=STARTS, slack=0):
 
 @pytest.mark.parametrize("colour", DEPTH16)
 def test_pack16_every_width_and_height(colour, monkeypatch):
-    """Representable pictures of every width of WIDTHS at heights 1, 2, 3 and one more than a band, between guards, the
+    """Representable pictures of every width of gh.EXPAND_WIDTHS at heights 1, 2, 3 and one more than a band, between guards, the
     RGBA16 slots starting at 0, 2, 8 and 10 mod 16: the packed bytes are the model's, and fdh_png_expand16_batch takes
     them back to the pictures."""
     import torch
     r = np.random.default_rng(17200 + colour)
-    for width in WIDTHS:
+    for width in gh.EXPAND_WIDTHS:
         pictures = [_representable(r, width * h, colour) for h in HEIGHTS]
         want = [m16.pack16(p.tobytes(), width, colour) for p in pictures]
         assert all(w[1] == 0 for w in want)
         for waves in (1, 7):
-            _waves(monkeypatch, "FDH_PNG_PACK16_WAVES", waves)
+            gh.set_env(monkeypatch, FDH_PNG_PACK16_WAVES=waves)
             st, slots = _pack_call(pictures, width, colour)
             assert st == [0] * len(pictures), (width, waves)
             for k, (s, w) in enumerate(zip(slots, want)):
@@ -431,7 +428,7 @@ def test_pack16_every_width_and_height(colour, monkeypatch):
         p_off = np.concatenate([[0], np.cumsum([s.size for s in slots])]).astype(np.int64)
         r_off = np.concatenate([[0], np.cumsum([p.size for p in pictures])]).astype(np.int64)
         back = torch.empty(int(r_off[-1]), dtype=torch.uint8, device="cuda")
-        st = _p16().png_expand16_batch(_dev(packed), _dev(p_off), back, _dev(r_off), width, 16, colour)
+        st = _p16().png_expand16_batch(gh.dev(packed), gh.dev(p_off), back, gh.dev(r_off), width, 16, colour)
         assert st.cpu().tolist() == [0] * len(pictures) and np.array_equal(back.cpu().numpy(), np.concatenate(pictures)), width
 
 
@@ -442,7 +439,7 @@ def test_pack16_every_reason_for_status_13_status_2_and_upstream():
     2, nothing written.  An upstream value is passed on."""
     import torch
     r = np.random.default_rng(17300)
-    width, rows = 13, BAND + 2
+    width, rows = 13, gh.BAND + 2
     n = width * rows
     reasons = {0: ((1, 1), (2, 1), (1, 0x100), (3, -1), (3, -0xFF00)), 4: ((1, 1), (2, 1), (2, 0x100)), 2: ((3, -1), (3, -0xFF00), (3, -65535))}
     for colour, cases in reasons.items():
@@ -475,7 +472,7 @@ def test_pack16_every_reason_for_status_13_status_2_and_upstream():
         s_off = np.concatenate([[0], np.cumsum([p.size for p in half])]).astype(np.int64)
         o_off = s_off // 8 * 2 * fm.CHANNELS[colour]
         out = torch.full((int(o_off[-1]) + 8,), GUARD, dtype=torch.uint8, device="cuda")
-        st = p16.png_pack16_batch(_dev(np.concatenate(half)), _dev(s_off), out, _dev(o_off), width, colour)
+        st = p16.png_pack16_batch(gh.dev(np.concatenate(half)), gh.dev(s_off), out, gh.dev(o_off), width, colour)
         assert st.cpu().tolist() == [0, 2, 0] and (out.cpu().numpy()[int(o_off[1]):int(o_off[2])] == GUARD).all()
 
 
@@ -504,13 +501,13 @@ def _pillow_grey16(png):
 def _model_file(r, width, height, depth, colour, keyed, method=0, idat_chunks=2):
     """(file, RGBA16 bytes by the model) of a model-written file: a tEXt in front, PLTE, tRNS, random filter types."""
     import png_model as pm
-    pix, key, pal = xm.random_case(r, width, height, depth, colour, keyed)
+    pix, key, pal = pc.random_case(r, width, height, depth, colour, keyed)
     rb, bpp = fm.geometry(width, depth, colour)
     if method:
         idat = am.stream_of(pix.tobytes(), width, height, depth, colour, r.integers(0, 5, am.pass_rows(width, height)).tolist())
     else:
         idat = zlib.compress(pm.filter_rows(pix.reshape(height, rb), bpp, r.integers(0, 5, height).tolist()).tobytes())
-    f = am.write_file(idat, width, height, depth, colour, xm.pre_chunks(colour, key, pal, text=True), idat_chunks, zlib.crc32, method=method)
+    f = am.write_file(idat, width, height, depth, colour, pc.pre_chunks(colour, key, pal, text=True), idat_chunks, zlib.crc32, method=method)
     rgba, st = m16.expand16(pix, width, depth, colour, key, pal)
     assert st == 0
     return f, rgba
@@ -528,9 +525,9 @@ def test_files_of_one_geometry_to_rgba16(pair):
     made = [_model_file(r, width, 3, depth, colour, colour in (0, 2, 3)), _model_file(r, width, 70, depth, colour, False),
             _model_file(r, width, 9, depth, colour, False, method=1)]
     heights = (3, 70, 9)
-    host, f_off, f_len = _batch_of([f for f, _ in made])
-    rgba, rgba_off, info, status, png_status = _p16().png_decode_files_rgba16_batch(_dev(host), _dev(f_off), width, depth, colour,
-                                                                                    file_len=_dev(f_len), flags=fd.PNG_FLAG_ADAM7)
+    host, f_off, f_len = gh.batch_of([f for f, _ in made])
+    rgba, rgba_off, info, status, png_status = _p16().png_decode_files_rgba16_batch(gh.dev(host), gh.dev(f_off), width, depth, colour,
+                                                                                    file_len=gh.dev(f_len), flags=fd.PNG_FLAG_ADAM7)
     torch.cuda.synchronize()
     assert status.cpu().tolist() == [0] * 3 and png_status.cpu().tolist() == [0] * 3
     off = rgba_off.cpu().tolist()
@@ -568,8 +565,8 @@ def test_mixed_files_to_rgba16_with_one_read_back_of_48_bytes(mixed_files, kind,
         r = np.random.default_rng(17550)
         mixed_files = [_model_file(r, 21, h, 16, 2, k == 0) + ((21, h),) for k, h in enumerate((4, 30, 5, 12))]
     route = None
-    host, f_off, f_len = _batch_of([f for f, _, _ in mixed_files])
-    d_file, d_off, d_len = _dev(host), _dev(f_off), _dev(f_len)
+    host, f_off, f_len = gh.batch_of([f for f, _, _ in mixed_files])
+    d_file, d_off, d_len = gh.dev(host), gh.dev(f_off), gh.dev(f_len)
     moved, stray = [], []
     inner = api._read_back
     originals = {name: getattr(torch.Tensor, name) for name in ("cpu", "tolist", "item", "numpy")}
@@ -611,8 +608,8 @@ def test_uniform_route_and_max_bytes():
     r = np.random.default_rng(17600)
     width = 21
     made = [_model_file(r, width, h, 16, 2, False) for h in (4, 30, 5, 12)]
-    host, f_off, f_len = _batch_of([f for f, _ in made])
-    d_file, d_off, d_len = _dev(host), _dev(f_off), _dev(f_len)
+    host, f_off, f_len = gh.batch_of([f for f, _ in made])
+    d_file, d_off, d_len = gh.dev(host), gh.dev(f_off), gh.dev(f_len)
     chosen = _p16().png_decode_mixed_files_rgba16_batch(d_file, d_off, d_len)
     forced = _p16().png_decode_mixed_files_rgba16_batch(d_file, d_off, d_len, route="mixed")
     uniform = _p16().png_decode_mixed_files_rgba16_batch(d_file, d_off, d_len, route="uniform")
@@ -652,7 +649,7 @@ def test_rgba16_to_files_and_back(colour):
     slot = (fd.png_file_bound(max(heights), rb) + 15) & ~15
     f_off = torch.arange(len(pictures) + 1, dtype=torch.int64, device="cuda") * slot
     files = torch.full((len(pictures) * slot + 16,), GUARD, dtype=torch.uint8, device="cuda")
-    file_len, st = _p16().png_encode_rgba16_files_batch(_dev(np.concatenate(pictures)), _dev(s_off), files, f_off, width, colour)
+    file_len, st = _p16().png_encode_rgba16_files_batch(gh.dev(np.concatenate(pictures)), gh.dev(s_off), files, f_off, width, colour)
     torch.cuda.synchronize()
     assert st.cpu().tolist() == want_st
     lens, host = file_len.cpu().tolist(), files.cpu().numpy()

@@ -14,26 +14,17 @@ import numpy as np
 import pytest
 
 import png_adam7_model as am
+import png_corpus as pc
 import png_expand_model as em
 import png_file_model as fm
+import png_gpu_harness as gh
 import png_model as pm
-import test_png_adam7_model as ta
-import test_png_expand_model as xm
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 0x5A
 PASSED_ON = 77          # an upstream status (png_status 3): such entries are the guards between the images
 ANY = "any"             # a pix slot whose contents are not specified (status 1)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _i32(values):
-    return _dev(np.asarray(values, dtype=np.uint32).view(np.int32))
 
 
 class Entry:
@@ -72,14 +63,14 @@ def run(fd, entries, geometry, guards=True, method="given", gates=True, front=3)
     filt = np.full(int(f_off[-1]) + 9, GUARD, dtype=np.uint8)
     for o, e in zip(f_off[:-1], seq):
         filt[int(o):int(o) + len(e.filt)] = e.filt
-    d_filt = _dev(filt)
+    d_filt = gh.dev(filt)
     d_pix = torch.full((int(p_off[-1]) + 33,), GUARD, dtype=torch.uint8, device="cuda")
     st = torch.full((n + 16,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     fd.png_unfilter_interlaced_batch(
-        d_filt, _dev(f_off), d_pix, _dev(p_off), *geometry,
-        method=None if method is None else _dev(np.array([e.method for e in seq], dtype=np.uint8)),
-        upstream=_i32([e.upstream for e in seq]) if gates else None,
-        upstream_len=_i32([e.upstream_len for e in seq]) if gates else None, png_status=st[8:8 + n])
+        d_filt, gh.dev(f_off), d_pix, gh.dev(p_off), *geometry,
+        method=None if method is None else gh.dev(np.array([e.method for e in seq], dtype=np.uint8)),
+        upstream=gh.words([e.upstream for e in seq]) if gates else None,
+        upstream_len=gh.words([e.upstream_len for e in seq]) if gates else None, png_status=st[8:8 + n])
     torch.cuda.synchronize()
     st = st.cpu().numpy()
     assert (st[:8] == 0x5A5A5A5A).all() and (st[8 + n:] == 0x5A5A5A5A).all()
@@ -115,7 +106,7 @@ def random_types(r, width, height, force=None):
 def adam7_entry(r, width, height, depth, colour, force=None, types=None):
     """A random picture (padding bits zero), interlaced and filtered by the model."""
     rb = fm.geometry(width, depth, colour)[0]
-    pix = ta.clear_padding(r.integers(0, 256, height * rb, dtype=np.uint8), width, height, depth, colour)
+    pix = pc.clear_padding(r.integers(0, 256, height * rb, dtype=np.uint8), width, height, depth, colour)
     types = random_types(r, width, height, force) if types is None else types
     stream = am.filter_passes(am.interlace(pix, width, height, depth, colour), width, height, depth, colour, types)
     assert len(stream) == am.size(width, height, depth, colour)
@@ -175,7 +166,7 @@ def test_padding_bits_of_the_pass_rows_do_not_reach_the_picture(pair):
         rb = fm.geometry(width, depth, colour)[0]
         entries = []
         for height in (2, 9):
-            pix = ta.clear_padding(r.integers(0, 256, height * rb, dtype=np.uint8), width, height, depth, colour)
+            pix = pc.clear_padding(r.integers(0, 256, height * rb, dtype=np.uint8), width, height, depth, colour)
             images = []
             for (pw, ph), img in zip(am.passes(width, height), am.interlace(pix, width, height, depth, colour)):
                 spare = -(pw * depth) % 8
@@ -239,7 +230,7 @@ def test_methods_in_one_batch(pair):
         p_off = np.concatenate([[0], np.cumsum([e.pix_size for e in prog])]).astype(np.int64)
         filt = np.concatenate([[0]] + [e.filt for e in prog]).astype(np.uint8)
         pix = torch.empty(int(p_off[-1]), dtype=torch.uint8, device="cuda")
-        st = fd.png_unfilter_batch(_dev(filt), _dev(f_off), pix, _dev(p_off), rb, bpp)
+        st = fd.png_unfilter_batch(gh.dev(filt), gh.dev(f_off), pix, gh.dev(p_off), rb, bpp)
         torch.cuda.synchronize()
         assert st.cpu().tolist() == [0] * len(prog)
         assert pix.cpu().numpy().tobytes() == b"".join(bytes(e.want) for e in prog)
@@ -313,10 +304,10 @@ def test_more_images_than_wavefronts(n):
         reps = -(-n // 40)
         filt = np.tile(np.concatenate([e.filt for e in kinds]), reps)[:n * fs]
         want = np.tile(np.concatenate([np.frombuffer(e.want, dtype=np.uint8) for e in kinds]), reps)[:n * ps]
-        d_filt = _dev(np.concatenate([[GUARD], filt, [GUARD] * 8]).astype(np.uint8))
+        d_filt = gh.dev(np.concatenate([[GUARD], filt, [GUARD] * 8]).astype(np.uint8))
         pix = torch.full((n * ps + 32,), GUARD, dtype=torch.uint8, device="cuda")
-        st = fd.png_unfilter_interlaced_batch(d_filt, _dev(1 + np.arange(n + 1, dtype=np.int64) * fs), pix,
-                                              _dev(3 + np.arange(n + 1, dtype=np.int64) * ps), 5, depth, colour)
+        st = fd.png_unfilter_interlaced_batch(d_filt, gh.dev(1 + np.arange(n + 1, dtype=np.int64) * fs), pix,
+                                              gh.dev(3 + np.arange(n + 1, dtype=np.int64) * ps), 5, depth, colour)
         torch.cuda.synchronize()
         assert int(st.abs().sum()) == 0
         got = pix.cpu().numpy()
@@ -325,19 +316,6 @@ def test_more_images_than_wavefronts(n):
 
 
 # ---- the scan ----
-
-def _batch_of(files, front=5, slack=3):
-    f_off = np.concatenate([[front], front + np.cumsum([len(f) + slack for f in files])]).astype(np.int64)
-    host = np.full(int(f_off[-1]) + 16, 0xEE, dtype=np.uint8)
-    for o, f in zip(f_off[:-1], files):
-        host[int(o):int(o) + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    return host, f_off, np.array([len(f) for f in files], dtype=np.uint32).view(np.int32)
-
-
-def _info_rows(fd, info):
-    f = fd.png_info_fields(info)
-    return [tuple(int(f[k][i]) for k in fm.Info.FIELDS) for i in range(len(f["status"]))]
-
 
 def test_scan_accepts_adam7_on_request():
     """An interlaced file with the flag: status 0, interlace 1, every count as the scan of the same file with method 0;
@@ -359,12 +337,12 @@ def test_scan_accepts_adam7_on_request():
     in_ihdr = bytearray(inter)
     in_ihdr[29] ^= 1                                        # the IHDR's own CRC field
     files = [inter, as_progressive, two, bytes(damaged), bytes(in_ihdr), inter[:60], inter]
-    host, f_off, f_len = _batch_of(files)
+    host, f_off, f_len = gh.batch_of(files)
     for flags, adam7, ignore in ((0, False, False), (fd.PNG_FLAG_ADAM7, True, False),
                                  (fd.PNG_FLAG_ADAM7 | fd.PNG_FLAG_IGNORE_CRC, True, True), (fd.PNG_FLAG_IGNORE_CRC, False, True)):
-        info = fd.png_scan_files_batch(_dev(host), _dev(f_off), _dev(f_len), flags=flags)
+        info = fd.png_scan_files_batch(gh.dev(host), gh.dev(f_off), gh.dev(f_len), flags=flags)
         torch.cuda.synchronize()
-        rows = _info_rows(fd, info)
+        rows = gh.info_rows(fd, info)
         assert rows == [am.scan(f, adam7, ignore, zlib.crc32).fields() for f in files], flags
         st = [w[0] for w in rows]
         if adam7:
@@ -395,15 +373,15 @@ def test_files_end_to_end(cls):
     rb = fm.geometry(width, depth, colour)[0]
 
     def make(height, interlaced, w=width):
-        pix, key, pal = xm.random_case(r, w, height, depth, colour, keyed)
-        pix = ta.clear_padding(pix, w, height, depth, colour)
-        pre = xm.pre_chunks(colour, key, pal, text=True)
+        pix, key, pal = pc.random_case(r, w, height, depth, colour, keyed)
+        pix = pc.clear_padding(pix, w, height, depth, colour)
+        pre = pc.pre_chunks(colour, key, pal, text=True)
         if interlaced:
             png = am.write_file(am.stream_of(pix, w, height, depth, colour, random_types(r, w, height)), w, height, depth, colour, pre, 3, zlib.crc32)
         else:
-            png = em.write_file(xm.stream_of(pix, fm.geometry(w, depth, colour)[0]), w, height, depth, colour, pre, 3, zlib.crc32)
+            png = em.write_file(pc.stream_of(pix, fm.geometry(w, depth, colour)[0]), w, height, depth, colour, pre, 3, zlib.crc32)
         rgba = em.expand(pix, w, depth, colour, key, pal)[0]
-        assert xm.pillow_rgba(png) == rgba or (keyed and (depth, colour) in xm.LEFT_OUT)
+        assert pc.pillow_rgba(png) == rgba or (keyed and (depth, colour) in pc.LEFT_OUT)
         return png, pix.tobytes(), rgba, height, interlaced
 
     cases = [make(9, True), make(7, False), make(70, True), make(3, False), make(1, True)]
@@ -412,21 +390,21 @@ def test_files_end_to_end(cls):
     #        file, pixels, rgba, height, interlaced, png_status with the flag
     plan = [cases[0] + (0,), cases[1] + (0,), (cut, b"", b"", 0, True, 3), cases[2] + (0,), (other, b"", b"", 0, True, 7),
             cases[3] + (0,), cases[4] + (0,)]
-    host, f_off, f_len = _batch_of([p[0] for p in plan])
+    host, f_off, f_len = gh.batch_of([p[0] for p in plan])
     for flags in (fd.PNG_FLAG_ADAM7, 0):
         shown = [p if (flags or not p[4]) else (p[0], b"", b"", 0, True, 3) for p in plan]
         want_info = [4 if (p[4] and not flags) else (2 if p[0] is cut else 0) for p in plan]
-        pix, pix_off, info, status, png_status = fd.png_decode_files_batch(_dev(host), _dev(f_off), width, depth, colour,
-                                                                           file_len=_dev(f_len), flags=flags)
+        pix, pix_off, info, status, png_status = fd.png_decode_files_batch(gh.dev(host), gh.dev(f_off), width, depth, colour,
+                                                                           file_len=gh.dev(f_len), flags=flags)
         torch.cuda.synchronize()
         assert info[:, 0].cpu().tolist() == want_info, (cls, flags)
-        assert _info_rows(fd, info) == [am.scan(p[0], bool(flags), False, zlib.crc32).fields() for p in plan]
+        assert gh.info_rows(fd, info) == [am.scan(p[0], bool(flags), False, zlib.crc32).fields() for p in plan]
         assert png_status.cpu().tolist() == [p[5] for p in shown], (cls, flags)
         assert [status[k].item() for k, p in enumerate(shown) if p[5] == 0] == [0] * sum(1 for p in shown if p[5] == 0)
         assert pix_off.cpu().tolist() == np.concatenate([[0], np.cumsum([len(p[1]) for p in shown])]).tolist()
         assert pix.cpu().numpy().tobytes() == b"".join(p[1] for p in shown), (cls, flags)
-        rgba, rgba_off, info, status, png_status = fd.png_decode_files_rgba_batch(_dev(host), _dev(f_off), width, depth, colour,
-                                                                                 file_len=_dev(f_len), flags=flags)
+        rgba, rgba_off, info, status, png_status = fd.png_decode_files_rgba_batch(gh.dev(host), gh.dev(f_off), width, depth, colour,
+                                                                                 file_len=gh.dev(f_len), flags=flags)
         torch.cuda.synchronize()
         assert info[:, 0].cpu().tolist() == want_info and png_status.cpu().tolist() == [p[5] for p in shown], (cls, flags)
         assert rgba_off.cpu().tolist() == np.concatenate([[0], np.cumsum([len(p[2]) for p in shown])]).tolist()
@@ -443,12 +421,12 @@ def test_a_batch_without_interlaced_files_is_the_same_with_the_flag():
     files = []
     for height in (1, 5, 66):
         pix = r.integers(0, 256, height * rb, dtype=np.uint8)
-        files.append(em.write_file(xm.stream_of(pix, rb), width, height, depth, colour, (), 2, zlib.crc32))
+        files.append(em.write_file(pc.stream_of(pix, rb), width, height, depth, colour, (), 2, zlib.crc32))
     files.insert(1, files[0][:50])
-    host, f_off, f_len = _batch_of(files)
+    host, f_off, f_len = gh.batch_of(files)
     outs = []
     for flags in (0, fd.PNG_FLAG_ADAM7):
-        res = fd.png_decode_files_rgba_batch(_dev(host), _dev(f_off), width, depth, colour, file_len=_dev(f_len), flags=flags)
+        res = fd.png_decode_files_rgba_batch(gh.dev(host), gh.dev(f_off), width, depth, colour, file_len=gh.dev(f_len), flags=flags)
         torch.cuda.synchronize()
         outs.append([t.cpu().numpy().tobytes() for t in res])
     assert outs[0] == outs[1]

@@ -25,12 +25,12 @@ import pytest
 
 import oracle_binding as ob
 import png_choose_model as cm
+import png_gpu_harness as gh
 import png_model
 
 pytestmark = pytest.mark.gpu
 
 BPPS = (1, 2, 3, 4, 6, 8)
-CHUNKS = (1, 2, 8, 9, 63, 64, 65, 127, 128, 129, 255, 256)    # N = ceil(row_bytes / 16), as tests/test_gpu_png.py
 EXTRA_CHUNKS = (4, 32)                      # the default choice's G = 4 and G = 32 (N = 3..4 and 17..32)
 SUBSET_CHUNKS = (1, 9, 64, 65, 256)         # the forced shapes
 GATE = 4096
@@ -38,38 +38,8 @@ FILL = 0xEE
 ENV = ("FDH_PNG_CHOOSE_LANES", "FDH_PNG_CHOOSE_WAVES")
 
 
-def widths_of(bpp, n):
-    """The smallest and the largest multiple of bpp in (16 (n - 1), 16 n]."""
-    lo, hi = 16 * (n - 1), 16 * n
-    small, large = (lo // bpp + 1) * bpp, hi // bpp * bpp
-    assert lo < small <= large <= hi
-    return small, large
-
-
-def widths_above(bpp):
-    first = (GATE // bpp + 1) * bpp
-    assert first > GATE and first - bpp <= GATE
-    return first, 5760, 15360
-
-
 def _shape(monkeypatch, lanes=None, waves=None):
-    for name, val in zip(ENV, (lanes, waves)):
-        if val is None:
-            monkeypatch.delenv(name, raising=False)
-        else:
-            monkeypatch.setenv(name, str(val))
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _offsets(sizes, front, slack):
-    off = np.zeros(len(sizes) + 1, dtype=np.int64)
-    off[0] = front
-    off[1:] = front + np.cumsum(np.asarray(sizes, dtype=np.int64) + np.asarray(slack, dtype=np.int64))
-    return off
+    gh.set_env(monkeypatch, **dict(zip(ENV, (lanes, waves))))
 
 
 class Batch:
@@ -86,11 +56,11 @@ class Batch:
         self.imgs = imgs
         self.rows = [im.shape[0] for im in imgs]
         self.types, self.sums = zip(*(cm.choose(im, bpp) for im in imgs))
-        self.p_off = _offsets([im.size for im in imgs], 3, [0] * self.n)
+        self.p_off = gh.offsets([im.size for im in imgs], 3, [0] * self.n)
         self.pix = np.zeros(int(self.p_off[-1]) + 5, dtype=np.uint8)
         for o, im in zip(self.p_off[:-1], imgs):
             self.pix[int(o):int(o) + im.size] = im.reshape(-1)
-        self.t_off = _offsets(self.rows, 7, [0] * self.n)
+        self.t_off = gh.offsets(self.rows, 7, [0] * self.n)
         self.want = np.full(int(self.t_off[-1]) + 33, FILL, dtype=np.uint8)
         for o, t in zip(self.t_off[:-1], self.types):
             self.want[int(o):int(o) + t.size] = t
@@ -99,7 +69,7 @@ class Batch:
 def _run(fd, b, faults, what, status=None):
     import torch
     d_t = torch.full((b.want.size,), FILL, dtype=torch.uint8, device="cuda")
-    st = fd.png_choose_filters_batch(_dev(b.pix), _dev(b.p_off), d_t, _dev(b.t_off), b.rb, b.bpp)
+    st = fd.png_choose_filters_batch(gh.dev(b.pix), gh.dev(b.p_off), d_t, gh.dev(b.t_off), b.rb, b.bpp)
     torch.cuda.synchronize()
     got = d_t.cpu().numpy()
     if st.cpu().tolist() != (status or [0] * b.n):
@@ -123,15 +93,15 @@ def test_slack_between_types_slots():
     r = np.random.default_rng(4700)
     imgs = cm.choose_images(r, rb, bpp)
     # every image alone, at its own odd offset with odd slack behind it, in one shared buffer
-    t_at = _offsets([im.shape[0] for im in imgs], 9, [2 * (i % 5) + 1 for i in range(len(imgs))])
+    t_at = gh.offsets([im.shape[0] for im in imgs], 9, [2 * (i % 5) + 1 for i in range(len(imgs))])
     want = np.full(int(t_at[-1]) + 33, FILL, dtype=np.uint8)
     d_t = torch.full((want.size,), FILL, dtype=torch.uint8, device="cuda")
     for i, im in enumerate(imgs):
         types, _ = cm.choose(im, bpp)
         want[int(t_at[i]):int(t_at[i]) + types.size] = types
         pix = np.concatenate([np.zeros(1, dtype=np.uint8), im.reshape(-1)])
-        st = fd.png_choose_filters_batch(_dev(pix), _dev(np.array([1, 1 + im.size], dtype=np.int64)), d_t,
-                                         _dev(np.array([t_at[i], t_at[i] + im.shape[0]], dtype=np.int64)), rb, bpp)
+        st = fd.png_choose_filters_batch(gh.dev(pix), gh.dev(np.array([1, 1 + im.size], dtype=np.int64)), d_t,
+                                         gh.dev(np.array([t_at[i], t_at[i] + im.shape[0]], dtype=np.int64)), rb, bpp)
         assert st.cpu().tolist() == [0]
     torch.cuda.synchronize()
     assert np.array_equal(d_t.cpu().numpy(), want)
@@ -149,7 +119,7 @@ def test_types_at_every_width_class(bpp, monkeypatch):
     assert torch.cuda.is_available()
     t0 = time.time()
     r = np.random.default_rng(4600 + bpp)
-    widths = [(n, w) for n in CHUNKS + EXTRA_CHUNKS for w in sorted(set(widths_of(bpp, n)))] + [(0, w) for w in widths_above(bpp)]
+    widths = [(n, w) for n in gh.CHUNKS + EXTRA_CHUNKS for w in sorted(set(gh.widths_of(bpp, n)))] + [(0, w) for w in gh.widths_above(bpp, GATE)]
     faults, runs = [], 0
     count, ties, total = np.zeros(5, dtype=np.int64), 0, 0
     for k, (n, rb) in enumerate(widths):
@@ -196,7 +166,7 @@ def test_sizes_that_do_not_fit(bpp, monkeypatch):
                 tsize[bad] += 1
             else:
                 tsize[bad] -= 1
-            p_off, t_off = _offsets(psize, 3, [0] * 5), _offsets(tsize, 7, [0] * 5)
+            p_off, t_off = gh.offsets(psize, 3, [0] * 5), gh.offsets(tsize, 7, [0] * 5)
             pix = np.zeros(int(p_off[-1]) + 16, dtype=np.uint8)
             want = np.full(int(t_off[-1]) + 33, FILL, dtype=np.uint8)
             for i, im in enumerate(imgs):
@@ -204,7 +174,7 @@ def test_sizes_that_do_not_fit(bpp, monkeypatch):
                 if i != bad:
                     want[int(t_off[i]):int(t_off[i]) + rows[i]] = types[i]
             d_t = torch.full((want.size,), FILL, dtype=torch.uint8, device="cuda")
-            st = fd.png_choose_filters_batch(_dev(pix), _dev(p_off), d_t, _dev(t_off), rb, bpp)
+            st = fd.png_choose_filters_batch(gh.dev(pix), gh.dev(p_off), d_t, gh.dev(t_off), rb, bpp)
             torch.cuda.synchronize()
             assert st.cpu().tolist() == [2 if i == bad else 0 for i in range(5)], (bpp, rb, case, st.cpu().tolist())
             assert np.array_equal(d_t.cpu().numpy(), want), (bpp, rb, case)
@@ -218,7 +188,7 @@ def test_refused_arguments():
     import fdeflate_amd as fd
     from fdeflate_amd import _lib
     pix = torch.zeros(64, dtype=torch.uint8, device="cuda")
-    off = _dev(np.array([0, 0], dtype=np.int64))
+    off = gh.dev(np.array([0, 0], dtype=np.int64))
     types = torch.full((8,), FILL, dtype=torch.uint8, device="cuda")
     st = torch.full((1,), 77, dtype=torch.int32, device="cuda")
     L = _lib.lib()
@@ -270,23 +240,23 @@ def test_pixels_to_idat_end_to_end(bpp, monkeypatch):
         assert st == 0
         filt.append(f)
         want.append(ob.compress_ultra_fast(f))
-    p_off = _offsets([im.size for im in imgs], 3, [0] * n)
+    p_off = gh.offsets([im.size for im in imgs], 3, [0] * n)
     pix = np.zeros(int(p_off[-1]) + 1, dtype=np.uint8)
     for o, im in zip(p_off[:-1], imgs):
         pix[int(o):int(o) + im.size] = im.reshape(-1)
     caps = [int(fd.ultrafast_bound(nr * (rb + 1))) for nr in rows]
-    o_off = _offsets(caps, 7, [2 * (i % 4) + 1 for i in range(n)])
+    o_off = gh.offsets(caps, 7, [2 * (i % 4) + 1 for i in range(n)])
     expect = np.full(int(o_off[-1]) + 33, FILL, dtype=np.uint8)
     for o, w in zip(o_off[:-1], want):
         expect[int(o):int(o) + len(w)] = np.frombuffer(w, dtype=np.uint8)
     all_types = np.concatenate(types)
-    d_pix, d_poff, d_ooff = _dev(pix), _dev(p_off), _dev(o_off)
+    d_pix, d_poff, d_ooff = gh.dev(pix), gh.dev(p_off), gh.dev(o_off)
     for own in (False, True):
         d_out = torch.full((expect.size,), FILL, dtype=torch.uint8, device="cuda")
         if own:
-            t_off = _offsets(rows, 5, [0] * n)
+            t_off = gh.offsets(rows, 5, [0] * n)
             d_types = torch.full((int(t_off[-1]) + 9,), FILL, dtype=torch.uint8, device="cuda")
-            ol, st, ty = fd.png_encode_ultrafast_batch(d_pix, d_poff, d_out, d_ooff, rb, bpp, types=d_types, types_off=_dev(t_off))
+            ol, st, ty = fd.png_encode_ultrafast_batch(d_pix, d_poff, d_out, d_ooff, rb, bpp, types=d_types, types_off=gh.dev(t_off))
             assert ty is d_types
             got_t = ty.cpu().numpy()
             assert (got_t[:5] == FILL).all() and (got_t[int(t_off[-1]):] == FILL).all()

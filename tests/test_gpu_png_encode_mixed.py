@@ -9,36 +9,18 @@ import numpy as np
 import pytest
 
 import png_choose_model as cm
+import png_corpus as pc
 import png_encode_mixed_model as em
 import png_file_model as fm
+import png_gpu_harness as gh
 import png_mixed_model as mm
 import png_model
 import png_pack_model as pm
-import test_gpu_png_pack as gp
-import test_png_encode_mixed_model as tm
-import test_png_expand_model as xm
-import test_png_pack_model as tp
+from png_gpu_harness import GUARD, HEIGHTS, PASSED_ON
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0x5A
 GUARD_WORD = 0x5A5A5A5A
-WIDTHS = gp.WIDTHS          # 1 .. 9, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1023: every G from 1 to 64 and looped rows
-HEIGHTS = gp.HEIGHTS        # 1, 2, 3, one more than a band
-PASSED_ON = 77
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _words(rows):
-    return _dev(np.asarray(rows, dtype=np.uint32).view(np.int32))
-
-
-def _offsets(sizes, front=0):
-    return np.concatenate([[front], front + np.cumsum(sizes)]).astype(np.int64)
 
 
 class Picture:
@@ -62,9 +44,9 @@ class Picture:
 def representable(r, width, height, depth, colour):
     if colour == 3:
         colours = int(r.integers(1, (1 << depth) + 1))
-        px = tp.palette_image(r, width, height, colours, int(r.integers(0, colours + 1))).view(np.uint32)
+        px = pc.palette_image(r, width, height, colours, int(r.integers(0, colours + 1))).view(np.uint32)
     else:
-        px = gp.random_rgba(r, width, height, depth, colour)
+        px = gh.random_rgba(r, width, height, depth, colour)
     return Picture(px, width, height, depth, colour)
 
 
@@ -72,11 +54,11 @@ _CROSS = []
 
 
 def cross_product():
-    """All fifteen pairs times WIDTHS times HEIGHTS, built once."""
+    """All fifteen pairs times gh.PACK_WIDTHS times HEIGHTS, built once."""
     if not _CROSS:
         r = np.random.default_rng(12200)
         for depth, colour in fm.PAIRS:
-            for width in WIDTHS:
+            for width in gh.PACK_WIDTHS:
                 for height in HEIGHTS:
                     _CROSS.append(representable(r, width, height, depth, colour))
     return _CROSS
@@ -88,10 +70,10 @@ class Mixed:
     def __init__(self, pictures, file_sizes=None):
         self.p = pictures
         self.n = len(pictures)
-        self.r_off = _offsets([4 * p.px.size for p in pictures], 5)
-        self.p_off = _offsets([p.pix_size for p in pictures], 3)
-        self.t_off = _offsets([p.types_size for p in pictures], 1)
-        self.f_off = _offsets(file_sizes or [p.file_size for p in pictures], 7)
+        self.r_off = gh.offsets([4 * p.px.size for p in pictures], 5)
+        self.p_off = gh.offsets([p.pix_size for p in pictures], 3)
+        self.t_off = gh.offsets([p.types_size for p in pictures], 1)
+        self.f_off = gh.offsets(file_sizes or [p.file_size for p in pictures], 7)
         self.e_off = self.f_off.copy()
         self.e_off[:self.n] += [p.prefix for p in pictures]
         self.e_off[self.n] = max(self.f_off[self.n] - 16, self.e_off[self.n - 1]) if self.n else self.f_off[0]
@@ -105,10 +87,10 @@ class Mixed:
 
     def device(self):
         import torch
-        self.d_rgba, self.d_info = _dev(self.rgba), _words(self.info)
-        self.d_pal, self.d_colour, self.d_trns = _words(self.pal), _words(self.colour), _words(self.trns)
-        self.d_r_off, self.d_p_off, self.d_t_off = _dev(self.r_off), _dev(self.p_off), _dev(self.t_off)
-        self.d_f_off, self.d_e_off = _dev(self.f_off), _dev(self.e_off)
+        self.d_rgba, self.d_info = gh.dev(self.rgba), gh.words(self.info)
+        self.d_pal, self.d_colour, self.d_trns = gh.words(self.pal), gh.words(self.colour), gh.words(self.trns)
+        self.d_r_off, self.d_p_off, self.d_t_off = gh.dev(self.r_off), gh.dev(self.p_off), gh.dev(self.t_off)
+        self.d_f_off, self.d_e_off = gh.dev(self.f_off), gh.dev(self.e_off)
         full = lambda size: torch.full((int(size),), GUARD, dtype=torch.uint8, device="cuda")
         self.pix, self.types, self.file = full(self.p_off[-1] + 11), full(self.t_off[-1] + 11), full(self.f_off[-1] + 11)
         return self
@@ -123,12 +105,12 @@ class Mixed:
         self.device()
         st = [self.status() for _ in range(6)]
         view = lambda t: t[8:8 + self.n]
-        up = [None if u is None else _words(u) for u in upstream]
+        up = [None if u is None else gh.words(u) for u in upstream]
         fd.png_pack_mixed_batch(self.d_rgba, self.d_r_off, self.pix, self.d_p_off, self.d_info, pal=self.d_pal if pal else None,
                                 colour=self.d_colour if pal else None, upstream=up[0], png_status=view(st[0]))
         fd.png_choose_filters_mixed_batch(self.pix, self.d_p_off, self.types, self.d_t_off, self.d_info, upstream=up[1], png_status=view(st[1]))
         if types is not None:
-            self.types[self.t_off[0]:self.t_off[-1]] = _dev(types)
+            self.types[self.t_off[0]:self.t_off[-1]] = gh.dev(types)
         fd.png_filter_deflate_ultrafast_mixed_batch(self.pix, self.d_p_off, self.types, self.d_t_off, self.file, self.d_e_off, self.d_info,
                                                     upstream=up[2], out_len=view(st[2]), png_status=view(st[3]))
         idat = torch.where(view(st[3]) != 0, torch.zeros_like(view(st[2])), view(st[2]))
@@ -170,19 +152,19 @@ def reference(fd, pictures):
     for (depth, colour, width), group in groups.items():
         n = len(group)
         rb, bpp = group[0].rb, group[0].bpp
-        r_off = _offsets([4 * p.px.size for p in group])
-        p_off, t_off = _offsets([p.pix_size for p in group]), _offsets([p.height for p in group])
-        o_off = _offsets([p.file_size for p in group])
-        rgba = _dev(np.concatenate([p.px.view(np.uint8) for p in group]))
+        r_off = gh.offsets([4 * p.px.size for p in group])
+        p_off, t_off = gh.offsets([p.pix_size for p in group]), gh.offsets([p.height for p in group])
+        o_off = gh.offsets([p.file_size for p in group])
+        rgba = gh.dev(np.concatenate([p.px.view(np.uint8) for p in group]))
         pix = torch.zeros(int(p_off[-1]), dtype=torch.uint8, device="cuda")
         types = torch.zeros(int(t_off[-1]), dtype=torch.uint8, device="cuda")
         out = torch.zeros(int(o_off[-1]), dtype=torch.uint8, device="cuda")
-        d_p_off, d_t_off = _dev(p_off), _dev(t_off)
-        pal = _words([p.pal for p in group]) if colour == 3 else None
-        col = _words([[p.count, 0, 0, 0] for p in group]) if colour == 3 else None
-        st1 = fd.png_pack_batch(rgba, _dev(r_off), pix, d_p_off, width, depth, colour, pal=pal, colour=col)
+        d_p_off, d_t_off = gh.dev(p_off), gh.dev(t_off)
+        pal = gh.words([p.pal for p in group]) if colour == 3 else None
+        col = gh.words([[p.count, 0, 0, 0] for p in group]) if colour == 3 else None
+        st1 = fd.png_pack_batch(rgba, gh.dev(r_off), pix, d_p_off, width, depth, colour, pal=pal, colour=col)
         st2 = fd.png_choose_filters_batch(pix, d_p_off, types, d_t_off, rb, bpp)
-        out_len, st3 = fd.png_filter_deflate_ultrafast_batch(pix, d_p_off, types, d_t_off, out, _dev(o_off), rb, bpp)
+        out_len, st3 = fd.png_filter_deflate_ultrafast_batch(pix, d_p_off, types, d_t_off, out, gh.dev(o_off), rb, bpp)
         assert st1.cpu().tolist() == [0] * n and st2.cpu().tolist() == [0] * n and st3.cpu().tolist() == [0] * n
         h_pix, h_types, h_out, lens = pix.cpu().numpy(), types.cpu().numpy(), out.cpu().numpy(), out_len.cpu().tolist()
         for k, p in enumerate(group):
@@ -190,11 +172,11 @@ def reference(fd, pictures):
             # the framing of the image alone, with its own palette sizes: the stream goes where the prefix ends
             prefix = p.prefix
             slot = torch.zeros(prefix + lens[k] + 16, dtype=torch.uint8, device="cuda")
-            slot[prefix:prefix + lens[k]] = _dev(stream)
-            f_off = _dev(np.asarray([0, slot.numel()], dtype=np.int64))
-            idat, height = _words([lens[k]]), _words([p.height])
+            slot[prefix:prefix + lens[k]] = gh.dev(stream)
+            f_off = gh.dev(np.asarray([0, slot.numel()], dtype=np.int64))
+            idat, height = gh.words([lens[k]]), gh.words([p.height])
             if colour == 3:
-                f_len, st4 = fd.png_frame_palette_batch(slot, f_off, idat, height, _words([p.pal]), _words([[p.count, 0, 0, 0]]), _words([p.trns]),
+                f_len, st4 = fd.png_frame_palette_batch(slot, f_off, idat, height, gh.words([p.pal]), gh.words([[p.count, 0, 0, 0]]), gh.words([p.trns]),
                                                         width, depth, p.count, p.trns)
             else:
                 f_len, st4 = fd.png_frame_batch(slot, f_off, idat, height, width, depth, colour)
@@ -250,7 +232,7 @@ def test_every_seventh_image_against_the_models():
         assert b.slot("types", k).tolist() == types.tolist(), what
         idat = ob.compress_ultra_fast(png_model.filter_rows(rows, p.bpp, types.tolist()).tobytes())
         assert b.png(k) == em.write_file(idat, p.width, p.height, p.depth, p.colour, p.pal, p.count, p.trns, zlib.crc32), what
-        assert xm.pillow_rgba(b.png(k)) == p.px.view(np.uint8).tobytes() or p.depth == 16, what
+        assert pc.pillow_rgba(b.png(k)) == p.px.view(np.uint8).tobytes() or p.depth == 16, what
 
 
 # ---- the plan on the device ----
@@ -259,7 +241,7 @@ def _chosen_pictures():
     r = np.random.default_rng(12400)
     out = []
     for width, height in ((37, 29), (64, 17), (5, 3)):
-        out += [(name, px, width, height) for name, px, _, _ in tm.kinds(r, width, height)]
+        out += [(name, px, width, height) for name, px, _, _ in pc.kinds(r, width, height)]
     two = np.asarray([0xFF000000, 0xFFFFFFFF], dtype=np.uint32)
     for side in (1, 2):                                             # the palette loses to its own chunks
         out.append(("two-greys", two[r.integers(0, 2, side * side)].view(np.uint8), side, side))
@@ -282,12 +264,12 @@ def test_analyse_and_plan_choose_what_the_model_chooses(allowed):
     import fdeflate_amd as fd
     cases = _chosen_pictures()
     n = len(cases)
-    r_off = _offsets([px.size for _, px, _, _ in cases], 3)
+    r_off = gh.offsets([px.size for _, px, _, _ in cases], 3)
     rgba = np.full(int(r_off[-1]) + 5, GUARD, dtype=np.uint8)
     for k, (_, px, _, _) in enumerate(cases):
         rgba[r_off[k]:r_off[k + 1]] = px
-    info = fd.png_encode_records(_words([c[2] for c in cases]), _words([c[3] for c in cases]))
-    pal, colour, trns, summary, analysed = fd.png_analyse_mixed_batch(_dev(rgba), _dev(r_off), info)
+    info = fd.png_encode_records(gh.words([c[2] for c in cases]), gh.words([c[3] for c in cases]))
+    pal, colour, trns, summary, analysed = fd.png_analyse_mixed_batch(gh.dev(rgba), gh.dev(r_off), info)
     before = info.clone()
     sizes = fd.png_encode_plan_batch(info, colour, trns, summary, analysed, allowed)
     torch.cuda.synchronize()
@@ -376,7 +358,7 @@ def test_one_wrong_image_among_good_ones():
         check_against_reference(fd, b, skip=(k,))
     # a pixel the pair cannot hold
     r = np.random.default_rng(12501)
-    px = gp.random_rgba(r, 33, 5, 8, 0)
+    px = gh.random_rgba(r, 33, 5, 8, 0)
     spoilt = Picture(px, 33, 5, 8, 0)
     spoilt.px = px.copy()
     spoilt.px[77] = 0xFF010000
@@ -405,7 +387,7 @@ def test_upstream_at_each_call_null_palette_colours_and_filter_types():
         check_against_reference(fd, b, skip=(2,))
     # analyse: upstream, more colours than max_colours, a slot off by one, a record of neither kind
     b = Mixed(list(good)).device()
-    up = _words([0, PASSED_ON] + [0] * (n - 2))
+    up = gh.words([0, PASSED_ON] + [0] * (n - 2))
     info = b.d_info.clone()
     info[4, 2] += 1                                   # one row more than the slot holds
     info[5, 3] = 8 | 5 << 8
@@ -470,15 +452,15 @@ def _ragged(seed):
     r = np.random.default_rng(seed)
     out = []
     for width, height in ((37, 29), (64, 17), (5, 3), (341, 64), (1, 1), (2, 2), (1023, 3)):
-        out += [(name, px, width, height, depth, colour) for name, px, depth, colour in tm.kinds(r, width, height)]
+        out += [(name, px, width, height, depth, colour) for name, px, depth, colour in pc.kinds(r, width, height)]
     order = r.permutation(len(out))
     return [out[k] for k in order]
 
 
 def _collection(cases):
-    r_off = _offsets([c[1].size for c in cases])
+    r_off = gh.offsets([c[1].size for c in cases])
     rgba = np.concatenate([c[1] for c in cases]).astype(np.uint8)
-    return _dev(rgba), _dev(r_off), _words([c[2] for c in cases]), _words([c[3] for c in cases])
+    return gh.dev(rgba), gh.dev(r_off), gh.words([c[2] for c in cases]), gh.words([c[3] for c in cases])
 
 
 def test_ragged_collection_end_to_end():
@@ -503,7 +485,7 @@ def test_ragged_collection_end_to_end():
         scan = fm.scan(png, crc=zlib.crc32)
         assert (scan.status, scan.width, scan.height, scan.bit_depth, scan.colour_type) == (0, w, h, depth, colour), (k, name)
         assert fields[k, 3] == depth | colour << 8 and offs[k + 1] - offs[k] >= lens[k]
-        assert xm.pillow_rgba(png) == px.tobytes(), (k, name)
+        assert pc.pillow_rgba(png) == px.tobytes(), (k, name)
     back, back_off, _, status, png_status = fd.png_decode_mixed_files_rgba_batch(file, f_off, file_len=f_len)
     torch.cuda.synchronize()
     assert status.cpu().tolist() == [0] * len(cases) and png_status.cpu().tolist() == [0] * len(cases)
@@ -528,14 +510,14 @@ def test_forced_pair_against_the_per_geometry_pipeline(pair):
     images = [representable(r, width, h, depth, colour) for h in heights]
     spoilt = 0xFF010203 if colour != 2 and (depth, colour) != (16, 6) and colour != 3 else None
     rgba = np.concatenate([p.px.view(np.uint8) for p in images])
-    r_off = _offsets([4 * p.px.size for p in images])
-    d_rgba, d_off = _dev(rgba), _dev(r_off)
-    w, h = _words([width] * 4), _words(list(heights))
+    r_off = gh.offsets([4 * p.px.size for p in images])
+    d_rgba, d_off = gh.dev(rgba), gh.dev(r_off)
+    w, h = gh.words([width] * 4), gh.words(list(heights))
     file, f_off, f_len, st, info = fd.png_encode_mixed_rgba_files_batch(d_rgba, d_off, w, h, pairs=pair)
     extra = fd.png_palette_file_prefix(1 << depth, 1 << depth) - 41 if colour == 3 else 0
-    u_off = gp._file_slots(fd, heights, width, depth, colour, extra)
+    u_off = gh.file_slots(fd, heights, width, depth, colour, extra)
     u_file = torch.full((int(u_off[-1]) + 16,), GUARD, dtype=torch.uint8, device="cuda")
-    u_len, u_st = fd.png_encode_rgba_files_batch(d_rgba, d_off, u_file, _dev(u_off), width, depth, colour)
+    u_len, u_st = fd.png_encode_rgba_files_batch(d_rgba, d_off, u_file, gh.dev(u_off), width, depth, colour)
     torch.cuda.synchronize()
     assert st.cpu().tolist() == [0] * 4 and u_st.cpu().tolist() == [0] * 4
     host, offs, lens = file.cpu().numpy(), f_off.cpu().tolist(), f_len.cpu().tolist()
@@ -564,11 +546,11 @@ def test_forced_pair_against_the_per_geometry_pipeline(pair):
                 assert len(body) == p.trns and other[:len(body)] == body and set(other[len(body):]) <= {255}
             else:
                 assert body == other, (pair, k, tag)
-        assert xm.pillow_rgba(mine) == p.px.view(np.uint8).tobytes()
+        assert pc.pillow_rgba(mine) == p.px.view(np.uint8).tobytes()
     if spoilt is not None:
         bad = rgba.copy()
         bad.view(np.uint32)[images[0].px.size + 3] = spoilt
-        _, _, f_len, st, _ = fd.png_encode_mixed_rgba_files_batch(_dev(bad), d_off, w, h, pairs=pair)
+        _, _, f_len, st, _ = fd.png_encode_mixed_rgba_files_batch(gh.dev(bad), d_off, w, h, pairs=pair)
         torch.cuda.synchronize()
         assert st.cpu().tolist() == [0, 13, 0, 0] and f_len.cpu().tolist()[1] == 0
 
@@ -585,9 +567,9 @@ def test_caller_slots_too_many_colours_and_bad_records_in_the_pipeline():
     sizes = lens.copy()
     sizes[3] -= 1
     sizes[8] = 20
-    own_off = _offsets(sizes, 6)
+    own_off = gh.offsets(sizes, 6)
     own = torch.full((int(own_off[-1]) + 9,), GUARD, dtype=torch.uint8, device="cuda")
-    _, _, own_len, own_st, _ = fd.png_encode_mixed_rgba_files_batch(rgba, r_off, width, height, file=own, file_off=_dev(own_off))
+    _, _, own_len, own_st, _ = fd.png_encode_mixed_rgba_files_batch(rgba, r_off, width, height, file=own, file_off=gh.dev(own_off))
     torch.cuda.synchronize()
     want = [0] * 12
     want[3] = want[8] = 2
@@ -600,11 +582,11 @@ def test_caller_slots_too_many_colours_and_bad_records_in_the_pipeline():
             assert host[own_off[k]:own_off[k + 1]].tobytes() == first[offs[k]:offs[k] + lens[k]].tobytes(), k
     # a forced palette pair on a picture of more than 256 colours: the analysis' 12; width 0: 3; both without a file
     many = np.random.default_rng(13001).integers(0, 1 << 32, 40 * 40, dtype=np.uint64).astype(np.uint32).view(np.uint8)
-    few = tp.palette_image(np.random.default_rng(13002), 40, 40, 200, 3)
-    rgba2, off2 = _dev(np.concatenate([few, many, few])), _dev(_offsets([few.size, many.size, few.size]))
-    _, _, l2, s2, _ = fd.png_encode_mixed_rgba_files_batch(rgba2, off2, _words([40, 40, 40]), _words([40, 40, 40]), pairs=(8, 3))
-    _, _, l3, s3, _ = fd.png_encode_mixed_rgba_files_batch(rgba2, off2, _words([40, 0, 40]), _words([40, 40, 40]))
-    _, _, l4, s4, _ = fd.png_encode_mixed_rgba_files_batch(rgba2, off2, _words([40, 40, 40]), _words([40, 41, 40]))
+    few = pc.palette_image(np.random.default_rng(13002), 40, 40, 200, 3)
+    rgba2, off2 = gh.dev(np.concatenate([few, many, few])), gh.dev(gh.offsets([few.size, many.size, few.size]))
+    _, _, l2, s2, _ = fd.png_encode_mixed_rgba_files_batch(rgba2, off2, gh.words([40, 40, 40]), gh.words([40, 40, 40]), pairs=(8, 3))
+    _, _, l3, s3, _ = fd.png_encode_mixed_rgba_files_batch(rgba2, off2, gh.words([40, 0, 40]), gh.words([40, 40, 40]))
+    _, _, l4, s4, _ = fd.png_encode_mixed_rgba_files_batch(rgba2, off2, gh.words([40, 40, 40]), gh.words([40, 41, 40]))
     torch.cuda.synchronize()
     assert s2.cpu().tolist() == [0, 12, 0] and l2.cpu().tolist()[1] == 0
     assert s3.cpu().tolist() == [0, 3, 0] and l3.cpu().tolist()[1] == 0

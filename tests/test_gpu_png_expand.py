@@ -13,35 +13,13 @@ import zlib
 import numpy as np
 import pytest
 
+import png_corpus as pc
 import png_expand_model as em
 import png_file_model as fm
-import test_png_expand_model as xm
-import test_png_file_model as tm
+import png_gpu_harness as gh
+from png_gpu_harness import GUARD, HEIGHTS, PASSED_ON
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 0x5A
-BAND = 64
-# either side of a byte of 1-bit pixels, a lane's four pixels, a 16-byte store, a wavefront's 256 pixels; the bench row
-WIDTHS = tuple(range(1, 10)) + (31, 32, 33, 63, 64, 65, 255, 256, 257, 1023)
-HEIGHTS = (1, 2, 3, BAND + 1)
-PASSED_ON = 77          # an upstream status: such slots are the guards between the images
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _words(rows):
-    return _dev(np.asarray(rows, dtype=np.uint32).view(np.int32))
-
-
-def _waves(monkeypatch, waves):
-    if waves is None:
-        monkeypatch.delenv("FDH_PNG_EXPAND_WAVES", raising=False)
-    else:
-        monkeypatch.setenv("FDH_PNG_EXPAND_WAVES", str(waves))
 
 
 class Batch:
@@ -78,13 +56,13 @@ class Batch:
     def run(self, fd):
         """-> (output buffer, png_status) after one call; the input must not change."""
         import torch
-        d_pix = _dev(self.pix)
+        d_pix = gh.dev(self.pix)
         rgba = torch.full((self.expect.size,), GUARD, dtype=torch.uint8, device="cuda")
         st = torch.full((self.n + 16,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-        fd.png_expand_batch(d_pix, _dev(self.p_off), rgba, _dev(self.r_off), *self.geometry,
-                            pal=None if self.pal is None else _words(self.pal),
-                            colour=None if self.colour is None else _words(self.colour),
-                            upstream=_words(self.upstream), png_status=st[8:8 + self.n])
+        fd.png_expand_batch(d_pix, gh.dev(self.p_off), rgba, gh.dev(self.r_off), *self.geometry,
+                            pal=None if self.pal is None else gh.words(self.pal),
+                            colour=None if self.colour is None else gh.words(self.colour),
+                            upstream=gh.words(self.upstream), png_status=st[8:8 + self.n])
         torch.cuda.synchronize()
         assert np.array_equal(d_pix.cpu().numpy(), self.pix)
         st = st.cpu().numpy()
@@ -103,7 +81,7 @@ class Batch:
 
 @pytest.mark.parametrize("pair", fm.PAIRS, ids=["depth%d-colour%d" % p for p in fm.PAIRS])
 def test_expand_every_width_and_height(pair, monkeypatch):
-    """Every width of WIDTHS at heights 1, 2, 3 and one more than a band, eight images a call (each height twice, with
+    """Every width of gh.EXPAND_WIDTHS at heights 1, 2, 3 and one more than a band, eight images a call (each height twice, with
     different pixels), with a key / tRNS and without: the output buffer equals the model's byte for byte, guard slots
     and the bytes behind the last slot included, and every status is right.  Each batch runs with one wavefront per
     image (a wavefront takes two bands), with seven (more wavefronts than bands) and with the default."""
@@ -113,13 +91,13 @@ def test_expand_every_width_and_height(pair, monkeypatch):
     for keyed in (False, True):
         if keyed and colour in (4, 6):
             continue                    # (no key and no tRNS in these)
-        for width in WIDTHS:
-            images = [xm.random_case(r, width, h, depth, colour, keyed) for h in HEIGHTS + HEIGHTS]
+        for width in gh.EXPAND_WIDTHS:
+            images = [pc.random_case(r, width, h, depth, colour, keyed) for h in HEIGHTS + HEIGHTS]
             b = Batch(images, width, depth, colour)
             if keyed and colour != 3:
                 assert all(0 in w[3::4] for w in b.want)
             for waves in (1, 7, None):
-                _waves(monkeypatch, waves)
+                gh.set_env(monkeypatch, FDH_PNG_EXPAND_WAVES=waves)
                 b.check(fd, (pair, keyed, width, waves))
 
 
@@ -151,7 +129,7 @@ def test_palette_sizes_and_an_index_outside(depth, monkeypatch):
         b = Batch(images, width, depth, 3)
         assert b.want_status[0::2] == [0, 0, 0, 9, 0]
         for waves in (None, 1):
-            _waves(monkeypatch, waves)
+            gh.set_env(monkeypatch, FDH_PNG_EXPAND_WAVES=waves)
             b.check(fd, (depth, width, waves))
 
 
@@ -182,16 +160,16 @@ def test_slots_that_do_not_fit_and_upstream():
                 expect[r_off[k]:r_off[k + 1]] = np.frombuffer(rgba, dtype=np.uint8)
         rgba = torch.full((expect.size,), GUARD, dtype=torch.uint8, device="cuda")
         n = len(plan)
-        st = fd.png_expand_batch(_dev(pix), _dev(p_off), rgba, _dev(r_off), width, depth, colour,
-                                 pal=_words([em.pal_words(pal)] * n) if pal else None,
-                                 colour=_words([em.colour_words(256, None)] * n) if pal else None,
-                                 upstream=_words([p[2] for p in plan]))
+        st = fd.png_expand_batch(gh.dev(pix), gh.dev(p_off), rgba, gh.dev(r_off), width, depth, colour,
+                                 pal=gh.words([em.pal_words(pal)] * n) if pal else None,
+                                 colour=gh.words([em.colour_words(256, None)] * n) if pal else None,
+                                 upstream=gh.words([p[2] for p in plan]))
         torch.cuda.synchronize()
         assert st.cpu().numpy().view(np.uint32).tolist() == [p[3] for p in plan], (depth, colour)
         assert np.array_equal(rgba.cpu().numpy(), expect), (depth, colour)
         # without upstream: the two entries that were passed on are images like the others
-        st = fd.png_expand_batch(_dev(pix), _dev(p_off), rgba, _dev(r_off), width, depth, colour,
-                                 pal=_words([em.pal_words(pal)] * n) if pal else None)
+        st = fd.png_expand_batch(gh.dev(pix), gh.dev(p_off), rgba, gh.dev(r_off), width, depth, colour,
+                                 pal=gh.words([em.pal_words(pal)] * n) if pal else None)
         torch.cuda.synchronize()
         assert st.cpu().tolist() == [0 if p[2] else p[3] for p in plan]
         got = rgba.cpu().numpy()
@@ -216,9 +194,9 @@ def test_more_images_than_wavefronts_fill():
         per = [em.expand(pix[p_off[k]:p_off[k + 1]], width, depth, colour, None, pal)[1] for k in range(n)]
         assert (want_st == 9) == (colour == 3) and (colour != 3 or 0 in per)
         rgba = torch.full((int(r_off[-1]) + 16,), GUARD, dtype=torch.uint8, device="cuda")
-        st = fd.png_expand_batch(_dev(pix), _dev(p_off), rgba, _dev(r_off), width, depth, colour,
-                                 pal=_words([em.pal_words(pal)] * n) if pal else None,
-                                 colour=_words([em.colour_words(3, None)] * n) if pal else None)
+        st = fd.png_expand_batch(gh.dev(pix), gh.dev(p_off), rgba, gh.dev(r_off), width, depth, colour,
+                                 pal=gh.words([em.pal_words(pal)] * n) if pal else None,
+                                 colour=gh.words([em.colour_words(3, None)] * n) if pal else None)
         torch.cuda.synchronize()
         got = rgba.cpu().numpy()
         assert st.cpu().tolist() == per
@@ -227,25 +205,17 @@ def test_more_images_than_wavefronts_fill():
 
 # ---- fdh_png_colour_batch ----
 
-def _batch_of(files, front=5, slack=3):
-    f_off = np.concatenate([[front], front + np.cumsum([len(f) + slack for f in files])]).astype(np.int64)
-    host = np.full(int(f_off[-1]) + 16, 0xEE, dtype=np.uint8)
-    for o, f in zip(f_off[:-1], files):
-        host[int(o):int(o) + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    return host, f_off, np.array([len(f) for f in files], dtype=np.uint32).view(np.int32)
-
-
 def test_colour_batch_every_status():
-    """The files of test_png_expand_model.status_files in one batch, read with every geometry that occurs among them:
+    """The files of png_corpus.status_files in one batch, read with every geometry that occurs among them:
     each file gets the model's status (0, 3, 7, 10, 11 all occur), and on the sound ones `pal` and `colour` are the
     model's word for word.  Nothing outside the result arrays is written."""
     import torch
     import fdeflate_amd as fd
-    cases = xm.status_files()
+    cases = pc.status_files()
     files = [c[1] for c in cases]
-    host, f_off, f_len = _batch_of(files)
-    d_file, d_off = _dev(host), _dev(f_off)
-    info = fd.png_scan_files_batch(d_file, d_off, _dev(f_len))
+    host, f_off, f_len = gh.batch_of(files)
+    d_file, d_off = gh.dev(host), gh.dev(f_off)
+    info = fd.png_scan_files_batch(d_file, d_off, gh.dev(f_len))
     model_info = [fm.scan(f, crc=zlib.crc32) for f in files]
     n, seen, sound = len(files), set(), 0
     for call in sorted({c[2] for c in cases}):
@@ -306,31 +276,31 @@ def test_files_to_rgba(cls):
     rb = fm.geometry(width, depth, colour)[0]
     files, want, heights = [], [], []
     for height in (3, 70):
-        pix, key, pal = xm.random_case(r, width, height, depth, colour, keyed)
-        files.append(em.write_file(xm.stream_of(pix, rb), width, height, depth, colour, xm.pre_chunks(colour, key, pal, text=True), 3, zlib.crc32))
+        pix, key, pal = pc.random_case(r, width, height, depth, colour, keyed)
+        files.append(em.write_file(pc.stream_of(pix, rb), width, height, depth, colour, pc.pre_chunks(colour, key, pal, text=True), 3, zlib.crc32))
         rgba = em.expand(pix, width, depth, colour, key, pal)[0]
-        if (depth, colour) not in xm.LEFT_OUT:
-            assert xm.pillow_rgba(files[-1]) == rgba
+        if (depth, colour) not in pc.LEFT_OUT:
+            assert pc.pillow_rgba(files[-1]) == rgba
         want.append(rgba)
         heights.append(height)
     mode = PILLOW_MODES.get((depth, colour))
     if mode:
         height = 41
-        im = tm._corpus_image(r, mode, width, height)
+        im = pc.corpus_image(r, mode, width, height)
         buf = io.BytesIO()
         im.save(buf, format="PNG")
         png = buf.getvalue()
         info, pal, key = _model_rgba(png, width, depth, colour)
         assert (info.width, info.height) == (width, height)
-        rgba = em.expand(tm.packed_scanlines(im), width, depth, colour, key, pal)[0]
+        rgba = em.expand(pc.packed_scanlines(im), width, depth, colour, key, pal)[0]
         assert rgba == im.convert("RGBA").tobytes()
         files.append(png)
         want.append(rgba)
         heights.append(height)
-    host, f_off, f_len = _batch_of(files)
+    host, f_off, f_len = gh.batch_of(files)
     for with_len in (True, False):
-        rgba, rgba_off, info, status, png_status = fd.png_decode_files_rgba_batch(_dev(host), _dev(f_off), width, depth, colour,
-                                                                                 file_len=_dev(f_len) if with_len else None)
+        rgba, rgba_off, info, status, png_status = fd.png_decode_files_rgba_batch(gh.dev(host), gh.dev(f_off), width, depth, colour,
+                                                                                 file_len=gh.dev(f_len) if with_len else None)
         torch.cuda.synchronize()
         assert status.cpu().tolist() == [0] * len(files) and png_status.cpu().tolist() == [0] * len(files)
         off = rgba_off.cpu().tolist()
@@ -355,22 +325,22 @@ def test_files_to_rgba_each_failure_has_its_status():
 
     def sound(pre=(plte, trns), idat=None, d=depth, c=colour):
         pix = r.integers(0, 256, height * fm.geometry(width, d, c)[0], dtype=np.uint8)
-        return pix, em.write_file(idat or xm.stream_of(pix, fm.geometry(width, d, c)[0]), width, height, d, c, list(pre), 2, zlib.crc32)
+        return pix, em.write_file(idat or pc.stream_of(pix, fm.geometry(width, d, c)[0]), width, height, d, c, list(pre), 2, zlib.crc32)
 
     good = [sound() for _ in range(7)]
     crc = bytearray(good[0][1])
     crc[45] ^= 1                                                  # a byte of the PLTE's body: its CRC no longer fits
-    stream = bytearray(xm.stream_of(good[0][0], rb))
+    stream = bytearray(pc.stream_of(good[0][0], rb))
     stream[len(stream) // 2] ^= 0x55
     stream[0] = 0x79                                              # (and a zlib header that cannot be)
     short_pal = em.palette(em.plte_body(pal[:15]))
     pix9 = np.full(height * rb, 0xFE, dtype=np.uint8)             # indices 15 and 14
     files = [good[0][1], bytes(crc), good[1][1], sound(pre=())[1], good[2][1], sound(pre=(plte, (b"tRNS", bytes(17))))[1], good[3][1],
              sound(idat=bytes(stream))[1], good[4][1], sound(d=8)[1], good[5][1],
-             em.write_file(xm.stream_of(pix9, rb), width, height, depth, colour, [(b"PLTE", em.plte_body(short_pal))], 1, zlib.crc32), good[6][1]]
+             em.write_file(pc.stream_of(pix9, rb), width, height, depth, colour, [(b"PLTE", em.plte_body(short_pal))], 1, zlib.crc32), good[6][1]]
     want_st = [0, 3, 0, 10, 0, 11, 0, 3, 0, 7, 0, 9, 0]
-    host, f_off, f_len = _batch_of(files)
-    rgba, rgba_off, info, status, png_status = fd.png_decode_files_rgba_batch(_dev(host), _dev(f_off), width, depth, colour, file_len=_dev(f_len))
+    host, f_off, f_len = gh.batch_of(files)
+    rgba, rgba_off, info, status, png_status = fd.png_decode_files_rgba_batch(gh.dev(host), gh.dev(f_off), width, depth, colour, file_len=gh.dev(f_len))
     torch.cuda.synchronize()
     assert png_status.cpu().tolist() == want_st
     assert status[7].item() != 0 and [status[k].item() for k in (0, 2, 4, 6, 8, 10, 11, 12)] == [0] * 8

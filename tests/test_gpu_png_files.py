@@ -19,30 +19,22 @@ import pytest
 
 import oracle_binding as ob
 import png_choose_model as cm
+import png_corpus as pc
 import png_file_model as fm
-import test_png_file_model as tm
-from test_gpu_png_choose import CHUNKS, widths_above, widths_of
+import png_gpu_harness as gh
 
 pytestmark = pytest.mark.gpu
 
 FILL = 0xEE
 GUARD32 = 0x5A5A5A5A
+GATE = 4096         # the row widths are those of tests/test_gpu_png_choose.py: its gate
 ENV = ("FDH_CRC_PIECES", "FDH_CRC_COPIES")
 # (bytes per pixel, bit depth, colour type): bpp 1, 2, 3, 4 at 8 bits, 2, 4, 6, 8 at 16
 GEOMETRIES = ((1, 8, 0), (2, 8, 4), (3, 8, 2), (4, 8, 6), (2, 16, 0), (4, 16, 4), (6, 16, 2), (8, 16, 6))
 
 
 def _shape(monkeypatch, pieces=None, copies=None):
-    for name, val in zip(ENV, (pieces, copies)):
-        if val is None:
-            monkeypatch.delenv(name, raising=False)
-        else:
-            monkeypatch.setenv(name, str(val))
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    gh.set_env(monkeypatch, **dict(zip(ENV, (pieces, copies))))
 
 
 def _u32(t):
@@ -67,8 +59,8 @@ def _crc(fd, data, off, length=None, seed=None):
     n = off.size - 1
     cw, c = _guarded(n)
     sw, s = _guarded(n)
-    fd.crc32_batch(data, _dev(off), None if length is None else _dev(np.asarray(length, dtype=np.uint32).view(np.int32)),
-                   None if seed is None else _dev(np.asarray(seed, dtype=np.uint32).view(np.int32)), c, s)
+    fd.crc32_batch(data, gh.dev(off), None if length is None else gh.dev(np.asarray(length, dtype=np.uint32).view(np.int32)),
+                   None if seed is None else gh.dev(np.asarray(seed, dtype=np.uint32).view(np.int32)), c, s)
     torch.cuda.synchronize()
     assert _guards_intact(cw, n) and _guards_intact(sw, n)
     return _u32(c), _u32(s)
@@ -95,7 +87,7 @@ def test_crc_every_length_at_every_alignment(shape, monkeypatch):
     off = np.asarray(off, dtype=np.int64)
     assert sorted(set((off[:-1] % 16).tolist())) == list(range(16))
     host = r.integers(0, 256, int(off[-1]) + 16, dtype=np.uint8)
-    data = _dev(host)
+    data = gh.dev(host)
     assert data.data_ptr() % 16 == 0
     raw = host.tobytes()
     seeds = r.integers(0, 1 << 32, len(lens), dtype=np.uint64).astype(np.uint32)
@@ -122,7 +114,7 @@ def test_crc_ragged_ranges(copies, monkeypatch):
     off = np.concatenate([[3], 3 + np.cumsum(sizes)]).astype(np.int64)
     host = r.integers(0, 256, int(off[-1]) + 7, dtype=np.uint8)
     raw = host.tobytes()
-    data = _dev(host)
+    data = gh.dev(host)
     lens = [int(r.integers(0, s + 1)) if k % 2 else s for k, s in enumerate(sizes)]
     for pieces in (None, 1, 7):
         _shape(monkeypatch, pieces, copies)
@@ -162,7 +154,7 @@ def test_crc_seeds_join_type_and_body():
     off = np.concatenate([[1], 1 + np.cumsum([4 + b for b in bodies])]).astype(np.int64)
     host = r.integers(0, 256, int(off[-1]) + 3, dtype=np.uint8)
     raw = host.tobytes()
-    data = _dev(host)
+    data = gh.dev(host)
     whole, st = _crc(fd, data, off)
     types, st1 = _crc(fd, data, off, [4] * 200)
     body_off = np.concatenate([off[:-1] + 4, off[-1:]]).astype(np.int64)   # slot k: from the body of chunk k to the body of chunk k + 1
@@ -182,7 +174,7 @@ def test_crc_lengths_that_do_not_fit(pieces, monkeypatch):
     host = r.integers(0, 256, int(off[-1]) + 5000, dtype=np.uint8)
     raw = host.tobytes()
     lens = [100, 38, 0, 0xFFFFFFFF, 64, 6000, 1]
-    crc, st = _crc(fd, _dev(host), off, lens, [7] * 7)
+    crc, st = _crc(fd, gh.dev(host), off, lens, [7] * 7)
     assert st.tolist() == [0, 2, 0, 2, 0, 2, 0]
     assert crc.tolist() == [zlib.crc32(raw[int(a):int(a) + n], 7) if s == 0 else 0 for a, n, s in zip(off[:-1], lens, st.tolist())]
     assert crc[2] == 7           # no bytes: the seed
@@ -205,8 +197,8 @@ def _file_case(r, rb, bpp, depth, colour, shift):
 
 
 def _pillow_check(png, im, width, depth, colour):
-    mode, size, shown = tm.pillow_view(png)
-    want_mode, want = tm.pillow_expected(im, width, depth, colour)
+    mode, size, shown = pc.pillow_view(png)
+    want_mode, want = pc.pillow_expected(im, width, depth, colour)
     assert (mode, size) == (want_mode, (width, im.shape[0])) and shown == want
 
 
@@ -225,7 +217,7 @@ def test_pixels_to_files_at_every_width_class(geometry):
     bpp, depth, colour = geometry
     t0 = time.time()
     r = np.random.default_rng(6600 + 16 * bpp + depth)
-    widths = [w for n in CHUNKS for w in sorted(set(widths_of(bpp, n)))] + list(widths_above(bpp))
+    widths = [w for n in gh.CHUNKS for w in sorted(set(gh.widths_of(bpp, n)))] + list(gh.widths_above(bpp, GATE))
     opened = 0
     for k, rb in enumerate(widths):
         assert fd.png_geometry(rb // bpp, depth, colour) == fm.geometry(rb // bpp, depth, colour) == (rb, bpp)
@@ -243,7 +235,7 @@ def test_pixels_to_files_at_every_width_class(geometry):
         for o, im in zip(p_off[:-1], imgs):
             pix[int(o):int(o) + im.size] = im.reshape(-1)
         d_file = torch.full((int(f_off[-1]) + 64,), FILL, dtype=torch.uint8, device="cuda")
-        file_len, st, ty = fd.png_encode_files_batch(_dev(pix), _dev(p_off), d_file, _dev(f_off), rb // bpp, depth, colour)
+        file_len, st, ty = fd.png_encode_files_batch(gh.dev(pix), gh.dev(p_off), d_file, gh.dev(f_off), rb // bpp, depth, colour)
         torch.cuda.synchronize()
         got = d_file.cpu().numpy()
         bad = [i for i in range(n) if rows[i] == 0 or i in small]
@@ -282,7 +274,7 @@ def test_last_slot_too_small_and_frame_alone():
         slots = [fd.png_file_bound(9, rb), fd.png_file_bound(30, rb), last]
         f_off = np.concatenate([[1], 1 + np.cumsum(slots)]).astype(np.int64)
         d_file = torch.full((int(f_off[-1]) + 100,), FILL, dtype=torch.uint8, device="cuda")
-        file_len, st, _ = fd.png_encode_files_batch(_dev(pix), _dev(p_off), d_file, _dev(f_off), 100, 8, 2)
+        file_len, st, _ = fd.png_encode_files_batch(gh.dev(pix), gh.dev(p_off), d_file, gh.dev(f_off), 100, 8, 2)
         torch.cuda.synchronize()
         got = d_file.cpu().numpy()
         assert st.cpu().tolist() == [0, 0, 2] and _u32(file_len)[2] == 0
@@ -290,7 +282,7 @@ def test_last_slot_too_small_and_frame_alone():
         assert (got[int(f_off[2]):int(f_off[2]) + min(41, last)] == FILL).all(), last
         for i in range(2):
             f = got[int(f_off[i]):int(f_off[i]) + int(_u32(file_len)[i])].tobytes()
-            assert tm.pillow_view(f)[2] == imgs[i].tobytes()
+            assert pc.pillow_view(f)[2] == imgs[i].tobytes()
     # the framing call alone
     L = _lib.lib()
     stream = zlib.compress(bytes(5 * 31), 1)
@@ -300,12 +292,12 @@ def test_last_slot_too_small_and_frame_alone():
     host = np.full(int(f_off[-1]) + 40, FILL, dtype=np.uint8)
     for o in f_off[:-1]:
         host[int(o) + 41:int(o) + 41 + len(stream)] = np.frombuffer(stream, dtype=np.uint8)
-    d_file = _dev(host)
-    idat_len = _dev(np.array([len(stream), 0, 0xFFFFFFFF, 0x80000000, len(stream), len(stream)], dtype=np.uint32).view(np.int32))
-    height = _dev(np.array([5, 5, 5, 5, 0, 5], dtype=np.uint32).view(np.int32))
+    d_file = gh.dev(host)
+    idat_len = gh.dev(np.array([len(stream), 0, 0xFFFFFFFF, 0x80000000, len(stream), len(stream)], dtype=np.uint32).view(np.int32))
+    height = gh.dev(np.array([5, 5, 5, 5, 0, 5], dtype=np.uint32).view(np.int32))
     lw, flen = _guarded(6)
     sw, st = _guarded(6)
-    d_off = _dev(f_off)
+    d_off = gh.dev(f_off)
     args = [C.c_void_p(t.data_ptr()) for t in (d_file, d_off, idat_len, height, flen, st)]
     for width, depth, colour in ((0, 8, 0), (1 << 31, 8, 0), (30, 3, 0), (30, 16, 3), (30, 8, 7)):
         assert L.fdh_png_frame_batch(*args, 6, width, depth, colour, None) == 1
@@ -321,24 +313,10 @@ def test_last_slot_too_small_and_frame_alone():
     want = host.copy()
     want[3:3 + slot] = np.frombuffer(fm.write_file(stream, 30, 5, 8, 0), dtype=np.uint8)
     assert np.array_equal(got, want)
-    assert tm.pillow_view(got[3:3 + slot].tobytes()) == ("L", (30, 5), bytes(150))
+    assert pc.pillow_view(got[3:3 + slot].tobytes()) == ("L", (30, 5), bytes(150))
 
 
 # ---- files -> pixels ----
-
-def _batch_of(files, front=5, slack=3):
-    """Files one behind the other from byte `front`, `slack` fill bytes inside every slot behind the file."""
-    f_off = np.concatenate([[front], front + np.cumsum([len(f) + slack for f in files])]).astype(np.int64)
-    host = np.full(int(f_off[-1]) + 16, FILL, dtype=np.uint8)
-    for o, f in zip(f_off[:-1], files):
-        host[int(o):int(o) + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    return host, f_off, np.array([len(f) for f in files], dtype=np.uint32).view(np.int32)
-
-
-def _info_rows(fd, info):
-    f = fd.png_info_fields(info)
-    return [tuple(int(f[k][i]) for k in fm.Info.FIELDS) for i in range(len(f["status"]))]
-
 
 def test_pillow_files_to_pixels():
     """Every file of the Pillow-written corpus (level-6 streams in three or more IDAT chunks behind tEXt, pHYs and PLTE
@@ -346,14 +324,14 @@ def test_pillow_files_to_pixels():
     statuses are 0, the pixels are the ones Pillow shows."""
     import torch
     import fdeflate_amd as fd
-    for name, png, width, height, depth, colour, pixels in tm.pillow_corpus():
+    for name, png, width, height, depth, colour, pixels in pc.pillow_corpus():
         want_info = fm.scan(png, crc=zlib.crc32).fields()
-        host, f_off, f_len = _batch_of([png] * 3)
+        host, f_off, f_len = gh.batch_of([png] * 3, fill=FILL)
         for with_len in (True, False):
-            pix, pix_off, info, status, png_status = fd.png_decode_files_batch(_dev(host), _dev(f_off), width, depth, colour,
-                                                                               file_len=_dev(f_len) if with_len else None)
+            pix, pix_off, info, status, png_status = fd.png_decode_files_batch(gh.dev(host), gh.dev(f_off), width, depth, colour,
+                                                                               file_len=gh.dev(f_len) if with_len else None)
             torch.cuda.synchronize()
-            assert _info_rows(fd, info) == [want_info] * 3, (name, with_len)
+            assert gh.info_rows(fd, info) == [want_info] * 3, (name, with_len)
             assert status.cpu().tolist() == [0] * 3 and png_status.cpu().tolist() == [0] * 3, name
             assert pix_off.cpu().tolist() == [k * len(pixels) for k in range(4)]
             assert pix.cpu().numpy().tobytes() == pixels * 3, (name, with_len)
@@ -373,15 +351,15 @@ def test_own_files_to_pixels(geometry):
         p_off = np.concatenate([[0], np.cumsum([im.size for im in imgs])]).astype(np.int64)
         f_off = np.concatenate([[9], 9 + np.cumsum([fd.png_file_bound(im.shape[0], rb) for im in imgs])]).astype(np.int64)
         d_file = torch.full((int(f_off[-1]) + 16,), FILL, dtype=torch.uint8, device="cuda")
-        file_len, st, _ = fd.png_encode_files_batch(_dev(np.concatenate([im.reshape(-1) for im in imgs])), _dev(p_off), d_file,
-                                                    _dev(f_off), rb // bpp, depth, colour)
+        file_len, st, _ = fd.png_encode_files_batch(gh.dev(np.concatenate([im.reshape(-1) for im in imgs])), gh.dev(p_off), d_file,
+                                                    gh.dev(f_off), rb // bpp, depth, colour)
         assert st.cpu().tolist() == [0] * n
-        pix, pix_off, info, status, png_status = fd.png_decode_files_batch(d_file, _dev(f_off), rb // bpp, depth, colour, file_len=file_len)
+        pix, pix_off, info, status, png_status = fd.png_decode_files_batch(d_file, gh.dev(f_off), rb // bpp, depth, colour, file_len=file_len)
         torch.cuda.synchronize()
         got = d_file.cpu().numpy()
         lens = _u32(file_len)
         want = [fm.scan(got[int(o):int(o) + int(m)].tobytes(), crc=zlib.crc32).fields() for o, m in zip(f_off[:-1], lens)]
-        assert _info_rows(fd, info) == want and all(w[0] == 0 and w[1:3] == (rb // bpp, im.shape[0]) for w, im in zip(want, imgs))
+        assert gh.info_rows(fd, info) == want and all(w[0] == 0 and w[1:3] == (rb // bpp, im.shape[0]) for w, im in zip(want, imgs))
         assert status.cpu().tolist() == [0] * n and png_status.cpu().tolist() == [0] * n
         assert pix_off.cpu().tolist() == p_off.tolist()
         assert pix.cpu().numpy().tobytes() == b"".join(im.tobytes() for im in imgs), (geometry, rb)
@@ -389,11 +367,11 @@ def test_own_files_to_pixels(geometry):
 
 def _mixed_batch():
     """Good files of one geometry between one file of every kind of damage, and one good file of another geometry."""
-    corpus = tm.pillow_corpus()
+    corpus = pc.pillow_corpus()
     name, png, width, height, depth, colour, pixels = corpus[1]
     other = corpus[4][1]
     files, expect = [png], [(0, 0, 0)]        # (info.status, the same ignoring CRCs, png_status of the decode)
-    for what, f, status, status_ignoring, _ in tm.damaged_files(png):
+    for what, f, status, status_ignoring, _ in pc.damaged_files(png):
         files += [f, png]
         expect += [(status, status_ignoring, 3), (0, 0, 0)]
     files += [other, png]
@@ -410,12 +388,12 @@ def test_mixed_batch_every_status():
     import fdeflate_amd as fd
     files, expect, (width, depth, colour), pixels, png = _mixed_batch()
     assert {e[0] for e in expect} == {0, 1, 2, 3, 4, 5, 6}
-    host, f_off, f_len = _batch_of(files)
-    d_file = _dev(host)
+    host, f_off, f_len = gh.batch_of(files, fill=FILL)
+    d_file = gh.dev(host)
     for flags in (0, fd.PNG_FLAG_IGNORE_CRC):
-        pix, pix_off, info, status, png_status = fd.png_decode_files_batch(d_file, _dev(f_off), width, depth, colour, file_len=_dev(f_len), flags=flags)
+        pix, pix_off, info, status, png_status = fd.png_decode_files_batch(d_file, gh.dev(f_off), width, depth, colour, file_len=gh.dev(f_len), flags=flags)
         torch.cuda.synchronize()
-        rows = _info_rows(fd, info)
+        rows = gh.info_rows(fd, info)
         assert rows == [fm.scan(f, ignore_crc=bool(flags), crc=zlib.crc32).fields() for f in files]
         assert [w[0] for w in rows] == [e[1] if flags else e[0] for e in expect]
         got_pix, off = pix.cpu().numpy().tobytes(), pix_off.cpu().tolist()
@@ -441,9 +419,9 @@ def test_gather_slots_and_guards():
     import torch
     import fdeflate_amd as fd
     files, expect, (width, depth, colour), pixels, png = _mixed_batch()
-    host, f_off, f_len = _batch_of(files)
-    d_file, d_off = _dev(host), _dev(f_off)
-    info = fd.png_scan_files_batch(d_file, d_off, _dev(f_len))
+    host, f_off, f_len = gh.batch_of(files, fill=FILL)
+    d_file, d_off = gh.dev(host), gh.dev(f_off)
+    info = fd.png_scan_files_batch(d_file, d_off, gh.dev(f_len))
     model = [fm.scan(f, crc=zlib.crc32) for f in files]
     sound = [i for i, e in enumerate(expect) if e == (0, 0, 0)]
     short, empty = sound[1], sound[3]
@@ -462,7 +440,7 @@ def test_gather_slots_and_guards():
     comp = torch.full((want.size,), FILL, dtype=torch.uint8, device="cuda")
     lw, comp_len = _guarded(len(files))
     sw, st = _guarded(len(files))
-    fd.png_gather_idat_batch(d_file, d_off, info, comp, _dev(c_off), width, depth, colour, comp_len=comp_len, png_status=st)
+    fd.png_gather_idat_batch(d_file, d_off, info, comp, gh.dev(c_off), width, depth, colour, comp_len=comp_len, png_status=st)
     torch.cuda.synchronize()
     assert _u32(st).tolist() == want_st and _u32(comp_len).tolist() == want_len
     assert _guards_intact(lw, len(files)) and _guards_intact(sw, len(files))
@@ -500,14 +478,14 @@ def test_round_trip_of_4096_images():
     assert int(status.abs().sum()) == 0 and int(png_status.abs().sum()) == 0 and int(info[:, 0].abs().sum()) == 0
     assert torch.equal(back_off, p_off) and torch.equal(back, pix)
     lens = _u32(file_len)
-    rows_info = _info_rows(fd, info)
+    rows_info = gh.info_rows(fd, info)
     opened = 0
     for k in range(5, n, 64):
         f = d_file[k * slot + 1:k * slot + 1 + int(lens[k])].cpu().numpy().tobytes()
-        assert [t for t, _ in tm.chunks_of(f)] == [b"IHDR", b"IDAT", b"IEND"]       # (chunks_of checks every CRC with zlib)
+        assert [t for t, _ in pc.chunks_of(f)] == [b"IHDR", b"IDAT", b"IEND"]       # (chunks_of checks every CRC with zlib)
         assert rows_info[k] == fm.scan(f, crc=zlib.crc32).fields() == (0, width, rows, 8, 6, 0, len(f) - 57, 1, 33, 3)
         if k % 512 == 5:
-            assert tm.pillow_view(f) == ("RGBA", (width, rows), pix[k * rows * rb:(k + 1) * rows * rb].cpu().numpy().tobytes())
+            assert pc.pillow_view(f) == ("RGBA", (width, rows), pix[k * rows * rb:(k + 1) * rows * rb].cpu().numpy().tobytes())
             opened += 1
     assert opened == 8
     assert d_file[0].item() == FILL and d_file[-1].item() == FILL

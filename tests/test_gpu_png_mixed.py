@@ -16,28 +16,20 @@ import numpy as np
 import pytest
 
 import png_adam7_model as am
+import png_corpus as pc
 import png_expand_model as em
 import png_file_model as fm
+import png_gpu_harness as gh
 import png_mixed_model as mm
 import png_model as pm
-import test_png_expand_model as xm
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 0x5A
 PASSED_ON = 77
-WIDTHS = tuple(range(1, 10)) + (31, 32, 33, 63, 64, 65, 255, 256, 257, 1023)     # those of tests/test_gpu_png_expand.py
+WIDTHS = gh.EXPAND_WIDTHS
 HEIGHTS = (1, 2, 3, 9, 65)                                                        # 65: one band of 64 rows plus a row
 PALETTE_SIZES = (1, 2, 16, 17, 255, 256)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _i32(values):
-    return _dev(np.asarray(values, dtype=np.uint32).view(np.int32))
 
 
 # ---- images ----
@@ -117,7 +109,7 @@ class Call:
         self.filt = np.full(int(self.f_off[-1]) + 9, GUARD, dtype=np.uint8)
         for o, e in zip(self.f_off[:-1], seq):
             self.filt[int(o):int(o) + len(e.filt)] = e.filt
-        self.info = _i32([mm.words(e.rec) for e in seq]).view(-1, 8) if seq else _i32(np.zeros((0, 8)))
+        self.info = gh.words([mm.words(e.rec) for e in seq]).view(-1, 8) if seq else gh.words(np.zeros((0, 8)))
         self.pal = np.full((self.n, 256), 0x5A5A5A5A, dtype=np.uint32)
         for k, e in enumerate(seq):
             if e.pal is not None:
@@ -127,12 +119,12 @@ class Call:
     def unfilter(self, fd, gates=True):
         """-> (status list, pix buffer on the host); checks the guard bytes around the slots and the status array's."""
         import torch
-        d_filt = _dev(self.filt)
+        d_filt = gh.dev(self.filt)
         d_pix = torch.full((int(self.p_off[-1]) + 33,), GUARD, dtype=torch.uint8, device="cuda")
         st = torch.full((self.n + 16,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-        fd.png_unfilter_mixed_batch(d_filt, _dev(self.f_off), d_pix, _dev(self.p_off), self.info,
-                                    upstream=_i32([e.upstream for e in self.seq]),
-                                    upstream_len=_i32([e.upstream_len for e in self.seq]) if gates else None, png_status=st[8:8 + self.n])
+        fd.png_unfilter_mixed_batch(d_filt, gh.dev(self.f_off), d_pix, gh.dev(self.p_off), self.info,
+                                    upstream=gh.words([e.upstream for e in self.seq]),
+                                    upstream_len=gh.words([e.upstream_len for e in self.seq]) if gates else None, png_status=st[8:8 + self.n])
         torch.cuda.synchronize()
         st, got, after = st.cpu().numpy(), d_pix.cpu().numpy(), d_filt.cpu().numpy()
         assert (st[:8] == 0x5A5A5A5A).all() and (st[8 + self.n:] == 0x5A5A5A5A).all()
@@ -146,9 +138,9 @@ class Call:
         import torch
         d_rgba = torch.full((int(self.r_off[-1]) + 33,), GUARD, dtype=torch.uint8, device="cuda")
         st = torch.full((self.n + 16,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-        fd.png_expand_mixed_batch(_dev(pix), _dev(self.p_off), d_rgba, _dev(self.r_off), self.info,
-                                  pal=_dev(self.pal.view(np.int32)) if pal else None, colour=_dev(self.col.view(np.int32)) if colour else None,
-                                  upstream=_i32([e.upstream for e in self.seq]), png_status=st[8:8 + self.n])
+        fd.png_expand_mixed_batch(gh.dev(pix), gh.dev(self.p_off), d_rgba, gh.dev(self.r_off), self.info,
+                                  pal=gh.dev(self.pal.view(np.int32)) if pal else None, colour=gh.dev(self.col.view(np.int32)) if colour else None,
+                                  upstream=gh.words([e.upstream for e in self.seq]), png_status=st[8:8 + self.n])
         torch.cuda.synchronize()
         st, got = st.cpu().numpy(), d_rgba.cpu().numpy()
         assert (st[:8] == 0x5A5A5A5A).all() and (st[8 + self.n:] == 0x5A5A5A5A).all()
@@ -182,11 +174,11 @@ def by_geometry(fd, images):
         r_off = np.concatenate([[0], np.cumsum([e.rgba_size for e in es], dtype=np.int64)]).astype(np.int64)
         d_pix = torch.zeros(max(1, int(p_off[-1])), dtype=torch.uint8, device="cuda")
         d_rgba = torch.zeros(max(1, int(r_off[-1])), dtype=torch.uint8, device="cuda")
-        st_u = fd.png_unfilter_interlaced_batch(_dev(np.concatenate([e.filt for e in es])), _dev(f_off), d_pix, _dev(p_off), width, depth, colour,
-                                                method=_dev(np.array([e.rec["interlace"] for e in es], dtype=np.uint8)))
-        pal = _dev(np.stack([e.pal for e in es]).view(np.int32)) if colour == 3 else None
-        st_e = fd.png_expand_batch(d_pix, _dev(p_off), d_rgba, _dev(r_off), width, depth, colour, pal=pal,
-                                   colour=_dev(np.array([e.col for e in es], dtype=np.uint32).view(np.int32)))
+        st_u = fd.png_unfilter_interlaced_batch(gh.dev(np.concatenate([e.filt for e in es])), gh.dev(f_off), d_pix, gh.dev(p_off), width, depth, colour,
+                                                method=gh.dev(np.array([e.rec["interlace"] for e in es], dtype=np.uint8)))
+        pal = gh.dev(np.stack([e.pal for e in es]).view(np.int32)) if colour == 3 else None
+        st_e = fd.png_expand_batch(d_pix, gh.dev(p_off), d_rgba, gh.dev(r_off), width, depth, colour, pal=pal,
+                                   colour=gh.dev(np.array([e.col for e in es], dtype=np.uint32).view(np.int32)))
         torch.cuda.synchronize()
         st_u, st_e, pix, rgba = st_u.cpu().tolist(), st_e.cpu().tolist(), d_pix.cpu().numpy(), d_rgba.cpu().numpy()
         for j, k in enumerate(members):
@@ -478,7 +470,7 @@ def test_plan_on_the_device_is_the_model():
         by_limit.setdefault(m, []).append(rec)
     assert 0 in by_limit and len(by_limit) > 10
     for m, recs in by_limit.items():
-        info = _i32([mm.words(x) for x in recs]).view(-1, 8)
+        info = gh.words([mm.words(x) for x in recs]).view(-1, 8)
         want = np.array([mm.plan(x, m) for x in recs], dtype=np.uint64)
         combos = range(16) if m == 0 else (15, 5)
         for mask in combos:
@@ -495,30 +487,22 @@ def test_plan_on_the_device_is_the_model():
 
 # ---- files ----
 
-def _batch_of(files, front=5, slack=3):
-    f_off = np.concatenate([[front], front + np.cumsum([len(f) + slack for f in files])]).astype(np.int64)
-    host = np.full(int(f_off[-1]) + 16, 0xEE, dtype=np.uint8)
-    for o, f in zip(f_off[:-1], files):
-        host[int(o):int(o) + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    return host, f_off, np.array([len(f) for f in files], dtype=np.uint32).view(np.int32)
-
-
 def test_colour_mixed_batch_every_status():
-    """The files of test_png_expand_model.status_files, each read at ITS geometry: the model's status (0, 3, 10, 11), pal
+    """The files of png_corpus.status_files, each read at ITS geometry: the model's status (0, 3, 10, 11), pal
     and colour word for word; the pal rows of files that are not of colour type 3 keep the guard pattern; upstream passes."""
     import torch
     import fdeflate_amd as fd
-    cases = [c for c in xm.status_files() if c[3] != 7]
+    cases = [c for c in pc.status_files() if c[3] != 7]
     files = [c[1] for c in cases]
-    host, f_off, f_len = _batch_of(files)
-    d_file, d_off = _dev(host), _dev(f_off)
-    info = fd.png_scan_files_batch(d_file, d_off, _dev(f_len))
+    host, f_off, f_len = gh.batch_of(files)
+    d_file, d_off = gh.dev(host), gh.dev(f_off)
+    info = fd.png_scan_files_batch(d_file, d_off, gh.dev(f_len))
     n, seen = len(files), set()
     upstream = [15 if k == 4 else 0 for k in range(n)]
     pal = torch.full((n + 2, 256), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     col = torch.full((n + 2, 4), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     st = torch.full((n + 2,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
-    fd.png_colour_mixed_batch(d_file, d_off, info, upstream=_i32(upstream), pal=pal[1:n + 1], colour=col[1:n + 1], png_status=st[1:n + 1])
+    fd.png_colour_mixed_batch(d_file, d_off, info, upstream=gh.words(upstream), pal=pal[1:n + 1], colour=col[1:n + 1], png_status=st[1:n + 1])
     torch.cuda.synchronize()
     pal, col, st = (t.cpu().numpy().view(np.uint32) for t in (pal, col, st))
     for t in (pal, col, st):
@@ -560,7 +544,7 @@ def _rewrite(f, r, method, idat_chunks, pre_extra=()):
     w, h, d, c, pix = am.decode(f)
     info = am.scan(f, adam7=True, crc=zlib.crc32)
     _, pal, key = em.read_colour(f, info, w, d, c)
-    pre = list(pre_extra) + xm.pre_chunks(c, key, pal)
+    pre = list(pre_extra) + pc.pre_chunks(c, key, pal)
     if method:
         idat = am.stream_of(bytes(pix), w, h, d, c, r.integers(0, 5, am.pass_rows(w, h)).tolist())
     else:
@@ -591,12 +575,12 @@ def collection():
     for d, c in fm.PAIRS:
         for method in (0, 1):
             w, h = 1 + (5 * k) % 41, 1 + (3 * k) % 11
-            keyed = (d, c) in xm.KEYED or (d, c) in xm.LEFT_OUT
-            pix, key, pal = xm.random_case(r, w, h, d, c, keyed and k % 2 == 0)
+            keyed = (d, c) in pc.KEYED or (d, c) in pc.LEFT_OUT
+            pix, key, pal = pc.random_case(r, w, h, d, c, keyed and k % 2 == 0)
             types = r.integers(0, 5, am.pass_rows(w, h) if method else h).tolist()
             rb, bpp = fm.geometry(w, d, c)
             idat = am.stream_of(pix.tobytes(), w, h, d, c, types) if method else zlib.compress(pm.filter_rows(pix.reshape(h, rb), bpp, types).tobytes())
-            out.append((am.write_file(idat, w, h, d, c, xm.pre_chunks(c, key, pal, text=k % 4 == 0), 1 + k % 3, zlib.crc32, method=method),
+            out.append((am.write_file(idat, w, h, d, c, pc.pre_chunks(c, key, pal, text=k % 4 == 0), 1 + k % 3, zlib.crc32, method=method),
                         "model depth %d colour %d method %d" % (d, c, method)))
             k += 1
     sound = out[4][0]
@@ -627,11 +611,11 @@ def test_gather_mixed_batch(collection):
     want_st = [3 if m.status else 8 if k == short else 15 if k == passed else 0 for k, m in enumerate(infos)]
     sizes = [0 if m.status else len(m.idat) - (k == short) for k, m in enumerate(infos)]
     c_off = np.concatenate([[3], 3 + np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
-    host, f_off, f_len = _batch_of(files)
-    d_file, d_off = _dev(host), _dev(f_off)
-    info = fd.png_scan_files_batch(d_file, d_off, _dev(f_len), flags=fd.PNG_FLAG_ADAM7)
+    host, f_off, f_len = gh.batch_of(files)
+    d_file, d_off = gh.dev(host), gh.dev(f_off)
+    info = fd.png_scan_files_batch(d_file, d_off, gh.dev(f_len), flags=fd.PNG_FLAG_ADAM7)
     comp = torch.full((int(c_off[-1]) + 40,), GUARD, dtype=torch.uint8, device="cuda")
-    comp_len, st = fd.png_gather_idat_mixed_batch(d_file, d_off, info, comp, _dev(c_off), upstream=_i32([15 if k == passed else 0 for k in range(len(files))]))
+    comp_len, st = fd.png_gather_idat_mixed_batch(d_file, d_off, info, comp, gh.dev(c_off), upstream=gh.words([15 if k == passed else 0 for k in range(len(files))]))
     torch.cuda.synchronize()
     assert st.cpu().tolist() == want_st and {0, 3, 8, 15} == set(want_st)
     got, lens = comp.cpu().numpy(), comp_len.cpu().tolist()
@@ -666,10 +650,10 @@ def test_files_end_to_end(collection):
     models = [_model_of(f, what) for f, what in collection]
     assert {m[0] for m in models} == {0, 2, 3} and sum(1 for m in models if m[0] == 0) >= 40
     for (f, what), m in zip(collection, models):                 # Pillow, where it follows the specification
-        if m[0] == 0 and (m[3][2], m[3][3]) not in xm.LEFT_OUT:
-            assert xm.pillow_rgba(f) == m[2], what
-    host, f_off, f_len = _batch_of(files)
-    d_file, d_off, d_len = _dev(host), _dev(f_off), _dev(f_len)
+        if m[0] == 0 and (m[3][2], m[3][3]) not in pc.LEFT_OUT:
+            assert pc.pillow_rgba(f) == m[2], what
+    host, f_off, f_len = gh.batch_of(files)
+    d_file, d_off, d_len = gh.dev(host), gh.dev(f_off), gh.dev(f_len)
     torch.cuda.reset_peak_memory_stats()
     before = torch.cuda.memory_allocated()
     rgba, rgba_off, info, status, png_status = fd.png_decode_mixed_files_rgba_batch(d_file, d_off, d_len, flags=fd.PNG_FLAG_ADAM7, max_bytes=1 << 28)
@@ -721,8 +705,8 @@ def test_routes_give_the_same_tensors():
     import torch
     import fdeflate_amd as fd
     files, geometry = _uniform_batch()
-    host, f_off, f_len = _batch_of(files)
-    d_file, d_off, d_len = _dev(host), _dev(f_off), _dev(f_len)
+    host, f_off, f_len = gh.batch_of(files)
+    d_file, d_off, d_len = gh.dev(host), gh.dev(f_off), gh.dev(f_len)
     for decode, parent in ((fd.png_decode_mixed_files_rgba_batch, fd.png_decode_files_rgba_batch), (fd.png_decode_mixed_files_batch, fd.png_decode_files_batch)):
         mixed = decode(d_file, d_off, d_len, route="mixed")
         uniform = decode(d_file, d_off, d_len, route="uniform")
@@ -738,11 +722,11 @@ def test_routes_give_the_same_tensors():
 
 def test_route_uniform_refuses_a_mixed_batch(collection):
     import fdeflate_amd as fd
-    host, f_off, f_len = _batch_of([f for f, _ in collection[:12]])
+    host, f_off, f_len = gh.batch_of([f for f, _ in collection[:12]])
     with pytest.raises(ValueError):
-        fd.png_decode_mixed_files_rgba_batch(_dev(host), _dev(f_off), _dev(f_len), route="uniform")
+        fd.png_decode_mixed_files_rgba_batch(gh.dev(host), gh.dev(f_off), gh.dev(f_len), route="uniform")
     with pytest.raises(ValueError):
-        fd.png_decode_mixed_files_batch(_dev(host), _dev(f_off), _dev(f_len), route="sideways")
+        fd.png_decode_mixed_files_batch(gh.dev(host), gh.dev(f_off), gh.dev(f_len), route="sideways")
 
 
 # ---- the read-back ----
@@ -755,8 +739,8 @@ def test_one_read_back_of_at_most_64_bytes(route, monkeypatch):
     import fdeflate_amd as fd
     from fdeflate_amd import api
     files, _ = _uniform_batch()
-    host, f_off, f_len = _batch_of(files)
-    d_file, d_off, d_len = _dev(host), _dev(f_off), _dev(f_len)
+    host, f_off, f_len = gh.batch_of(files)
+    d_file, d_off, d_len = gh.dev(host), gh.dev(f_off), gh.dev(f_len)
     moved, stray = [], []
     inner = api._read_back
 

@@ -14,50 +14,16 @@ import zlib
 import numpy as np
 import pytest
 
+import png_corpus as pc
 import png_expand_model as em
 import png_file_model as fm
+import png_gpu_harness as gh
 import png_pack_model as pm
-import test_png_expand_model as xm
-import test_png_pack_model as tp
+from png_gpu_harness import GUARD, HEIGHTS, PASSED_ON
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0x5A
 GUARD_WORD = 0x5A5A5A5A
-BAND = 64
-# either side of a byte of 1-bit pixels, a lane's four pixels, a 16-byte load, a wavefront's 256 pixels; the bench row
-WIDTHS = tuple(range(1, 10)) + (31, 32, 33, 63, 64, 65, 255, 256, 257, 1023)
-HEIGHTS = (1, 2, 3, BAND + 1)
-PASSED_ON = 77          # an upstream status: such slots are the guards between the images
-UNIT = {1: 255, 2: 85, 4: 17, 8: 1, 16: 1}
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _words(rows):
-    return _dev(np.asarray(rows, dtype=np.uint32).view(np.int32))
-
-
-def _waves(monkeypatch, name, waves):
-    if waves is None:
-        monkeypatch.delenv(name, raising=False)
-    else:
-        monkeypatch.setenv(name, str(waves))
-
-
-def random_rgba(r, width, height, depth, colour):
-    """Random pixel words (uint32 [height * width]) that the pair holds without loss (not colour type 3)."""
-    n = width * height
-    if colour in (0, 4):
-        g = r.integers(0, 1 << min(depth, 8), n).astype(np.uint32) * UNIT[depth]
-        rgb = g * 0x010101
-    else:
-        rgb = r.integers(0, 1 << 24, n).astype(np.uint32)
-    alpha = r.integers(0, 256, n).astype(np.uint32) if colour in (4, 6) else np.full(n, 255, dtype=np.uint32)
-    return rgb | alpha << 24
 
 
 def random_palette(r, depth, duplicates=True):
@@ -117,13 +83,13 @@ class Batch:
     def run(self, fd):
         """-> (packed buffer on the device, png_status) after one call; the input must not change."""
         import torch
-        d_rgba = _dev(self.rgba)
+        d_rgba = gh.dev(self.rgba)
         pix = torch.full((self.expect.size,), GUARD, dtype=torch.uint8, device="cuda")
         st = torch.full((self.n + 16,), GUARD_WORD, dtype=torch.int32, device="cuda")
-        fd.png_pack_batch(d_rgba, _dev(self.s_off), pix, _dev(self.p_off), *self.geometry,
-                          pal=None if self.pal is None else _words(self.pal),
-                          colour=None if self.colour is None else _words(self.colour),
-                          upstream=_words(self.upstream), png_status=st[8:8 + self.n])
+        fd.png_pack_batch(d_rgba, gh.dev(self.s_off), pix, gh.dev(self.p_off), *self.geometry,
+                          pal=None if self.pal is None else gh.words(self.pal),
+                          colour=None if self.colour is None else gh.words(self.colour),
+                          upstream=gh.words(self.upstream), png_status=st[8:8 + self.n])
         torch.cuda.synchronize()
         assert np.array_equal(d_rgba.cpu().numpy(), self.rgba)
         st = st.cpu().numpy()
@@ -146,10 +112,10 @@ class Batch:
             sizes = np.diff(self.s_off)
             b_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
             back = torch.full((int(b_off[-1]) + 16,), GUARD, dtype=torch.uint8, device="cuda")
-            est = fd.png_expand_batch(pix, _dev(self.p_off), back, _dev(b_off), *self.geometry,
-                                      pal=None if self.pal is None else _words(self.pal),
-                                      colour=None if self.colour is None else _words(self.colour),
-                                      upstream=_words(st))
+            est = fd.png_expand_batch(pix, gh.dev(self.p_off), back, gh.dev(b_off), *self.geometry,
+                                      pal=None if self.pal is None else gh.words(self.pal),
+                                      colour=None if self.colour is None else gh.words(self.colour),
+                                      upstream=gh.words(st))
             torch.cuda.synchronize()
             assert est.cpu().tolist() == st, what
             back = back.cpu().numpy()
@@ -162,25 +128,25 @@ class Batch:
 
 @pytest.mark.parametrize("pair", fm.PAIRS, ids=["depth%d-colour%d" % p for p in fm.PAIRS])
 def test_pack_every_width_and_height(pair, monkeypatch):
-    """Every width of WIDTHS at heights 1, 2, 3 and one more than a band, four images a call: the packed buffer equals
+    """Every width of gh.PACK_WIDTHS at heights 1, 2, 3 and one more than a band, four images a call: the packed buffer equals
     the model's byte for byte (padding bits zero), guard slots and the bytes behind the last slot included, the input is
     unchanged, every status is right, and fdh_png_expand_batch takes the packed rows back to the input on the device.
     Palettes are unsorted and hold duplicates.  Each batch runs with 1, 2 and 5 wavefronts per image and the default."""
     import fdeflate_amd as fd
     depth, colour = pair
     r = np.random.default_rng(9500 + 64 * colour + depth)
-    for width in WIDTHS:
+    for width in gh.PACK_WIDTHS:
         images = []
         for h in HEIGHTS:
             if colour == 3:
                 pal = random_palette(r, depth)
                 images.append((palette_pixels(r, pal, pal.size, width * h), pal, pal.size))
             else:
-                images.append((random_rgba(r, width, h, depth, colour), None, 256))
+                images.append((gh.random_rgba(r, width, h, depth, colour), None, 256))
         b = Batch(images, width, depth, colour)
         assert b.want_status[0::2] == [0] * len(images)
         for waves in (1, 2, 5, None):
-            _waves(monkeypatch, "FDH_PNG_PACK_WAVES", waves)
+            gh.set_env(monkeypatch, FDH_PNG_PACK_WAVES=waves)
             b.check(fd, (pair, width, waves), round_trip=waves in (2, None))
 
 
@@ -220,7 +186,7 @@ def test_not_representable_wherever_it_sits(pair):
             reasons += [("R != G", 0xFF000011), ("G != B", 0xFF110000)]
         if colour == 0 and depth < 8:
             reasons.append(("not a multiple of the unit", {4: 0xFF808080, 2: 0xFF111111, 1: 0xFF555555}[depth]))
-        base = lambda: (random_rgba(r, width, height, depth, colour), None, 256)
+        base = lambda: (gh.random_rgba(r, width, height, depth, colour), None, 256)
     if not reasons:
         assert colour == 6                          # (RGBA holds everything)
         return
@@ -278,7 +244,7 @@ def test_pack_slots_that_do_not_fit_and_upstream():
         rgba = np.full(int(s_off[-1]) + 3, GUARD, dtype=np.uint8)
         expect = np.full(int(p_off[-1]) + 32, GUARD, dtype=np.uint8)
         for k, (sb, pb, up, want) in enumerate(plan):
-            px = palette_pixels(r, pal, pal.size, sb // 4) if colour == 3 else random_rgba(r, sb // 4, 1, depth, colour)
+            px = palette_pixels(r, pal, pal.size, sb // 4) if colour == 3 else gh.random_rgba(r, sb // 4, 1, depth, colour)
             rgba[s_off[k]:s_off[k] + 4 * px.size] = px.view(np.uint8)
             if want == 0 and sb:
                 packed, st = pm.pack(px.view(np.uint8), width, depth, colour, None if pal is None else pal.tolist(), 1 << depth)
@@ -286,9 +252,9 @@ def test_pack_slots_that_do_not_fit_and_upstream():
                 expect[p_off[k]:p_off[k + 1]] = np.frombuffer(packed, dtype=np.uint8)
         n = len(plan)
         pix = torch.full((expect.size,), GUARD, dtype=torch.uint8, device="cuda")
-        pal_words = None if pal is None else _words([np.concatenate([pal, np.zeros(256 - pal.size, dtype=np.uint32)]).tolist()] * n)
-        st = fd.png_pack_batch(_dev(rgba), _dev(s_off), pix, _dev(p_off), width, depth, colour, pal=pal_words,
-                               colour=None if pal is None else _words([[pal.size, 0, 0, 0]] * n), upstream=_words([p[2] for p in plan]))
+        pal_words = None if pal is None else gh.words([np.concatenate([pal, np.zeros(256 - pal.size, dtype=np.uint32)]).tolist()] * n)
+        st = fd.png_pack_batch(gh.dev(rgba), gh.dev(s_off), pix, gh.dev(p_off), width, depth, colour, pal=pal_words,
+                               colour=None if pal is None else gh.words([[pal.size, 0, 0, 0]] * n), upstream=gh.words([p[2] for p in plan]))
         torch.cuda.synchronize()
         assert st.cpu().numpy().view(np.uint32).tolist() == [p[3] for p in plan], (depth, colour)
         assert np.array_equal(pix.cpu().numpy(), expect), (depth, colour)
@@ -304,16 +270,16 @@ def test_pack_more_images_than_wavefronts_fill():
     for (depth, colour), width, rows in (((2, 3), 7, 3), ((16, 4), 5, 2), ((1, 0), 3, 5)):
         rb = fm.geometry(width, depth, colour)[0]
         pal = random_palette(r, depth, duplicates=False) if colour == 3 else None
-        px = palette_pixels(r, pal, pal.size, n * rows * width) if colour == 3 else random_rgba(r, width, n * rows, depth, colour)
+        px = palette_pixels(r, pal, pal.size, n * rows * width) if colour == 3 else gh.random_rgba(r, width, n * rows, depth, colour)
         want, st = pm.pack(px.view(np.uint8), width, depth, colour, None if pal is None else pal.tolist(), 4)     # (the images one below the other)
         assert st == 0
         s_off = 1 + np.arange(n + 1, dtype=np.int64) * (rows * width * 4)
         p_off = np.arange(n + 1, dtype=np.int64) * (rows * rb)
         rgba = np.concatenate([[GUARD], px.view(np.uint8)]).astype(np.uint8)
         pix = torch.full((int(p_off[-1]) + 16,), GUARD, dtype=torch.uint8, device="cuda")
-        got_st = fd.png_pack_batch(_dev(rgba), _dev(s_off), pix, _dev(p_off), width, depth, colour,
-                                   pal=None if pal is None else _words([np.concatenate([pal, np.zeros(252, dtype=np.uint32)]).tolist()] * n),
-                                   colour=None if pal is None else _words([[4, 0, 0, 0]] * n))
+        got_st = fd.png_pack_batch(gh.dev(rgba), gh.dev(s_off), pix, gh.dev(p_off), width, depth, colour,
+                                   pal=None if pal is None else gh.words([np.concatenate([pal, np.zeros(252, dtype=np.uint32)]).tolist()] * n),
+                                   colour=None if pal is None else gh.words([[4, 0, 0, 0]] * n))
         torch.cuda.synchronize()
         got = pix.cpu().numpy()
         assert int(got_st.abs().sum()) == 0
@@ -334,11 +300,11 @@ def _analyse(fd, images, width, max_colours, with_pal=True, front=5):
         if isinstance(im, np.ndarray):
             rgba[off[k]:off[k + 1]] = im.view(np.uint8)
     n = len(images)
-    d_rgba = _dev(rgba)
+    d_rgba = gh.dev(rgba)
     pal = torch.full((n + 2, 256), GUARD_WORD, dtype=torch.int32, device="cuda")
     col = torch.full((n + 2, 4), GUARD_WORD, dtype=torch.int32, device="cuda")
     trns, summ, st = (torch.full((n + 2,), GUARD_WORD, dtype=torch.int32, device="cuda") for _ in range(3))
-    fd.png_analyse_batch(d_rgba, _dev(off), width, max_colours, with_pal=with_pal, pal=pal[1:n + 1] if with_pal else None,
+    fd.png_analyse_batch(d_rgba, gh.dev(off), width, max_colours, with_pal=with_pal, pal=pal[1:n + 1] if with_pal else None,
                          colour=col[1:n + 1], trns_len=trns[1:n + 1], summary=summ[1:n + 1], png_status=st[1:n + 1])
     torch.cuda.synchronize()
     assert np.array_equal(d_rgba.cpu().numpy(), rgba)
@@ -373,7 +339,7 @@ def _counted_images(r, width, height):
     npix = width * height
     images = []
     for c in COUNTS:
-        spread = tp.palette_image(r, width, height, c, c // 3).view(np.uint32)
+        spread = pc.palette_image(r, width, height, c, c // 3).view(np.uint32)
         assert len(set(spread.tolist())) == c
         images.append(spread)
         for at in (npix - 1, 0):
@@ -381,7 +347,7 @@ def _counted_images(r, width, height):
             if c == 1:
                 im = np.full(npix, extra, dtype=np.uint32)
             else:       # the other c - 1 colours on the other pixels
-                rest = tp.palette_image(r, npix - 1, 1, c - 1, c // 3).view(np.uint32)
+                rest = pc.palette_image(r, npix - 1, 1, c - 1, c // 3).view(np.uint32)
                 assert extra not in rest.tolist()
                 im = np.insert(rest, at, extra)
             assert len(set(im.tolist())) == c
@@ -402,7 +368,7 @@ def test_analyse_counts_against_every_threshold(monkeypatch):
     seen = set()
     for max_colours in limits:
         for waves in (1, 4, 16, None) if max_colours in (1, 16, 256) else (None,):
-            _waves(monkeypatch, "FDH_PNG_ANALYSE_WAVES", waves)
+            gh.set_env(monkeypatch, FDH_PNG_ANALYSE_WAVES=waves)
             got, rgba, off = _analyse(fd, images, width, max_colours)
             _check_analysis(got, rgba, off, width, max_colours, (max_colours, waves))
             seen |= {g[0] for g in got}
@@ -417,13 +383,13 @@ def test_analyse_large_images_at_every_launch_shape(monkeypatch):
     width, height = 301, 299
     images = []
     for colours in (200, 256, 300):
-        im = tp.palette_image(r, width, height, colours, 50).view(np.uint32)
+        im = pc.palette_image(r, width, height, colours, 50).view(np.uint32)
         runs = np.repeat(im[:width * height // 8 + 1], 8)[:width * height]          # runs of eight equal pixels
         runs[-colours:] = np.unique(im)[:colours]                                 # (and every colour at the end)
         images += [im, runs.copy()]
     answers = []
     for waves in (1, 2, 4, 7, 16, None):
-        _waves(monkeypatch, "FDH_PNG_ANALYSE_WAVES", waves)
+        gh.set_env(monkeypatch, FDH_PNG_ANALYSE_WAVES=waves)
         got, rgba, off = _analyse(fd, images, width, 256, front=1)
         _check_analysis(got, rgba, off, width, 256, waves)
         assert [g[0] for g in got] == [0, 0, 0, 0, 12, 12]
@@ -484,8 +450,8 @@ def test_analyse_without_palette_empty_images_and_bad_slots():
     import fdeflate_amd as fd
     r = np.random.default_rng(10400)
     width = 9
-    images = [tp.palette_image(r, width, 4, 20, 5).view(np.uint32), 0, tp.palette_image(r, width, 3, 7, 7).view(np.uint32), 4 * width + 4,
-              tp.palette_image(r, width, 1, 9, 0).view(np.uint32), 2, 0, tp.palette_image(r, width, 70, 256, 100).view(np.uint32)]
+    images = [pc.palette_image(r, width, 4, 20, 5).view(np.uint32), 0, pc.palette_image(r, width, 3, 7, 7).view(np.uint32), 4 * width + 4,
+              pc.palette_image(r, width, 1, 9, 0).view(np.uint32), 2, 0, pc.palette_image(r, width, 70, 256, 100).view(np.uint32)]
     for with_pal in (True, False):
         got, rgba, off = _analyse(fd, images, width, 256, with_pal=with_pal)
         _check_analysis(got, rgba, off, width, 256, with_pal, with_pal=with_pal)
@@ -520,11 +486,11 @@ def test_frame_palette_files(shape):
             (4, 1, 0, "trns_len above T"), (70, entries, alphas, None)]
     files, rows = [], []
     for height, colours, translucent, wrong in plan:
-        x = tp.palette_image(r, width, height, colours, translucent)
+        x = pc.palette_image(r, width, height, colours, translucent)
         st, pal, count, trns_len, _ = pm.analyse(x, width, 256)
         pix, pst = pm.pack(x, width, depth, 3, pal, count)
         assert st == 0 and pst == 0 and count <= entries and trns_len <= alphas
-        stream = xm.stream_of(pix, rb)
+        stream = pc.stream_of(pix, rb)
         idat_len, h, slot = len(stream), height, prefix + len(stream) + 16 + 3
         if wrong == "idat_len 0":
             idat_len = 0
@@ -556,13 +522,13 @@ def test_frame_palette_files(shape):
         if f:
             expect[f_off[k]:f_off[k] + len(f)] = np.frombuffer(f, dtype=np.uint8)
     assert sorted(set(want_st)) == [0, 2, 10, 11] and want_st.count(2) == 3 and want_st.count(10) == 2
-    d_file = _dev(host)
-    d_off = _dev(f_off)
-    pal_words = _words([row[2] for row in rows])
+    d_file = gh.dev(host)
+    d_off = gh.dev(f_off)
+    pal_words = gh.words([row[2] for row in rows])
     f_len = torch.full((n + 2,), GUARD_WORD, dtype=torch.int32, device="cuda")
     st = torch.full((n + 2,), GUARD_WORD, dtype=torch.int32, device="cuda")
-    fd.png_frame_palette_batch(d_file, d_off, _words([row[5] for row in rows]), _words([row[6] for row in rows]), pal_words,
-                               _words([[row[3], 0, 0, 0] for row in rows]), _words([row[4] for row in rows]), width, depth, entries,
+    fd.png_frame_palette_batch(d_file, d_off, gh.words([row[5] for row in rows]), gh.words([row[6] for row in rows]), pal_words,
+                               gh.words([[row[3], 0, 0, 0] for row in rows]), gh.words([row[4] for row in rows]), width, depth, entries,
                                alphas, file_len=f_len[1:n + 1], png_status=st[1:n + 1])
     torch.cuda.synchronize()
     got = d_file.cpu().numpy()
@@ -590,7 +556,7 @@ def test_frame_palette_files(shape):
         model_pal = em.read_colour(f, fm.scan(f, crc=zlib.crc32), width, depth, 3)[1]
         assert colour_back[k].tolist() == [entries, 0, 0, 0] and pal_back[k].tolist() == em.pal_words(model_pal)
         assert pal_back[k].tolist()[:row[3]] == row[2][:row[3]]
-        assert xm.pillow_rgba(got[f_off[k]:f_off[k] + want_len[k]].tobytes()) == row[0].tobytes(), k
+        assert pc.pillow_rgba(got[f_off[k]:f_off[k] + want_len[k]].tobytes()) == row[0].tobytes(), k
 
 
 def test_frame_palette_invalid_arguments():
@@ -600,7 +566,7 @@ def test_frame_palette_invalid_arguments():
     z = torch.zeros(64, dtype=torch.int32, device="cuda")
     pal = torch.zeros(256, dtype=torch.int32, device="cuda")
     f = torch.zeros(4096, dtype=torch.uint8, device="cuda")
-    off = _dev(np.array([0, 4096], dtype=np.int64))
+    off = gh.dev(np.array([0, 4096], dtype=np.int64))
     for width, depth, e, t in ((0, 8, 4, 0), (5, 16, 4, 0), (5, 8, 0, 0), (5, 8, 257, 0), (5, 2, 5, 0), (5, 4, 16, 17)):
         with pytest.raises(FdeflateHipError):
             fd.png_frame_palette_batch(f, off, z[:1], z[:1], pal, z[:4], z[:1], width, depth, e, t)
@@ -618,12 +584,6 @@ def test_frame_palette_invalid_arguments():
 
 # ---- RGBA -> files -> RGBA ----
 
-def _file_slots(fd, heights, width, depth, colour, extra=0):
-    rb = fm.geometry(width, depth, colour)[0]
-    sizes = [fd.png_file_bound(max(h, 1), rb) + extra + 5 for h in heights]
-    return np.concatenate([[3], 3 + np.cumsum(sizes)]).astype(np.int64)
-
-
 @pytest.mark.parametrize("pair", fm.PAIRS, ids=["depth%d-colour%d" % p for p in fm.PAIRS])
 def test_rgba_to_files_and_back(pair):
     """png_encode_rgba_files_batch, then png_decode_files_rgba_batch: the pictures come back byte for byte, for every
@@ -634,16 +594,16 @@ def test_rgba_to_files_and_back(pair):
     r = np.random.default_rng(10700 + 64 * colour + depth)
     width, heights = 37, (1, 5, 70)
     if colour == 3:
-        images = [tp.palette_image(r, width, h, 1 << depth, (1 << depth) // 2).view(np.uint32) for h in heights]
+        images = [pc.palette_image(r, width, h, 1 << depth, (1 << depth) // 2).view(np.uint32) for h in heights]
     else:
-        images = [random_rgba(r, width, h, depth, colour) for h in heights]
+        images = [gh.random_rgba(r, width, h, depth, colour) for h in heights]
     rgba = np.concatenate([[GUARD]] + [im.view(np.uint8) for im in images]).astype(np.uint8)
     r_off = np.concatenate([[1], 1 + np.cumsum([4 * im.size for im in images])]).astype(np.int64)
     extra = fd.png_palette_file_prefix(1 << depth, 1 << depth) - 41 if colour == 3 else 0
-    f_off = _file_slots(fd, heights, width, depth, colour, extra)
+    f_off = gh.file_slots(fd, heights, width, depth, colour, extra)
     file = torch.full((int(f_off[-1]) + 16,), GUARD, dtype=torch.uint8, device="cuda")
-    d_rgba = _dev(rgba)
-    file_len, st = fd.png_encode_rgba_files_batch(d_rgba, _dev(r_off), file, _dev(f_off), width, depth, colour)
+    d_rgba = gh.dev(rgba)
+    file_len, st = fd.png_encode_rgba_files_batch(d_rgba, gh.dev(r_off), file, gh.dev(f_off), width, depth, colour)
     torch.cuda.synchronize()
     assert st.cpu().tolist() == [0, 0, 0], pair
     assert np.array_equal(d_rgba.cpu().numpy(), rgba)
@@ -654,8 +614,8 @@ def test_rgba_to_files_and_back(pair):
         png = host[f_off[k]:f_off[k] + lens[k]].tobytes()
         info = fm.scan(png, crc=zlib.crc32)
         assert (info.status, info.width, info.height, info.bit_depth, info.colour_type) == (0, width, heights[k], depth, colour), (pair, k)
-        assert xm.pillow_rgba(png) == im.view(np.uint8).tobytes(), (pair, k)
-    back, back_off, info, status, png_status = fd.png_decode_files_rgba_batch(file, _dev(f_off), width, depth, colour, file_len=file_len)
+        assert pc.pillow_rgba(png) == im.view(np.uint8).tobytes(), (pair, k)
+    back, back_off, info, status, png_status = fd.png_decode_files_rgba_batch(file, gh.dev(f_off), width, depth, colour, file_len=file_len)
     torch.cuda.synchronize()
     assert status.cpu().tolist() == [0, 0, 0] and png_status.cpu().tolist() == [0, 0, 0]
     assert back_off.cpu().tolist() == (r_off - 1).tolist()
@@ -671,7 +631,7 @@ def test_one_batch_of_images_that_fit_and_images_that_do_not():
     import fdeflate_amd as fd
     r = np.random.default_rng(10800)
     width, height = 29, 6
-    good = lambda colours, clear: tp.palette_image(r, width, height, colours, clear).view(np.uint32)
+    good = lambda colours, clear: pc.palette_image(r, width, height, colours, clear).view(np.uint32)
     images = [good(16, 4), good(17, 0), good(3, 3), good(16, 4)[:width * height - width // 2], good(1, 0), good(9, 5), good(16, 0), good(2, 1)]
     want = [0, 12, 0, 2, 0, 11, None, 0]
     r_off = np.concatenate([[0], np.cumsum([4 * im.size for im in images])]).astype(np.int64)
@@ -681,28 +641,28 @@ def test_one_batch_of_images_that_fit_and_images_that_do_not():
     sizes[6] = prefix + 16 + 8                      # no stream fits
     f_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     file = torch.full((int(f_off[-1]),), GUARD, dtype=torch.uint8, device="cuda")
-    file_len, st = fd.png_encode_rgba_files_batch(_dev(rgba), _dev(r_off), file, _dev(f_off), width, 4, 3, plte_entries=16, trns_entries=4)
+    file_len, st = fd.png_encode_rgba_files_batch(gh.dev(rgba), gh.dev(r_off), file, gh.dev(f_off), width, 4, 3, plte_entries=16, trns_entries=4)
     torch.cuda.synchronize()
     st, lens, host = st.cpu().tolist(), file_len.cpu().tolist(), file.cpu().numpy()
     assert st[6] != 0 and [s for k, s in enumerate(st) if k != 6] == [w for w in want if w is not None], st
     for k, w in enumerate(want):
         if w == 0:
             png = host[f_off[k]:f_off[k] + lens[k]].tobytes()
-            assert fm.scan(png, crc=zlib.crc32).status == 0 and xm.pillow_rgba(png) == images[k].view(np.uint8).tobytes(), k
+            assert fm.scan(png, crc=zlib.crc32).status == 0 and pc.pillow_rgba(png) == images[k].view(np.uint8).tobytes(), k
         else:
             assert lens[k] == 0, k
     # grey
-    images = [random_rgba(r, width, height, 8, 0), _spoil(random_rgba(r, width, height, 8, 0), 77, 0xFF010000),
-              random_rgba(r, width, height, 8, 0), _spoil(random_rgba(r, width, height, 8, 0), width * height - 1, 0x80404040), random_rgba(r, width, height, 8, 0)]
+    images = [gh.random_rgba(r, width, height, 8, 0), _spoil(gh.random_rgba(r, width, height, 8, 0), 77, 0xFF010000),
+              gh.random_rgba(r, width, height, 8, 0), _spoil(gh.random_rgba(r, width, height, 8, 0), width * height - 1, 0x80404040), gh.random_rgba(r, width, height, 8, 0)]
     r_off = np.concatenate([[0], np.cumsum([4 * im.size for im in images])]).astype(np.int64)
-    f_off = _file_slots(fd, [height] * len(images), width, 8, 0)
+    f_off = gh.file_slots(fd, [height] * len(images), width, 8, 0)
     file = torch.full((int(f_off[-1]),), GUARD, dtype=torch.uint8, device="cuda")
-    file_len, st = fd.png_encode_rgba_files_batch(_dev(np.concatenate([im.view(np.uint8) for im in images])), _dev(r_off), file, _dev(f_off), width, 8, 0)
+    file_len, st = fd.png_encode_rgba_files_batch(gh.dev(np.concatenate([im.view(np.uint8) for im in images])), gh.dev(r_off), file, gh.dev(f_off), width, 8, 0)
     torch.cuda.synchronize()
     lens, host = file_len.cpu().tolist(), file.cpu().numpy()
     assert st.cpu().tolist() == [0, 13, 0, 13, 0] and lens[1] == 0 and lens[3] == 0
     for k in (0, 2, 4):
-        assert xm.pillow_rgba(host[f_off[k]:f_off[k] + lens[k]].tobytes()) == images[k].view(np.uint8).tobytes(), k
+        assert pc.pillow_rgba(host[f_off[k]:f_off[k] + lens[k]].tobytes()) == images[k].view(np.uint8).tobytes(), k
 
 
 def test_bench_shape_rgb8_and_palette8():

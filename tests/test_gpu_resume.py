@@ -7,6 +7,7 @@ import zlib
 import numpy as np
 import pytest
 
+import gpu_harness
 import oracle_binding as ob
 
 pytestmark = pytest.mark.gpu
@@ -46,88 +47,7 @@ def _streams():
     return out
 
 
-def _drive(fd, comps, in_cuts, out_cuts, per_call=False):
-    """All streams side by side in one batch; call k sees input up to in_cuts[i][k] and room up to out_cuts[i][k].
-    A slot is [out_off[j], out_off[j + 1]): the room a stream does not have yet is the slot of an empty stream
-    behind it (2n streams per call, every other one of length zero: InsufficientInput, nothing written).  The
-    input is packed anew for every call -- only the output has to stay where it is."""
-    import torch
-    n = len(comps)
-    cap = [oc[-1] for oc in out_cuts]
-    out_base = np.zeros(n + 1, dtype=np.int64)
-    out_base[1:] = np.cumsum([c + 16 for c in cap])
-    d_out = torch.full((int(out_base[-1]),), 0xA5, dtype=torch.uint8, device="cuda")
-    resume = torch.zeros((n, 4), dtype=torch.int32, device="cuda")
-    steps = max(max(len(x) for x in in_cuts), max(len(x) for x in out_cuts))
-    res = None
-    for k in range(steps):
-        io = np.zeros(2 * n + 1, dtype=np.int64)
-        oo = np.zeros(2 * n + 1, dtype=np.int64)
-        parts = []
-        pos = 0
-        for i in range(n):
-            cut = in_cuts[i][min(k, len(in_cuts[i]) - 1)]
-            parts.append(comps[i][:cut])
-            io[2 * i] = pos
-            pos += cut
-            io[2 * i + 1] = pos
-            oo[2 * i] = out_base[i]
-            oo[2 * i + 1] = out_base[i] + out_cuts[i][min(k, len(out_cuts[i]) - 1)]
-        io[2 * n] = pos
-        oo[2 * n] = out_base[n]
-        d_in = torch.from_numpy(np.frombuffer(b"".join(parts) + bytes(16), dtype=np.uint8).copy()).cuda()
-        r2 = torch.zeros((2 * n, 4), dtype=torch.int32, device="cuda")
-        r2[0::2] = resume
-        ln, st, ad = fd.inflate_batch_resumable(d_in, torch.from_numpy(io).cuda(), d_out, torch.from_numpy(oo).cuda(), r2,
-                                                resume_in=(k > 0))
-        torch.cuda.synchronize()
-        resume = r2[0::2].contiguous()
-        res = (ln.cpu().numpy().view(np.uint32)[0::2].copy(), st.cpu().numpy().view(np.uint32)[0::2].copy(),
-               ad.cpu().numpy().view(np.uint32)[0::2].copy())
-        if per_call:
-            # every call on its own: status, length and bytes so far are those of the reference's streaming `read`
-            # given the same input prefix and the same room in one go (src/decompress.rs:158-219 through the
-            # one-shot classification of :1111-1144), and a record is left exactly where the stream can go on
-            hk = d_out.cpu().numpy()
-            rk = resume.cpu().numpy()
-            for i in range(n):
-                cut = in_cuts[i][min(k, len(in_cuts[i]) - 1)]
-                room = out_cuts[i][min(k, len(out_cuts[i]) - 1)]
-                est, eout, _ = ob.decompress_bounded(comps[i][:cut], room)
-                assert int(res[1][i]) == est, (k, i, int(res[1][i]), est)
-                if est in (0, 17):
-                    assert int(res[0][i]) == len(eout) and hk[out_base[i]:out_base[i] + len(eout)].tobytes() == eout, (k, i)
-                if est == 2:
-                    d = ob.Decompressor()
-                    buf = np.zeros(max(room, 1), dtype=np.uint8)
-                    _, _, produced = d.read(comps[i][:cut], buf[:room], 0)
-                    assert int(res[0][i]) == produced, (k, i, int(res[0][i]), produced)
-                    assert hk[out_base[i]:out_base[i] + produced].tobytes() == buf[:produced].tobytes(), (k, i)
-                if est not in (2, 17):
-                    assert not rk[i].any(), (k, i, est, rk[i])  # "all zero for every other status"
-                else:
-                    # the record names a place inside what the call delivered, and its Adler word is the Adler-32 of
-                    # the bytes in front of that place (the call that goes on there starts its sums from it)
-                    rec = rk[i].view(np.uint32)
-                    opos = int(rec[2])
-                    if rec[0] == 0:
-                        # "no resume point" (include/fdeflate_hip.h: header_bit 0, the record all zero: go on from the
-                        # first byte).  Only for a call that delivered nothing: these streams lie far below the one gate
-                        # of the records (bit position < 2^30, DESIGN.md "Size gates"), so in front of any delivered
-                        # byte there is the start of a decoding step to name -- a record cleared by mistake would
-                        # otherwise cost only time and go unnoticed
-                        assert not rec.any() and int(res[0][i]) == 0, (k, i, est, rec.tolist(), int(res[0][i]))
-                    else:
-                        assert opos <= int(res[0][i]), (k, i, est, rec.tolist(), int(res[0][i]))
-                        assert int(rec[3]) == zlib.adler32(hk[out_base[i]:out_base[i] + opos].tobytes()), (k, i, est, rec.tolist())
-    h = d_out.cpu().numpy()
-    outs = [h[out_base[i]:out_base[i] + cap[i]] for i in range(n)]
-    guards = all((h[out_base[i] + cap[i]:out_base[i + 1]] == 0xA5).all() for i in range(n))
-    return res, outs, guards, resume.cpu().numpy()
-
-
 def _check_final(names, comps, caps, res, outs):
-    import gpu_harness
     ln, st, ad = res
     for i, name in enumerate(names):
         rs, rl, ra, ro = gpu_harness.oracle_inflate([comps[i]], [caps[i]])
@@ -157,7 +77,7 @@ def test_input_in_pieces(fd):
                 cuts = [len(c) - 9, len(c) - 5, len(c) - 4, len(c) - 1, len(c)]
             in_cuts.append(cuts)
         out_cuts = [[cap] for cap in caps]
-        res, outs, guards, _ = _drive(fd, comps, in_cuts, out_cuts, per_call=True)
+        res, outs, guards, _ = gpu_harness.drive_resumable(fd, comps, in_cuts, out_cuts, per_call=True)
         assert guards
         _check_final(names, comps, caps, res, outs)
 
@@ -172,7 +92,7 @@ def test_output_room_in_pieces(fd):
         caps = [len(x[2]) + final_slack for x in items]
         in_cuts = [[len(c)] for c in comps]
         out_cuts = [sorted(rnd.randrange(1, cap) for _ in range(5)) + [cap] for cap in caps]
-        res, outs, guards, _ = _drive(fd, comps, in_cuts, out_cuts, per_call=True)
+        res, outs, guards, _ = gpu_harness.drive_resumable(fd, comps, in_cuts, out_cuts, per_call=True)
         assert guards
         _check_final(names, comps, caps, res, outs)
 
@@ -187,11 +107,11 @@ def test_both_in_pieces_and_the_work_done(fd):
     steps = 8
     in_cuts = [[max(1, (len(c) * (k + 1)) // steps) for k in range(steps)] for c in comps]
     out_cuts = [[max(1, (cap * (k + 2)) // steps) if k + 2 < steps else cap for k in range(steps)] for cap in caps]
-    res, outs, guards, _ = _drive(fd, comps, in_cuts, out_cuts, per_call=True)
+    res, outs, guards, _ = gpu_harness.drive_resumable(fd, comps, in_cuts, out_cuts, per_call=True)
     assert guards
     _check_final(names, comps, caps, res, outs)
     # the resume points after half of the steps lie well inside the streams
-    res, outs, guards, rec = _drive(fd, comps, [x[:steps // 2] for x in in_cuts], [x[:steps // 2] for x in out_cuts])
+    res, outs, guards, rec = gpu_harness.drive_resumable(fd, comps, [x[:steps // 2] for x in in_cuts], [x[:steps // 2] for x in out_cuts])
     inside = [i for i in range(len(items)) if rec[i][0] != 0 and int(rec[i][1]) > 8 * len(comps[i]) // 4]
     assert len(inside) >= len(items) - 2, (len(inside), [(names[i], rec[i].tolist()) for i in range(len(items))])
 
@@ -206,7 +126,7 @@ def test_many_streams_taken_up_at_once(fd):
     comps = [ob.compress_ultra_fast(r) if i % 3 == 0 else zlib.compress(r, 1 + (i % 9)) for i, r in enumerate(raws)]
     in_cuts = [[len(c) // 3, (2 * len(c)) // 3, len(c)] for c in comps]
     out_cuts = [[len(r) // 2, len(r), len(r)] for r in raws]
-    (ln, st, ad), outs, guards, _ = _drive(fd, comps, in_cuts, out_cuts)
+    (ln, st, ad), outs, guards, _ = gpu_harness.drive_resumable(fd, comps, in_cuts, out_cuts)
     assert guards
     bad = [i for i in range(n) if int(st[i]) != 0 or int(ln[i]) != len(raws[i]) or outs[i].tobytes() != raws[i]
            or int(ad[i]) != zlib.adler32(raws[i])]

@@ -8,15 +8,13 @@ behaviour without a GPU.
 - the chain inputs reach every exit of the chain search at both levels (coverage is asserted, not hoped
   for).  What stays unpinned by a second implementation is the chain finder and match_length::<false>.
 """
-import functools
 import zlib
 
-import numpy as np
 import pytest
 
 import level_model as lm
 import oracle_binding as ob
-from test_oracle_golden import _encoder_inputs
+import streams
 
 
 def compress_bound(n):
@@ -24,47 +22,8 @@ def compress_bound(n):
     return n + n // 2 + 1024
 
 
-def chain_inputs():
-    """Inputs that drive the hash-chain search through all of its exits (seeds fixed): low-entropy noise
-    over 3 and 4 symbols (long chains, the depth exit, candidates at exactly ip - 32768; the 300 000-byte
-    ones also write more than 32 KiB in the first pass, so the second pass starts past 0), words with
-    short gaps (nice_length at level 3), the same cut short behind two words (end of data), and two
-    periodic streams (nice_length at level 2)."""
-    out = []
-    for seed in (5, 9):
-        r = np.random.default_rng(seed)
-        for a in (3, 4):
-            for n in (120000, 300000):
-                out.append(bytes(r.integers(0, a, n, dtype=np.uint8)))
-    r = np.random.default_rng(9)
-    w = [bytes(r.integers(0, 256, 12, dtype=np.uint8)) for _ in range(6)]
-    bb = bytearray()
-    for _ in range(9000):
-        bb += w[int(r.integers(0, 6))] + bytes(r.integers(0, 256, int(r.integers(0, 3)), dtype=np.uint8))
-    out.append(bytes(bb))
-    out.append(bytes(bb[:5000]) + w[0] + w[1])
-    out.append(b"abcdefgh" * 5000)
-    out.append(bytes(range(256)) * 300)
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def model_results():
-    """level -> (list of (input, stream, counters)) over the encoder inputs and the chain inputs; computed once
-    per process (the GPU tests use the same streams as expected bytes)."""
-    inputs = _encoder_inputs() + chain_inputs()
-    res = {}
-    for level in (2, 3):
-        rows = []
-        for x in inputs:
-            out = lm.compress(x, level)
-            rows.append((x, out, dict(lm.last_counters)))
-        res[level] = rows
-    return res
-
-
 def test_model_is_pinned_by_the_oracle_at_level1_and_rle():
-    for i, x in enumerate(_encoder_inputs()):
+    for i, x in enumerate(streams.encoder_inputs()):
         assert lm.compress(x, 1) == ob.compress_level1(x), ("level 1", i, len(x))
         assert lm.compress_rle(x) == ob.compress_rle(x), ("rle", i, len(x))
 
@@ -77,7 +36,7 @@ def test_model_empty_input_kat():
 
 @pytest.mark.parametrize("level", [2, 3])
 def test_levels_2_and_3_round_trip_and_fit_the_bound(level):
-    for i, (x, out, _) in enumerate(model_results()[level]):
+    for i, (x, out, _) in enumerate(lm.model_results()[level]):
         assert out[:2] == b"\x78\x01", (level, i)
         assert zlib.decompress(out) == x, (level, i, len(x))
         assert len(out) <= compress_bound(len(x)), (level, i, len(x), len(out))
@@ -86,7 +45,7 @@ def test_levels_2_and_3_round_trip_and_fit_the_bound(level):
 @pytest.mark.parametrize("level", [2, 3])
 def test_chain_inputs_reach_every_exit_of_the_search(level):
     tot = dict(steps2=0, nice=0, eod=0, depth=0, alias=0, unwritten=0, maxsteps=0)
-    for _, _, c in model_results()[level]:
+    for _, _, c in lm.model_results()[level]:
         for k, v in c.items():
             tot[k] = max(tot[k], v) if k == "maxsteps" else tot[k] + v
     print("level %d chain counters: %r" % (level, tot))

@@ -11,7 +11,7 @@ import png16_model as m16
 import png_adam7_model as am
 import png_expand_model as em
 import png_file_model as fm
-import test_png_expand_model as xm
+from png_corpus import random_case, stream_of
 
 Image = pytest.importorskip("PIL.Image")
 
@@ -83,8 +83,8 @@ def test_grey_16_against_pillow_both_ways():
     I;16 image, decoded by the models, are the source."""
     r = np.random.default_rng(16300)
     for width, height in ((1, 1), (7, 5), (33, 9), (100, 3)):
-        pix, _, _ = xm.random_case(r, width, height, 16, 0, False)
-        png = m16.write_file(xm.stream_of(pix, 2 * width), width, height, 16, 0, crc=zlib.crc32)
+        pix, _, _ = random_case(r, width, height, 16, 0, False)
+        png = m16.write_file(stream_of(pix, 2 * width), width, height, 16, 0, crc=zlib.crc32)
         im = Image.open(io.BytesIO(png))
         im.load()
         assert im.mode == "I;16"

@@ -15,7 +15,7 @@ import pytest
 import png_adam7_model as am
 import png_expand_model as em
 import png_file_model as fm
-import test_png_expand_model as xm
+from png_corpus import CLASSES, adam7_file, clear_padding, cycling_types, pillow_rgba, pre_chunks, random_case
 
 Image = pytest.importorskip("PIL.Image")
 
@@ -25,29 +25,7 @@ WIDTHS = tuple(range(1, 10)) + (17, 33)
 HEIGHTS = tuple(range(1, 10))
 
 
-def cycling_types(width, height, shift):
-    """All five filter types in turn from the first row of every pass on; `shift` moves the start, so that over five
-    files every pass has begun with every type."""
-    return [(r + p + shift) % 5 for p, (_, ph) in enumerate(am.passes(width, height)) for r in range(ph)]
-
-
-def adam7_file(pix, width, height, depth, colour, types, pre=(), idat_chunks=1, level=6):
-    return am.write_file(am.stream_of(pix, width, height, depth, colour, types, level), width, height, depth, colour, pre,
-                         idat_chunks, zlib.crc32)
-
-
-def clear_padding(pix, width, height, depth, colour):
-    """The picture with the padding bits of every row zero (what deinterlacing gives)."""
-    bits = fm.CHANNELS[colour] * depth
-    rb = fm.geometry(width, depth, colour)[0]
-    a = np.array(np.frombuffer(bytes(pix), dtype=np.uint8)).reshape(height, rb)
-    spare = rb * 8 - width * bits
-    if spare:
-        a[:, -1] &= (0xFF << spare) & 0xFF
-    return a.reshape(-1)
-
-
-@pytest.mark.parametrize("cls", xm.CLASSES, ids=["depth%d-colour%d%s" % (d, c, "-trns" if k else "") for d, c, k in xm.CLASSES])
+@pytest.mark.parametrize("cls", CLASSES, ids=["depth%d-colour%d%s" % (d, c, "-trns" if k else "") for d, c, k in CLASSES])
 def test_model_written_files_against_pillow(cls):
     """Model-written Adam7 files of the 22 classes on which Pillow follows the specification, every width of 1 .. 9, 17,
     33 at every height of 1 .. 9, the filter types cycling through all five from the first row of every pass on.
@@ -60,17 +38,17 @@ def test_model_written_files_against_pillow(cls):
     shift = 0
     for width in WIDTHS:
         for height in HEIGHTS:
-            pix, key, pal = xm.random_case(r, width, height, depth, colour, keyed)
+            pix, key, pal = random_case(r, width, height, depth, colour, keyed)
             pix = clear_padding(pix, width, height, depth, colour)
             shift += 1
-            png = adam7_file(pix, width, height, depth, colour, cycling_types(width, height, shift), xm.pre_chunks(colour, key, pal))
+            png = adam7_file(pix, width, height, depth, colour, cycling_types(width, height, shift), pre_chunks(colour, key, pal))
             im = Image.open(io.BytesIO(png))
             im.load()
             assert im.info.get("interlace") == 1 and im.size == (width, height), (cls, width, height)
             got = am.decode(png)
             assert got == (width, height, depth, colour, pix.tobytes()), (cls, width, height)
             rgba, st = em.expand(got[4], width, depth, colour, key, pal)
-            assert st == 0 and rgba == xm.pillow_rgba(png), (cls, width, height)
+            assert st == 0 and rgba == pillow_rgba(png), (cls, width, height)
             if depth == 8 or colour == 3 or (depth, colour) == (1, 0):
                 rb = fm.geometry(width, depth, colour)[0]
                 want = [s for y in range(height) for s in em.samples(got[4][y * rb:(y + 1) * rb], width, depth, ch)]

@@ -11,8 +11,7 @@ import pytest
 import png_encode_mixed_model as em
 import png_file_model as fm
 import png_mixed_model as mm
-import test_png_expand_model as xm
-import test_png_pack_model as tp
+from png_corpus import kinds, pillow_rgba
 
 BIT = {0: 1, 2: 4, 3: 8, 4: 16, 6: 64}
 
@@ -180,30 +179,6 @@ def test_records_of_neither_kind():
     assert em.dimension(mm.record(4, 4, 0, 0)) and not em.encodable(mm.record(4, 4, 0, 0)) and em.encodable(mm.record(4, 4, 1, 0))
 
 
-def kinds(r, width, height):
-    """RGBA8 pictures (uint8 [height * width * 4]) that are by construction grey-1 / 2 / 4 / 8, palette-1 / 2 / 4 / 8,
-    grey-alpha, RGB and RGBA when the plan chooses -> [(name, picture, depth, colour)].  The palette pictures are coloured
-    and large enough for the palette's chunks to pay."""
-    n = width * height
-    out = []
-    for d in (1, 2, 4, 8):
-        g = r.integers(0, 1 << d, n).astype(np.uint32)
-        g[:min(n, 1 << d)] = np.arange(min(n, 1 << d))                 # every level occurs where there is room
-        g = g * (255 // ((1 << d) - 1))
-        out.append(("grey%d" % d, (g * 0x010101 | 0xFF000000).astype(np.uint32).view(np.uint8), d, 0))
-    for d, colours, clear in ((1, 2, 0), (2, 4, 1), (4, 16, 16), (8, 200, 3)):
-        out.append(("palette%d" % d, tp.palette_image(r, width, height, colours, clear).reshape(-1), d, 3))
-    g = r.integers(0, 256, n).astype(np.uint32)
-    a = r.integers(0, 256, n).astype(np.uint32)
-    a[0] = 7
-    out.append(("grey-alpha", (g * 0x010101 | a << 24).astype(np.uint32).view(np.uint8), 8, 4))
-    rgb = r.integers(0, 1 << 24, n).astype(np.uint32)
-    rgb[0] = 0x010203
-    out.append(("rgb", (rgb | 0xFF000000).astype(np.uint32).view(np.uint8), 8, 2))
-    out.append(("rgba", (rgb | a << 24).astype(np.uint32).view(np.uint8), 8, 6))
-    return out
-
-
 def test_the_models_files_open_in_pillow():
     """Each of the five kinds the plan chooses, at every depth: the model's file has the planned pair in its IHDR, an
     exact PLTE / tRNS, and Pillow's convert("RGBA") gives the picture back."""
@@ -215,7 +190,7 @@ def test_the_models_files_open_in_pillow():
             assert (st, d, c) == (0, depth, colour), (name, st, d, c)
             info = fm.scan(f)
             assert (info.status, info.width, info.height, info.bit_depth, info.colour_type) == (0, width, height, depth, colour), name
-            assert xm.pillow_rgba(f) == px.tobytes(), name
+            assert pillow_rgba(f) == px.tobytes(), name
             im = Image.open(io.BytesIO(f))
             if colour == 3:
                 count = len(set(px.view(np.uint32).tolist()))
@@ -223,7 +198,7 @@ def test_the_models_files_open_in_pillow():
     # a forced pair, and a picture the forced pair cannot hold
     px = kinds(r, 9, 5)[0][1]
     st, f, d, c = em.encode(px.tobytes(), 9, 5, pair=(16, 6))
-    assert (st, d, c) == (0, 16, 6) and xm.pillow_rgba(f) == px.tobytes()
+    assert (st, d, c) == (0, 16, 6) and pillow_rgba(f) == px.tobytes()
     assert em.encode(kinds(r, 9, 5)[10][1].tobytes(), 9, 5, pair=(8, 0))[0] == em.NOT_REPRESENTABLE
     assert em.encode(kinds(r, 40, 40)[10][1].tobytes(), 40, 40, pair=(8, 3))[0] == em.TOO_MANY_COLOURS
     assert em.encode(px.tobytes(), 9, 4)[0] == em.BAD_SIZES

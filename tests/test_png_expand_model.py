@@ -1,7 +1,7 @@
 """tests/png_expand_model.py -- the referee of fdh_png_colour_batch and fdh_png_expand_batch -- against two references
 that share nothing with it: Pillow's reader (Image.open(..).convert("RGBA")) and expected bytes written out by hand.
-Also the cases the GPU tests share (random_case, status_files) and the CPU-side check that the library declares and
-exports the new entry points.
+Also the CPU-side check that the library declares and exports the new entry points.  The cases (random_case,
+status_files) come from tests/png_corpus.py, which the GPU tests share.
 
 Pillow is compared on 22 classes: all fifteen depth / colour pairs without tRNS, and with tRNS the palette at depths
 1, 2, 4 and 8, grey at depths 1 and 8 and RGB at depth 8.  Four classes are NOT compared with Pillow, because Pillow
@@ -11,7 +11,6 @@ key at all) and an RGB key at depth 16 (it compares the truncated high bytes, so
 their low byte only become transparent).  The specification (11.3.2.1) compares the raw samples: those four classes are
 checked against literal bytes below.
 """
-import io
 import os
 import re
 import zlib
@@ -21,71 +20,13 @@ import pytest
 
 import png_expand_model as em
 import png_file_model as fm
+from png_corpus import CLASSES, LEFT_OUT, pillow_rgba, pre_chunks, random_case, status_files, stream_of
 
 Image = pytest.importorskip("PIL.Image")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("fdh_png_colour_batch", "fdh_png_expand_batch")
 WIDTHS = (1, 3, 7, 8, 9, 33)
-KEYED = ((1, 3), (2, 3), (4, 3), (8, 3), (1, 0), (8, 0), (8, 2))      # (depth, colour) with tRNS that Pillow follows
-CLASSES = [(d, c, False) for d, c in fm.PAIRS] + [(d, c, True) for d, c in KEYED]
-LEFT_OUT = ((2, 0), (4, 0), (16, 0), (16, 2))
-
-
-def stream_of(pix, row_bytes):
-    """The zlib stream of packed rows, every row with filter type 0."""
-    pix = bytes(pix)
-    rows = len(pix) // row_bytes
-    return zlib.compress(b"".join(b"\0" + pix[r * row_bytes:(r + 1) * row_bytes] for r in range(rows)), 6)
-
-
-def random_case(r, width, height, depth, colour, keyed, entries=None):
-    """(pix uint8 [height * row_bytes], key or None, pal or None) of random rows.  A key is the first pixel's samples
-    (so it is hit at least once), and at depth 16 some pixels differ from it in their low bytes only.  A palette has
-    `entries` entries (2^depth by default) and with `keyed` a tRNS that is shorter than the PLTE when that has more than
-    two entries."""
-    rb = fm.geometry(width, depth, colour)[0]
-    ch = fm.CHANNELS[colour]
-    pix = r.integers(0, 256, (height, rb), dtype=np.uint8)
-    key = pal = None
-    if colour == 3:
-        n = entries if entries is not None else 1 << depth
-        alpha = r.integers(0, 256, n - 1 if n > 2 else n, dtype=np.uint8).tolist() if keyed else []
-        pal = em.palette(r.integers(0, 256, 3 * n, dtype=np.uint8).tobytes(), bytes(alpha))
-    elif keyed and colour in (0, 2):
-        key = tuple(em.samples(pix[0].tobytes(), 1, depth, ch))
-        if depth >= 8:       # more hits, and near misses in the low byte
-            bpp = ch * depth // 8
-            first = pix[0, :bpp].copy()
-            for x in range(2, width, 3):
-                pix[height // 2, x * bpp:(x + 1) * bpp] = first
-                if depth == 16 and x % 2:
-                    pix[height // 2, (x + 1) * bpp - 1] ^= 1
-    return pix.reshape(-1), key, pal
-
-
-def pre_chunks(colour, key, pal, text=False):
-    pre = [(b"tEXt", b"Comment\0in front")] if text else []
-    if pal is not None:
-        pre.append((b"PLTE", em.plte_body(pal)))
-        alpha = [e[3] for e in pal]
-        while alpha and alpha[-1] == 255:
-            alpha.pop()
-        if alpha:
-            pre.append((b"tRNS", bytes(alpha)))
-    if key is not None:
-        pre.append((b"tRNS", em.trns_body(key)))
-    return pre
-
-
-def pillow_rgba(png):
-    """Pillow's RGBA8 bytes of a file; 16-bit grey (mode I;16) is the array >> 8 with alpha 255."""
-    im = Image.open(io.BytesIO(png))
-    im.load()
-    if im.mode == "I;16":
-        g = (np.asarray(im).astype(np.uint16) >> 8).astype(np.uint8)
-        return np.stack([g, g, g, np.full_like(g, 255)], axis=-1).tobytes()
-    return im.convert("RGBA").tobytes()
 
 
 @pytest.mark.parametrize("cls", CLASSES, ids=["depth%d-colour%d%s" % (d, c, "-trns" if k else "") for d, c, k in CLASSES])
@@ -130,50 +71,6 @@ def test_left_out_classes_against_literal_bytes():
     assert st == 0 and rgba == bytes([1, 3, 5, 0, 1, 3, 5, 255, 1, 3, 5, 255, 1, 3, 5, 255])
     # padding bits behind the last pixel are ignored: width 3 at depth 2, the last two bits set
     assert em.expand(bytes([0b00011011]), 3, 2, 0)[0] == bytes([0, 0, 0, 255, 85, 85, 85, 255, 170, 170, 170, 255])
-
-
-def status_files(width=5, height=3, crc=zlib.crc32):
-    """[(what, file, (width, depth, colour) of the CALL, expected status)]: one file per way to get 10 and 11, the two
-    tolerated cases, a file the scan refuses (3), another geometry (7) and sound files in between."""
-    r = np.random.default_rng(7300)
-    out = []
-
-    def add(what, depth, colour, pre, want, call=None):
-        rb = fm.geometry(width, depth, colour)[0]
-        pix = r.integers(0, 256, height * rb, dtype=np.uint8)
-        if colour == 3:
-            pix &= 3                     # indices 0 .. 3
-        out.append((what, em.write_file(stream_of(pix, rb), width, height, depth, colour, pre, 2, crc), call or (width, depth, colour), want, pix))
-
-    plte4 = (b"PLTE", bytes(range(12)))
-    text = (b"tEXt", b"Title\0x")
-    add("sound palette", 8, 3, [text, plte4, (b"tRNS", bytes([9, 8, 7]))], 0)
-    add("no PLTE", 8, 3, [text], 10)
-    add("PLTE of no bytes", 8, 3, [(b"PLTE", b"")], 10)
-    add("PLTE of 13 bytes", 8, 3, [(b"PLTE", bytes(13))], 10)
-    add("PLTE of 771 bytes", 8, 3, [(b"PLTE", bytes(771))], 10)
-    add("two PLTE", 8, 3, [plte4, plte4], 10)
-    add("sound palette of 256", 8, 3, [(b"PLTE", bytes(768)), (b"tRNS", bytes(256))], 0)
-    add("grey tRNS of 1 byte", 8, 0, [(b"tRNS", b"\0")], 11)
-    add("grey tRNS of 4 bytes", 4, 0, [(b"tRNS", bytes(4))], 11)
-    add("RGB tRNS of 2 bytes", 8, 2, [(b"tRNS", bytes(2))], 11)
-    add("sound grey key", 8, 0, [(b"tRNS", b"\0\x07"), text], 0)
-    add("palette tRNS longer than PLTE", 8, 3, [plte4, (b"tRNS", bytes(5))], 11)
-    add("palette tRNS in front of PLTE", 8, 3, [(b"tRNS", bytes(2)), plte4], 11)
-    add("palette tRNS and no PLTE", 8, 3, [(b"tRNS", bytes(2))], 11)
-    add("two tRNS, grey", 8, 0, [(b"tRNS", bytes(2)), (b"tRNS", bytes(2))], 11)
-    add("two tRNS, RGB", 16, 2, [(b"tRNS", bytes(6)), text, (b"tRNS", bytes(6))], 11)
-    add("two tRNS, palette", 2, 3, [plte4, (b"tRNS", bytes(2)), (b"tRNS", bytes(2))], 11)
-    add("sound RGB key", 16, 2, [(b"tRNS", bytes([0x12, 0x34, 0, 5, 0xFF, 0xFE]))], 0)
-    add("tolerated: tRNS with grey + alpha", 8, 4, [(b"tRNS", bytes(2)), (b"tRNS", bytes(7))], 0)
-    add("tolerated: tRNS with RGBA", 8, 6, [(b"tRNS", bytes(1))], 0)
-    add("tolerated: PLTE with RGB", 8, 2, [(b"PLTE", bytes(5)), (b"PLTE", b"")], 0)
-    add("tolerated: PLTE with grey, behind its key", 8, 0, [(b"tRNS", b"\0\x21"), plte4], 0)
-    add("another geometry", 8, 0, [], 7, call=(width, 8, 3))
-    add("another width", 8, 3, [plte4], 7, call=(width + 1, 8, 3))
-    what, f, call, _, pix = out[0]
-    out.append(("refused by the scan", f[:40], call, 3, pix))
-    return out
 
 
 def test_reader_statuses():

@@ -1,8 +1,8 @@
 """tests/png_pack_model.py -- the referee of fdh_png_analyse_batch, fdh_png_pack_batch and fdh_png_frame_palette_batch --
 against references that share nothing with it: tests/png_expand_model.py (itself pinned to Pillow and to literal
-bytes), Pillow's reader on the model's files, Pillow's writer, and expected values written out by hand.  Also the cases
-the GPU tests share (representable, palette_image) and the CPU-side check that the library declares and exports the
-new entry points.
+bytes), Pillow's reader on the model's files, Pillow's writer, and expected values written out by hand.  Also the
+CPU-side check that the library declares and exports the new entry points.  The pictures (representable,
+palette_image) come from tests/png_corpus.py, which the GPU tests share.
 """
 import io
 import os
@@ -16,7 +16,7 @@ import oracle_binding as ob
 import png_expand_model as em
 import png_file_model as fm
 import png_pack_model as pm
-import test_png_expand_model as xm
+from png_corpus import palette_image, pillow_rgba, random_case, representable, stream_of
 
 Image = pytest.importorskip("PIL.Image")
 
@@ -26,29 +26,6 @@ WIDTHS = tuple(range(1, 10)) + (31, 32, 33)
 PALETTE_DEPTHS = (1, 2, 4, 8)
 CLASSES = [(d, c, False) for d, c in fm.PAIRS] + [(d, 3, True) for d in PALETTE_DEPTHS]
 IDS = ["depth%d-colour%d%s" % (d, c, "-trns" if k else "") for d, c, k in CLASSES]
-
-
-def representable(r, width, height, depth, colour):
-    """Random RGBA8 rows (uint8 [height * width * 4]) that the pair holds without loss: random packed rows, expanded."""
-    assert colour != 3
-    pix, _, _ = xm.random_case(r, width, height, depth, colour, False)
-    rgba, st = em.expand(pix, width, depth, colour)
-    assert st == 0
-    return np.frombuffer(rgba, dtype=np.uint8).copy()
-
-
-def palette_image(r, width, height, colours, translucent):
-    """Random RGBA8 rows of exactly min(colours, width * height) distinct pixels, `translucent` of them (at most) with
-    A < 255; every colour occurs."""
-    colours = min(colours, width * height)
-    words = set()
-    while len(words) < colours:
-        a = int(r.integers(0, 255)) if len(words) < translucent else 255
-        words.add(int(r.integers(0, 1 << 24)) | a << 24)
-    words = np.array(sorted(words), dtype=np.uint32)
-    idx = r.integers(0, colours, width * height)
-    idx[r.permutation(width * height)[:colours]] = np.arange(colours)
-    return words[idx].view(np.uint8).copy()
 
 
 @pytest.mark.parametrize("pair", fm.PAIRS, ids=["depth%d-colour%d" % p for p in fm.PAIRS])
@@ -67,7 +44,7 @@ def test_expand_of_pack_is_the_identity(pair):
             pix, st = pm.pack(x, width, depth, colour, pal, count)
             back = em.expand(pix, width, depth, colour, None, em.palette(*_plte_trns(pal, count)))
         else:
-            src, _, _ = xm.random_case(r, width, height, depth, colour, False)
+            src, _, _ = random_case(r, width, height, depth, colour, False)
             x = np.frombuffer(em.expand(src, width, depth, colour)[0], dtype=np.uint8)
             pix, st = pm.pack(x, width, depth, colour)
             back = em.expand(pix, width, depth, colour)
@@ -103,16 +80,16 @@ def test_pillow_reads_the_models_files(cls):
             st, pal, count, trns_len, _ = pm.analyse(x, width, entries)
             assert st == 0 and (trns_len > 0) == trns
             pix, st = pm.pack(x, width, depth, colour, pal, count)
-            png = pm.write_palette_file(xm.stream_of(pix, rb), width, height, depth, pal, count, entries, entries if trns else 0, zlib.crc32)
+            png = pm.write_palette_file(stream_of(pix, rb), width, height, depth, pal, count, entries, entries if trns else 0, zlib.crc32)
             info = fm.scan(png, crc=zlib.crc32)
             got = em.read_colour(png, info, width, depth, 3)
             assert info.status == 0 and got[0] == 0 and em.pal_words(got[1])[:count] == pal[:count]
         else:
             x = representable(r, width, height, depth, colour)
             pix, st = pm.pack(x, width, depth, colour)
-            png = em.write_file(xm.stream_of(pix, rb), width, height, depth, colour, crc=zlib.crc32)
+            png = em.write_file(stream_of(pix, rb), width, height, depth, colour, crc=zlib.crc32)
         assert st == 0
-        assert xm.pillow_rgba(png) == x.tobytes(), (cls, width)
+        assert pillow_rgba(png) == x.tobytes(), (cls, width)
 
 
 @pytest.mark.parametrize("mode", ("RGB", "L", "LA", "RGBA"))

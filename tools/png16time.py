@@ -11,7 +11,7 @@ reverse).  FDH_LIB=<another build of the library> measures that build: the two s
 (-DFDH_EXPAND16_GROUP=2 / 4) are compared by running this tool once with each.
 """
 import argparse
-import math
+import functools
 import os
 import sys
 
@@ -21,6 +21,8 @@ sys.path.insert(0, os.getcwd())
 import fdeflate_amd as fd  # noqa: E402
 import fdeflate_amd.png16 as p16  # noqa: E402
 from fdeflate_amd import synth  # noqa: E402
+import timing  # noqa: E402
+from timing import interleaved  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=65536)
@@ -29,41 +31,9 @@ ap.add_argument("--skip-files", action="store_true")
 ap.add_argument("--skip-torch", action="store_true")
 args = ap.parse_args()
 dev = "cuda"
-WINDOW_MS = 500.0
+show = functools.partial(timing.show, fmt="  %-58s median %9.3f ms, min %9.3f, max %9.3f over %d rounds of %d calls, %5.0f GB/s")
 WIDTH, ROWS = 341, 64
 CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
-
-
-def once(f, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        f()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def interleaved(variants, rounds):
-    calls = {}
-    for name, f in variants:
-        f()
-        f()
-        torch.cuda.synchronize()
-        calls[name] = max(1, int(math.ceil(WINDOW_MS / max(once(f, 1), 1e-3))))
-    ts = {name: [] for name, _ in variants}
-    for _ in range(rounds):
-        for name, f in variants:
-            ts[name].append(once(f, calls[name]))
-    return ts, calls
-
-
-def show(name, t, calls, nbytes):
-    t = sorted(t)
-    med = t[len(t) // 2]
-    print("  %-58s median %9.3f ms, min %9.3f, max %9.3f over %d rounds of %d calls, %5.0f GB/s"
-          % (name, med, t[0], t[-1], len(t), calls, nbytes / med / 1e6))
-    return med
 
 
 def swap16(pix):

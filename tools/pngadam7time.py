@@ -13,7 +13,7 @@ not depend on the values (every predictor is computed for every byte), and the f
 --profile runs every kernel three times and nothing else: for `rocprofv3 --kernel-trace --stats -- python ...`.
 """
 import argparse
-import math
+import functools
 import os
 import sys
 import zlib
@@ -23,6 +23,8 @@ import torch
 sys.path.insert(0, os.getcwd())
 import fdeflate_amd as fd  # noqa: E402
 from fdeflate_amd import synth  # noqa: E402
+import timing  # noqa: E402
+from timing import arange_off, interleaved  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=65536)
@@ -31,45 +33,9 @@ ap.add_argument("--profile", action="store_true")
 ap.add_argument("--skip-files", action="store_true")
 args = ap.parse_args()
 dev = "cuda"
-WINDOW_MS = 500.0
+show = functools.partial(timing.show, fmt="%-66s median %8.3f ms, min %8.3f, max %8.3f over %d rounds of %d calls, %.0f GB/s")
 X0, Y0 = (0, 4, 0, 2, 0, 1, 0), (0, 0, 4, 0, 2, 0, 1)
 DX, DY = (8, 8, 4, 4, 2, 2, 1), (8, 8, 8, 4, 4, 2, 2)
-
-
-def once(f, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        f()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def interleaved(variants, rounds):
-    calls = {}
-    for name, f in variants:
-        f()
-        f()
-        torch.cuda.synchronize()
-        calls[name] = max(1, int(math.ceil(WINDOW_MS / max(once(f, 1), 1e-3))))
-    ts = {name: [] for name, _ in variants}
-    for _ in range(rounds):
-        for name, f in variants:
-            ts[name].append(once(f, calls[name]))
-    return ts, calls
-
-
-def show(name, t, calls, nbytes):
-    t = sorted(t)
-    med = t[len(t) // 2]
-    print("%-66s median %8.3f ms, min %8.3f, max %8.3f over %d rounds of %d calls, %.0f GB/s"
-          % (name, med, t[0], t[-1], len(t), calls, nbytes / med / 1e6))
-    return med
-
-
-def arange_off(n, step, start=0):
-    return start + torch.arange(n + 1, dtype=torch.int64, device=dev) * step
 
 
 # ---- the pictures: the bench's synthetic PNG rows, reconstructed ----

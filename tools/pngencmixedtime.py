@@ -13,7 +13,6 @@ spread (max - min) of the per-geometry call's own rounds in this run.
       that geometry's pictures (what a caller had to do before, the grouping not counted)
 """
 import argparse
-import math
 import os
 import sys
 
@@ -22,6 +21,8 @@ import torch
 sys.path.insert(0, os.getcwd())
 import fdeflate_amd as fd  # noqa: E402
 from fdeflate_amd import synth  # noqa: E402
+import timing  # noqa: E402
+from timing import arange_off  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=65536)
@@ -29,46 +30,17 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--skip-files", action="store_true")
 args = ap.parse_args()
 dev = "cuda"
-WINDOW_MS = 500.0
 CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
-
-
-def once(f, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        f()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / calls
 
 
 def compare(title, variants):
     """Prints every variant; the first is the mixed call, the second what it is held against."""
-    calls = {}
-    for name, f in variants:
-        f()
-        f()
-        torch.cuda.synchronize()
-        calls[name] = max(1, int(math.ceil(WINDOW_MS / max(once(f, 1), 1e-3))))
-    ts = {name: [] for name, _ in variants}
-    for _ in range(args.rounds):
-        for name, f in variants:
-            ts[name].append(once(f, calls[name]))
-    stats = []
-    for name, _ in variants:
-        t = sorted(ts[name])
-        stats.append((t[len(t) // 2], t[0], t[-1]))
-        print("  %-64s median %9.3f ms [%9.3f .. %9.3f] over %d rounds of %d calls" % (name, t[len(t) // 2], t[0], t[-1], len(t), calls[name]))
+    stats = timing.measure(variants, args.rounds, width=64)
     (m, _, _), (p, plo, phi) = stats[0], stats[1]
     print("  %s: mixed / per-geometry = %.3f (%+.3f ms); margin (the per-geometry call's spread) %.3f ms: %s" %
           (title, m / p, m - p, phi - plo, "inside" if m - p <= phi - plo else "OUTSIDE"))
     sys.stdout.flush()
     return stats
-
-
-def arange_off(n, step, start=0):
-    return start + torch.arange(n + 1, dtype=torch.int64, device=dev) * step
 
 
 def records(n, width, height, depth, colour):

@@ -15,7 +15,7 @@ exceed.
       per distinct geometry over the whole batch (what a caller had to do before)
 """
 import argparse
-import math
+import functools
 import os
 import sys
 import zlib
@@ -25,6 +25,8 @@ import torch
 sys.path.insert(0, os.getcwd())
 import fdeflate_amd as fd  # noqa: E402
 from fdeflate_amd import synth  # noqa: E402
+import timing  # noqa: E402
+from timing import arange_off  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=65536)
@@ -32,54 +34,10 @@ ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--skip-files", action="store_true")
 args = ap.parse_args()
 dev = "cuda"
-WINDOW_MS = 500.0
+compare = functools.partial(timing.compare, rounds=args.rounds)
 X0, Y0 = (0, 4, 0, 2, 0, 1, 0), (0, 0, 4, 0, 2, 0, 1)
 DX, DY = (8, 8, 4, 4, 2, 2, 1), (8, 8, 8, 4, 4, 2, 2)
 CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}
-
-
-def once(f, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        f()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def interleaved(variants, rounds):
-    calls = {}
-    for name, f in variants:
-        f()
-        f()
-        torch.cuda.synchronize()
-        calls[name] = max(1, int(math.ceil(WINDOW_MS / max(once(f, 1), 1e-3))))
-    ts = {name: [] for name, _ in variants}
-    for _ in range(rounds):
-        for name, f in variants:
-            ts[name].append(once(f, calls[name]))
-    return ts, calls
-
-
-def compare(title, variants):
-    """Prints every variant; the first is the mixed call, the second what it is held against."""
-    ts, calls = interleaved(variants, args.rounds)
-    stats = []
-    for name, _ in variants:
-        t = sorted(ts[name])
-        stats.append((t[len(t) // 2], t[0], t[-1]))
-        print("  %-62s median %9.3f ms [%9.3f .. %9.3f] over %d rounds of %d calls" % (name, t[len(t) // 2], t[0], t[-1], len(t), calls[name]))
-    (m, mlo, mhi), (p, plo, phi) = stats[0], stats[1]
-    allowed = p + (phi - plo) + (mhi - mlo) + 0.05 * p
-    print("  %s: mixed / per-geometry = %.3f; allowance (spreads + 5 %%) %.3f ms: %s by %.3f ms" %
-          (title, m / p, allowed, "inside" if m <= allowed else "MISSED", abs(allowed - m)))
-    sys.stdout.flush()
-    return stats
-
-
-def arange_off(n, step, start=0):
-    return start + torch.arange(n + 1, dtype=torch.int64, device=dev) * step
 
 
 def records(n, width, height, depth, colour, interlace, idat_bytes=0):

@@ -2,6 +2,7 @@ import os, sys, torch
 sys.path.insert(0, os.getcwd())
 import fdeflate_amd as fd
 from fdeflate_amd import synth
+import timing
 n, L = 65536, 65536
 dev = "cuda"
 raw = synth.gen_batch_torch(0, n, L, model="D", device=dev)
@@ -82,22 +83,9 @@ def choose_and_encode():
     return fd.png_encode_ultrafast_batch(pixels, p_off, enc, o_off, rb, bpp, types=chosen, types_off=t_off)
 
 
-def once(f, calls=5):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls): f()
-    e1.record(); torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
 assert int(choose().abs().sum()) == 0
 variants = (("choose", choose), ("encode", encode_chosen), ("choose + encode", choose_and_encode))
-for _, f in variants:
-    f(); f(); torch.cuda.synchronize()
-times = {name: [] for name, _ in variants}
-for _ in range(9):
-    for name, f in variants:
-        times[name].append(once(f))
+times, _ = timing.interleaved(variants, 9, calls=5)
 med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
 for name, _ in variants:
     print("%-16s median %.3f ms, min %.3f ms over %d rounds of 5 calls" % (name, med[name], min(times[name]), len(times[name])))
@@ -129,16 +117,6 @@ assert int(st.abs().sum()) == 0
 stream_bytes = int(ol.to(torch.int64).sum())
 
 
-def interleaved(variants, rounds=9, calls=5):
-    for _, f in variants:
-        f(); f(); torch.cuda.synchronize()
-    ts = {name: [] for name, _ in variants}
-    for _ in range(rounds):
-        for name, f in variants:
-            ts[name].append(once(f, calls))
-    return ts
-
-
 def show(name, t, nbytes=None):
     t = sorted(t)
     rate = "" if nbytes is None else ", %.0f GB/s" % (nbytes / t[len(t) // 2] / 1e6)
@@ -149,12 +127,12 @@ big_n = 256 << 20
 big = torch.randint(0, 256, (big_n + 16,), dtype=torch.uint8, device=dev)
 big_off = torch.tensor([0, big_n], dtype=torch.int64, device=dev)
 enc_copy = torch.empty_like(enc)
-ts = interleaved((("device copy of the encoder's buffer", lambda: enc_copy.copy_(enc)),), rounds=5, calls=3)
+ts, _ = timing.interleaved((("device copy of the encoder's buffer", lambda: enc_copy.copy_(enc)),), 5, calls=3)
 show("device copy, %.2f GB read + as much written" % (enc.numel() / 1e9), ts["device copy of the encoder's buffer"], 2 * enc.numel())
 del enc_copy
 for copies in ("1", "8", "32"):
     os.environ["FDH_CRC_COPIES"] = copies
-    ts = interleaved((("streams", lambda: fd.crc32_batch(enc, o_off, ol)), ("big", lambda: fd.crc32_batch(big, big_off))))
+    ts, _ = timing.interleaved((("streams", lambda: fd.crc32_batch(enc, o_off, ol)), ("big", lambda: fd.crc32_batch(big, big_off))), 9, calls=5)
     show("crc32 of %d streams (%.2f GB), %s table copies" % (n, stream_bytes / 1e9, copies), ts["streams"], stream_bytes)
     show("crc32 of one 256 MiB range, %s table copies" % copies, ts["big"], big_n)
 os.environ.pop("FDH_CRC_COPIES")
@@ -176,7 +154,7 @@ variants = (
     ("encoder, streams at aligned addresses", lambda: fd.png_filter_deflate_ultrafast_batch(pixels, p_off, chosen, t_off, enc2, o_off, rb, bpp)),
     ("encoder, streams at aligned + 41", lambda: fd.png_filter_deflate_ultrafast_batch(pixels, p_off, chosen, t_off, enc2, o_off41, rb, bpp)),
 )
-ts = interleaved(variants)
+ts, _ = timing.interleaved(variants, 9, calls=5)
 for name, _ in variants:
     show(name, ts[name])
 
@@ -193,7 +171,7 @@ variants = (
     ("gather of the IDAT bodies", lambda: fd.png_gather_idat_batch(files, f_off0, info, comp, comp_off, width, depth, colour)),
     ("inflate_png_batch of the gathered streams", lambda: fd.inflate_png_batch(comp, comp_off, filt, r_off, pix2, p_off, rb, bpp)),
 )
-ts = interleaved(variants)
+ts, _ = timing.interleaved(variants, 9, calls=5)
 for name, _ in variants:
     show(name, ts[name], stream_bytes if "scan of" in name or "gather" in name else None)
 print("files -> pixels give the source back: %s" % bool(torch.equal(pix2, pixels)))
