@@ -28,6 +28,9 @@
 // oracle's section header for what is pinned and what is not); the order-dependent part (heap
 // merges) runs on one lane per tree -- the literal/length and the distance tree side by side on
 // lanes 0 and 1 -- the rest (compaction, code assignment, header) on the whole wavefront.
+#include <mutex>
+#include <string>
+
 #include "device_common.h"
 #include "bit_ring.h"
 #include "launch.h"
@@ -134,62 +137,37 @@ struct GParserT {
         return 2 * l + ((d1 >> (l - 1)) & 1);
     }
 
-    // Equal bytes walking backwards, data[a_end - 1 - i] == data[b_end - 1 - i] for i < limit
-    // (limit <= min(a_end, b_end)), eight at a time: the reference's byte loops (matchfinder/mod.rs
-    // :66-72, parse/mod.rs:72-81) give the same count, a dependent byte load per step is what they
-    // would cost here.
-    __device__ static uint32_t back_equal(const uint8_t* data, uint64_t a_end, uint64_t b_end, uint32_t limit) {
+    // Equal bytes from a point, eight at a time: the reference's byte loops (matchfinder/mod.rs:66-72, :113-145,
+    // parse/mod.rs:72-81) give the same count, a dependent byte load per step is what they would cost here.
+    // FWD: the bytes tested are a[0], a[1], ..; else a[-1], a[-2], ...  RUN: each is compared with `value`; else with
+    // the byte at the same offset from `b`.  At most `limit` bytes are tested; `room` (>= limit) is how many bytes are
+    // readable in the walking direction from `a` (and from `b`): a tail shorter than 8 bytes is taken with one wide
+    // load where room allows it, byte by byte where it does not -- the count is the same.
+    template <bool FWD, bool RUN>
+    __device__ static uint32_t equal_bytes(const uint8_t* a, const uint8_t* b, uint8_t value, uint32_t limit, uint64_t room) {
+        const uint64_t v8 = 0x0101010101010101ull * value;
+        const auto diff = [&](uint32_t n) {  // the 8 bytes behind the n already counted, against what they should be
+            const int64_t o = FWD ? (int64_t)n : -(int64_t)n - 8;
+            return g_load64(a + o) ^ (RUN ? v8 : g_load64(b + o));
+        };
+        const auto equal = [](uint64_t x) { return (uint32_t)(FWD ? __builtin_ctzll(x) : __builtin_clzll(x)) >> 3; };
         uint32_t n = 0;
-        while (n + 32 <= limit) {  // four pairs of loads in flight
-            const uint8_t *pa = data + a_end - n, *pb = data + b_end - n;
-            const uint64_t x0 = g_load64(pa - 8) ^ g_load64(pb - 8), x1 = g_load64(pa - 16) ^ g_load64(pb - 16);
-            const uint64_t x2 = g_load64(pa - 24) ^ g_load64(pb - 24), x3 = g_load64(pa - 32) ^ g_load64(pb - 32);
-            if (x0 | x1 | x2 | x3) {
-                return n + (x0 ? (uint32_t)__builtin_clzll(x0) >> 3
-                            : x1 ? 8 + ((uint32_t)__builtin_clzll(x1) >> 3)
-                            : x2 ? 16 + ((uint32_t)__builtin_clzll(x2) >> 3) : 24 + ((uint32_t)__builtin_clzll(x3) >> 3));
-            }
-            n += 32;
+        for (; n + 32 <= limit; n += 32) {  // four (pairs of) loads in flight
+            const uint64_t x0 = diff(n), x1 = diff(n + 8), x2 = diff(n + 16), x3 = diff(n + 24);
+            if (x0 | x1 | x2 | x3) return n + (x0 ? equal(x0) : x1 ? 8 + equal(x1) : x2 ? 16 + equal(x2) : 24 + equal(x3));
         }
-        while (n + 8 <= limit) {
-            const uint64_t x = g_load64(data + a_end - n - 8) ^ g_load64(data + b_end - n - 8);
-            if (x) return n + ((uint32_t)__builtin_clzll(x) >> 3);
-            n += 8;
+        for (; n + 8 <= limit; n += 8) {
+            const uint64_t x = diff(n);
+            if (x) return n + equal(x);
         }
         if (n < limit) {
-            if (a_end - n >= 8 && b_end - n >= 8) {
-                const uint64_t x = g_load64(data + a_end - n - 8) ^ g_load64(data + b_end - n - 8);
-                return n + min(x ? (uint32_t)__builtin_clzll(x) >> 3 : 8u, limit - n);
+            if (n + 8 <= room) {
+                const uint64_t x = diff(n);
+                return n + min(x ? equal(x) : 8u, limit - n);
             }
-            while (n < limit && data[a_end - n - 1] == data[b_end - n - 1]) n++;
+            while (n < limit && (FWD ? a[n] : a[-1 - (int64_t)n]) == (RUN ? value : FWD ? b[n] : b[-1 - (int64_t)n])) n++;
         }
         return n;
-    }
-    // Equal bytes walking forwards, a[i] == b[i] for i < limit; `wide_tail`: 8 bytes may be read at
-    // any offset below limit.
-    __device__ static uint32_t fwd_equal(const uint8_t* a, const uint8_t* b, uint32_t limit, bool wide_tail) {
-        uint32_t k = 0;
-        for (; k + 32 <= limit; k += 32) {  // four pairs of loads in flight
-            const uint64_t x0 = g_load64(a + k) ^ g_load64(b + k), x1 = g_load64(a + k + 8) ^ g_load64(b + k + 8);
-            const uint64_t x2 = g_load64(a + k + 16) ^ g_load64(b + k + 16), x3 = g_load64(a + k + 24) ^ g_load64(b + k + 24);
-            if (x0 | x1 | x2 | x3) {
-                return k + (x0 ? (uint32_t)__builtin_ctzll(x0) >> 3
-                            : x1 ? 8 + ((uint32_t)__builtin_ctzll(x1) >> 3)
-                            : x2 ? 16 + ((uint32_t)__builtin_ctzll(x2) >> 3) : 24 + ((uint32_t)__builtin_ctzll(x3) >> 3));
-            }
-        }
-        for (; k + 8 <= limit; k += 8) {
-            const uint64_t x = g_load64(a + k) ^ g_load64(b + k);
-            if (x) return k + ((uint32_t)__builtin_ctzll(x) >> 3);
-        }
-        if (k < limit) {
-            if (wide_tail) {
-                const uint64_t x = g_load64(a + k) ^ g_load64(b + k);
-                return k + min(x ? (uint32_t)__builtin_ctzll(x) >> 3 : 8u, limit - k);
-            }
-            while (k < limit && a[k] == b[k]) k++;
-        }
-        return k;
     }
 
     // match_length::<MIN8> (matchfinder/mod.rs:51-111): 8 equal bytes admit a candidate, or 4 with
@@ -205,7 +183,8 @@ struct GParserT {
         }
         uint64_t length = MIN8 || x == 0 ? 8 : (uint64_t)__builtin_ctzll(x) >> 3;
         {   // backwards while length < 258 && ip > anchor && prev_index > 0 && the bytes in front agree
-            const uint32_t n = back_equal(data, ip, prev_index, (uint32_t)min(min((uint64_t)258 - length, ip - anchor), prev_index));
+            const uint32_t limit = (uint32_t)min(min((uint64_t)258 - length, ip - anchor), prev_index);
+            const uint32_t n = equal_bytes<false, false>(data + ip, data + prev_index, 0, limit, prev_index);
             length += n;
             ip -= n;
             prev_index -= n;
@@ -214,7 +193,7 @@ struct GParserT {
         if (slice > 258 - length) slice = 258 - length;
         // (x != 0: the byte at ip + length is the one that differed, wherever the walk backwards put ip)
         if (MIN8 || x == 0)
-            length += fwd_equal(data + ip + length, data + prev_index + length, (uint32_t)slice, ip + length + slice + 8 <= len);
+            length += equal_bytes<true, false>(data + ip + length, data + prev_index + length, 0, (uint32_t)slice, len - ip - length);
         out_len = (uint32_t)length;
         out_start = ip;
     }
@@ -226,79 +205,33 @@ struct GParserT {
         uint64_t min_start = max((uint64_t)1, last_match);
         const uint64_t e = r.end();
         if (e > 258) min_start = max(min_start, e - 258);
-        const uint64_t v8 = 0x0101010101010101ull * value;
-        {   // while r.start > min_start && data[r.start - 2] == value: one byte further back
+        {   // while r.start > min_start && data[r.start - 2] == value: one byte further back (from data[ip - 1] on)
             const uint32_t limit = r.start > min_start ? (uint32_t)(r.start - min_start) : 0u;
-            const uint64_t end = r.start - 1;  // the bytes tested are data[end - 1], data[end - 2], ...
-            uint32_t n = 0;
-            bool stop = false;
-            while (!stop && n + 32 <= limit) {  // four loads in flight
-                const uint8_t* pe = data + end - n;
-                const uint64_t x0 = g_load64(pe - 8) ^ v8, x1 = g_load64(pe - 16) ^ v8, x2 = g_load64(pe - 24) ^ v8, x3 = g_load64(pe - 32) ^ v8;
-                if (x0 | x1 | x2 | x3) {
-                    n += x0 ? (uint32_t)__builtin_clzll(x0) >> 3
-                         : x1 ? 8 + ((uint32_t)__builtin_clzll(x1) >> 3)
-                         : x2 ? 16 + ((uint32_t)__builtin_clzll(x2) >> 3) : 24 + ((uint32_t)__builtin_clzll(x3) >> 3);
-                    stop = true;
-                } else {
-                    n += 32;
-                }
-            }
-            while (!stop && n + 8 <= limit) {
-                const uint64_t x = g_load64(data + end - n - 8) ^ v8;
-                if (x) {
-                    n += (uint32_t)__builtin_clzll(x) >> 3;
-                    stop = true;
-                } else {
-                    n += 8;
-                }
-            }
-            if (!stop && n < limit) {
-                if (end - n >= 8) {
-                    const uint64_t x = g_load64(data + end - n - 8) ^ v8;
-                    n += min(x ? (uint32_t)__builtin_clzll(x) >> 3 : 8u, limit - n);
-                } else {
-                    while (n < limit && data[end - n - 1] == value) n++;
-                }
-            }
+            const uint32_t n = equal_bytes<false, true>(data + ip, nullptr, value, limit, ip);
             r.start -= n;
             r.length += n;
         }
         uint64_t n = len - r.end();
         if (n > 258 - r.length) n = 258 - r.length;
-        const uint8_t* p = data + r.end();
-        uint64_t k = 0;
-        for (; k + 32 <= n; k += 32) {  // four loads in flight
-            const uint64_t c0 = g_load64(p + k) ^ v8, c1 = g_load64(p + k + 8) ^ v8, c2 = g_load64(p + k + 16) ^ v8, c3 = g_load64(p + k + 24) ^ v8;
-            if (c0 | c1 | c2 | c3) {
-                const uint32_t m = c0 ? (uint32_t)__builtin_ctzll(c0) >> 3
-                                   : c1 ? 8 + ((uint32_t)__builtin_ctzll(c1) >> 3)
-                                   : c2 ? 16 + ((uint32_t)__builtin_ctzll(c2) >> 3) : 24 + ((uint32_t)__builtin_ctzll(c3) >> 3);
-                r.length += m;
-                return r;
-            }
-            r.length += 32;
-        }
-        for (; k + 8 <= n; k += 8) {
-            const uint64_t c = g_load64(p + k);
-            if (c != v8) {
-                r.length += (uint32_t)(__builtin_ctzll(c ^ v8) / 8);
-                return r;
-            }
-            r.length += 8;
-        }
-        if (k < n) {
-            if (r.end() + 8 <= len) {  // (r.end() has moved with r.length: the next 8 bytes are inside the buffer)
-                const uint64_t x = g_load64(data + r.end()) ^ v8;
-                r.length += min(x ? (uint32_t)__builtin_ctzll(x) >> 3 : 8u, (uint32_t)(n - k));
-            } else {
-                for (; k < n; k++) {
-                    if (p[k] != value) break;
-                    r.length++;
-                }
-            }
-        }
+        r.length += equal_bytes<true, true>(data + r.end(), nullptr, value, (uint32_t)n, len - r.end());
         return r;
+    }
+
+    // the oldest table entry a match at `pos` may use (hashtable.rs:24-27, hashchain.rs:48-51): inside the window, and
+    // never 0, which is the empty entry
+    __device__ static uint32_t min_offset(uint32_t base_index, uint64_t pos) {
+        const uint32_t sub = (uint32_t)pos > 32768 ? (uint32_t)pos - 32768 : 0;
+        return max(base_index + sub, 1u);
+    }
+
+    // HashTableMatchFinder::get_and_insert (hashtable.rs:16-50) behind its table access: `offset` (>= min_offset) is
+    // what the table held for the 8 bytes `value` at ip
+    __device__ GMatch table_match(const uint8_t* data, uint64_t len, uint32_t base_index, uint64_t anchor, uint64_t value, uint32_t offset) {
+        uint32_t l;
+        uint64_t st;
+        match_length<true>(value, data, len, anchor, ip, (uint64_t)(offset - base_index), l, st);
+        if (l >= 8) return GMatch{l, (uint32_t)(ip - (uint64_t)(offset - base_index)), st};
+        return GMatch{0, 0, 0};
     }
 
     // HashChainMatchFinder::get_and_insert (hashchain.rs:40-107), as written there:
@@ -326,12 +259,11 @@ struct GParserT {
     // the candidate's bytes, not after they have been compared (the walk stores nothing, so the value is
     // the same; it is not used when the walk ends at this candidate).
     __device__ GMatch chain_walk(const uint8_t* data, uint64_t len, uint32_t base_index, uint64_t anchor, uint64_t value, uint32_t offset) {
-        const uint32_t sub = (uint32_t)ip > 32768 ? (uint32_t)ip - 32768 : 0;
-        const uint32_t min_offset = max(base_index + sub, 1u);
+        const uint32_t oldest = min_offset(base_index, ip);
         uint32_t best_offset = 0, best_length = kMinMatch - 1;
         uint64_t best_start = 0;
 #pragma nounroll
-        for (uint32_t n = kDepth; offset >= min_offset;) {
+        for (uint32_t n = kDepth; offset >= oldest;) {
             const uint32_t next = links[offset % kGWindow];
             uint32_t l;
             uint64_t st;
@@ -350,8 +282,7 @@ struct GParserT {
     }
 
     // ParserInner::get_match (parse/mod.rs:58-85) with HashTableMatchFinder::get_and_insert
-    // (hashtable.rs:16-50) / HashChainMatchFinder::get_and_insert / NullMatchFinder
-    template <bool RLE>
+    // (hashtable.rs:16-50) / HashChainMatchFinder::get_and_insert (the RLE parser's scan never comes here)
     __device__ GMatch get_match(const uint8_t* data, uint64_t len, uint32_t base_index, bool fizzle) {
         const uint64_t current = g_load64(data + ip);
         if ((uint32_t)current == (uint32_t)(current >> 8)) {
@@ -360,30 +291,21 @@ struct GParserT {
             return r;
         }
         GMatch r{0, 0, 0};
-        if (!RLE) {
-            const uint64_t anchor = fizzle ? ip : last_match;
-            if constexpr (kChain) {
-                r = chain_get_and_insert(data, len, base_index, anchor, current);
-            } else {
-                const uint32_t sub = (uint32_t)ip > 32768 ? (uint32_t)ip - 32768 : 0;
-                const uint32_t min_offset = max(base_index + sub, 1u);
-                const uint32_t h = g_hash(current);
-                const uint32_t offset = hash[h];
-                hash[h] = (uint32_t)ip + base_index;
-                if (offset >= min_offset) {
-                    uint32_t l;
-                    uint64_t st;
-                    match_length<true>(current, data, len, anchor, ip, (uint64_t)(offset - base_index), l, st);
-                    if (l >= 8) r = GMatch{l, (uint32_t)(ip - (uint64_t)(offset - base_index)), st};
-                }
-            }
-            if (fizzle && r.length != 0) {  // parse/mod.rs:72-81: take bytes in front of the match while they agree
-                const uint64_t room = r.start > (uint64_t)r.distance + 1 ? r.start - r.distance - 1 : 0;  // (never down to byte 0)
-                const uint64_t lim = min(min((uint64_t)(258 - r.length), r.start - last_match), room);
-                const uint32_t n = back_equal(data, r.start, r.start - r.distance, (uint32_t)lim);
-                r.length += n;
-                r.start -= n;
-            }
+        const uint64_t anchor = fizzle ? ip : last_match;
+        if constexpr (kChain) {
+            r = chain_get_and_insert(data, len, base_index, anchor, current);
+        } else {
+            const uint32_t h = g_hash(current);
+            const uint32_t offset = hash[h];
+            hash[h] = (uint32_t)ip + base_index;
+            if (offset >= min_offset(base_index, ip)) r = table_match(data, len, base_index, anchor, current, offset);
+        }
+        if (fizzle && r.length != 0) {  // parse/mod.rs:72-81: take bytes in front of the match while they agree
+            const uint64_t prev = r.start - r.distance;  // (never down to byte 0)
+            const uint64_t lim = min(min((uint64_t)(258 - r.length), r.start - last_match), prev > 1 ? prev - 1 : 0);
+            const uint32_t n = equal_bytes<false, false>(data + r.start, data + prev, 0, (uint32_t)lim, prev);
+            r.length += n;
+            r.start -= n;
         }
         ip++;
         return r;
@@ -447,8 +369,7 @@ struct GParserT {
                             if (h[j] == h[k]) offset = (uint32_t)p[j] + base_index;
                         hash[h[k]] = (uint32_t)p[k] + base_index;
                         if constexpr (kChain) links[((uint32_t)p[k] + base_index) % kGWindow] = offset;
-                        const uint32_t sub = (uint32_t)p[k] > 32768 ? (uint32_t)p[k] - 32768 : 0;
-                        if (offset >= max(base_index + sub, 1u)) {
+                        if (offset >= min_offset(base_index, p[k])) {
                             event = 3;
                             ev_off = offset;
                         }
@@ -469,21 +390,12 @@ struct GParserT {
                 ip = r.end() - 3;
                 return r;
             }
-            if constexpr (kChain) {
-                GT0(2);
-                const GMatch r = chain_walk(data, len, base_index, last_match, ev_cur, ev_off);
-                GT1(2);
-                ip++;
-                if (r.length != 0) return r;
-            } else {
-                uint32_t l;
-                uint64_t st;
-                GT0(2);
-                match_length<true>(ev_cur, data, len, last_match, ip, (uint64_t)(ev_off - base_index), l, st);
-                GT1(2);
-                ip++;
-                if (l >= 8) return GMatch{l, (uint32_t)(ev_p - (uint64_t)(ev_off - base_index)), st};
-            }
+            GT0(2);
+            const GMatch r = kChain ? chain_walk(data, len, base_index, last_match, ev_cur, ev_off)
+                                    : table_match(data, len, base_index, last_match, ev_cur, ev_off);
+            GT1(2);
+            ip++;
+            if (r.length != 0) return r;
             ip += (ip - last_match) >> kShift;
         }
         return GMatch{0, 0, 0};
@@ -491,7 +403,6 @@ struct GParserT {
 
     // ParserInner::advance (parse/mod.rs:105-114): the positions covered by a match go into the
     // table; four at a time (the loads are independent, the stores stay in position order)
-    template <bool RLE>
     __device__ void advance(const uint8_t* data, uint64_t len, uint32_t base_index, uint64_t end) {
         if constexpr (kChain) {  // HashChainMatchFinder::insert (hashchain.rs:109-114)
             const uint64_t stop = min(end, len - 8);
@@ -501,7 +412,7 @@ struct GParserT {
                 hash[h] = offset;
                 links[offset % kGWindow] = prev;
             }
-        } else if (!RLE) {
+        } else {
             const uint64_t stop = min(end, len - 8);
             uint64_t j = ip;
             for (; j + 4 <= stop; j += 4) {
@@ -591,12 +502,12 @@ struct GParserT {
                     if (m.length == 0) break;
                 }
                 GT0(3);
-                advance<false>(data, len, base_index, m.end());
+                advance(data, len, base_index, m.end());
                 GT1(3);
                 GMatch m2{0, 0, 0};
                 if (ip < max_ip) {
                     GT0(4);
-                    m2 = get_match<false>(data, len, base_index, true);
+                    m2 = get_match(data, len, base_index, true);
                     GT1(4);
                 } else if (!finish) {
                     break;
@@ -1554,32 +1465,131 @@ extern "C" int fdh_debug_gen_timers(uint64_t* host /* 8 x 32768 */) {
 }
 #endif
 
-// table bytes per resident stream; kind: 0 level 1, 1 RLE, 2 / 3 levels 2 / 3 (head table + link ring)
-extern "C" size_t fdh_deflate_general_hash_bytes(int kind) {
-    return kind == 1 ? 0 : ((size_t)fdh::kGHashSize + (kind >= 2 ? fdh::kGWindow : 0u)) * 4;
+// ---- the launch: plan, per-device workspace, the two kernels ----
+namespace {
+
+using fdh::GenMode;
+
+static_assert(fdh::kGenModes[FDH_MODE_LEVEL1 - 1].table_bytes == fdh::kGHashSize * 4 &&
+              fdh::kGenModes[FDH_MODE_LEVEL2 - 1].table_bytes == (fdh::kGHashSize + fdh::kGWindow) * 4, "launch.h's table sizes");
+
+// The parser runs one stream per lane and is bound by the latency of dependent loads: what helps is wavefronts in
+// flight.  A batch that does not fill the device with full wavefronts is given fewer lanes per wavefront and more
+// wavefronts -- 8 per CU at level 1 (208 VGPRs: two per SIMD), 16 per CU for the RLE parser (126 VGPRs, no hash
+// tables) -- and at level 1 the streams in flight are capped so that their hash tables (256 KiB each) stay below
+// 16 GiB.  (The cap was once 8 GiB and applied to the RLE parser too, which has no tables: 65 536 streams ran as
+// 1 024 wavefronts of 32 lanes in two rounds, one wavefront per SIMD.  All of them in flight: level 1 39.2 -> 31.7 ms,
+// RLE 25.4 -> 21.9 ms.)
+// Levels 2 and 3 run the same parser with the hash-chain finder, one stream per lane as well: a head table and a
+// link ring per stream (384 KiB), so fewer streams are resident under the same 16 GiB (43 690 instead of 65 536).
+// The chain parsers (211 VGPRs) have 8 wavefronts per CU resident like level 1, but are asked for twice as many, i.e.
+// half as many lanes each: 65 536 streams as 16 lanes x 2 730 wavefronts ran 42.9 / 499.7 ms at levels 2 / 3, as 32
+// lanes x 1 365 -- all that 16 GiB of tables allow at that width -- 48.3 / 562.6 ms.
+// FDH_GEN_LANES (1..64) sets the lanes, FDH_GEN_RESIDENT (64..2^20; levels 2 and 3 keep the 16 GiB) the streams in flight.
+struct GenPlan {
+    unsigned lanes, waves;  // streams per wavefront of the parser, wavefronts
+};
+GenPlan general_plan(uint64_t n, int cus, const GenMode& m) {
+    unsigned lanes = 64;
+    const uint64_t want_waves = (uint64_t)cus * m.waves_per_cu;
+    while (lanes > 4 && (n + lanes - 1) / lanes < want_waves) lanes /= 2;
+    if (const int v = fdh::env_int("FDH_GEN_LANES", 0); v >= 1 && v <= 64) lanes = (unsigned)v;
+    uint64_t max_resident = m.max_resident;
+    if (const int v = fdh::env_int("FDH_GEN_RESIDENT", 0); v >= 64 && v <= (1 << 20))
+        max_resident = m.chain ? std::min<uint64_t>((uint64_t)v, m.max_resident) : (uint64_t)v;
+    return {lanes, (unsigned)std::min<uint64_t>((n + lanes - 1) / lanes, std::max<uint64_t>(1, max_resident / lanes))};
 }
-// record slices for a batch whose inputs span `total_in` bytes: element counts
-extern "C" size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n) { return (size_t)fdh::g_match_slice(total_in, n) + 2; }
-extern "C" size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n) { return (size_t)fdh::g_block_slice(total_in, n) + 4; }
-extern "C" size_t fdh_deflate_general_match_record_bytes(void) { return sizeof(fdh::GMatchRec); }
-extern "C" size_t fdh_deflate_general_block_record_bytes(void) { return sizeof(fdh::GBlockRec); }
+
+// per-device workspace, grown on demand, never shrunk
+struct GenWork {
+    std::mutex mutex;         // the workspace is shared by the calls on ITS device only
+    void* hash = nullptr;     // the resident lanes' tables (GenMode::table_bytes each)
+    void* matches = nullptr;  // what the parser hands to the block writer, sliced per stream
+    void* blocks = nullptr;
+    void* nblocks = nullptr;
+    size_t hash_bytes = 0, match_bytes = 0, block_bytes = 0, nblock_bytes = 0;
+};
+GenWork g_gen_work[64];
+
+hipError_t failed(hipError_t e, const char* what) {
+    fdh_set_last_error((std::string(what) + ": " + hipGetErrorString(e)).c_str());
+    return e;
+}
+
+hipError_t grow(void** p, size_t* have, size_t want, const char* what, bool headroom = true) {
+    if (*have >= want) return hipSuccess;
+    if (hipError_t e = hipDeviceSynchronize(); e != hipSuccess) return failed(e, "hipDeviceSynchronize()");  // nobody may still be using the old buffer
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    const size_t sz = headroom ? want + want / 4 : want;  // headroom: batches of similar size do not reallocate
+    if (hipError_t e = hipMalloc(p, sz); e != hipSuccess) {
+        *p = nullptr;
+        return failed(e, what);
+    }
+    *have = sz;
+    return hipSuccess;
+}
+
+}  // namespace
+
+// what general_plan gives a batch of n streams on a device of `cus` CUs: out = {lanes, waves}; needs no device
+extern "C" int fdh_debug_general_plan(uint64_t n, int cus, uint32_t mode, uint32_t* out) {
+    const GenMode* m = fdh::gen_mode(mode);
+    if (!m || !out || n == 0) return -1;
+    const GenPlan p = general_plan(n, cus, *m);
+    out[0] = p.lanes;
+    out[1] = p.waves;
+    return 0;
+}
 
 extern "C" int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                                          uint32_t* out_len, uint64_t n, int kind, void* hash, void* matches, void* blocks,
-                                          uint32_t* nblocks, unsigned waves, unsigned lanes, hipStream_t stream) {
+                                          uint32_t* out_len, uint64_t n, uint32_t mode, uint64_t total_in, hipStream_t stream) {
+    const GenMode* m = fdh::gen_mode(mode);
     if (n == 0) return 0;
-    fdh::GParseArgs p{in, in_off, n, static_cast<uint32_t*>(hash), static_cast<fdh::GMatchRec*>(matches),
-                      static_cast<fdh::GBlockRec*>(blocks), nblocks, lanes};
-    if (kind == 1)
-        hipLaunchKernelGGL(fdh::deflate_parse_kernel<true>, dim3(waves), dim3(fdh::kWave), 0, stream, p);
-    else if (kind == 2)
-        hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 2>), dim3(waves), dim3(fdh::kWave), 0, stream, p);
-    else if (kind == 3)
-        hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 3>), dim3(waves), dim3(fdh::kWave), 0, stream, p);
+    if (!m) return -1;
+    int dev = 0, cus = 0;
+    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return (int)failed(e, "hipGetDevice(&dev)");
+    if (dev < 0 || dev >= 64) return (int)failed(hipErrorInvalidDevice, "general encoder: device ordinal out of range");
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    GenPlan plan = general_plan(n, cus, *m);
+    GenWork& w = g_gen_work[dev];
+    std::lock_guard<std::mutex> lock(w.mutex);
+    hipError_t e = hipSuccess;
+    if (!m->rle) {
+        // exactly the resident lanes' tables (no headroom: at the cap that is the whole 16 GiB); on a smaller or busy
+        // device the batch runs with fewer resident wavefronts instead of failing
+        for (;;) {
+            e = grow(&w.hash, &w.hash_bytes, (size_t)plan.waves * plan.lanes * m->table_bytes, "hipMalloc(hash tables)", false);
+            if (e == hipSuccess || plan.waves <= 1) break;
+            (void)hipGetLastError();
+            plan.waves /= 2;
+        }
+    }
+    // the record arrays are sized by the bytes the batch spans
+    if (e == hipSuccess)
+        e = grow(&w.matches, &w.match_bytes, (size_t)(fdh::g_match_slice(total_in, n) + 2) * sizeof(fdh::GMatchRec),
+                 "hipMalloc(back-reference records)");
+    if (e == hipSuccess)
+        e = grow(&w.blocks, &w.block_bytes, (size_t)(fdh::g_block_slice(total_in, n) + 4) * sizeof(fdh::GBlockRec), "hipMalloc(block records)");
+    if (e == hipSuccess) e = grow(&w.nblocks, &w.nblock_bytes, (size_t)n * 4, "hipMalloc(block counts)");
+    if (e != hipSuccess) return (int)e;
+    uint32_t* nblocks = static_cast<uint32_t*>(w.nblocks);
+    fdh::GParseArgs p{in, in_off, n, static_cast<uint32_t*>(w.hash), static_cast<fdh::GMatchRec*>(w.matches),
+                      static_cast<fdh::GBlockRec*>(w.blocks), nblocks, plan.lanes};
+    const dim3 grid(plan.waves), block(fdh::kWave);
+    if (m->rle)
+        hipLaunchKernelGGL(fdh::deflate_parse_kernel<true>, grid, block, 0, stream, p);
+    else if (m->chain == 2)
+        hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 2>), grid, block, 0, stream, p);
+    else if (m->chain == 3)
+        hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 3>), grid, block, 0, stream, p);
     else
-        hipLaunchKernelGGL(fdh::deflate_parse_kernel<false>, dim3(waves), dim3(fdh::kWave), 0, stream, p);
-    fdh::GWriteArgs w{in, in_off, out, out_off, out_len, n, static_cast<const fdh::GMatchRec*>(matches),
-                      static_cast<const fdh::GBlockRec*>(blocks), nblocks};
-    hipLaunchKernelGGL(fdh::deflate_write_kernel, dim3((unsigned)n), dim3(fdh::kWave), 0, stream, w);
-    return (int)hipGetLastError();
+        hipLaunchKernelGGL(fdh::deflate_parse_kernel<false>, grid, block, 0, stream, p);
+    fdh::GWriteArgs wa{in, in_off, out, out_off, out_len, n, p.matches, p.blocks, nblocks};
+    hipLaunchKernelGGL(fdh::deflate_write_kernel, dim3((unsigned)n), block, 0, stream, wa);
+    if (e = hipGetLastError(); e != hipSuccess) return (int)failed(e, "general-encoder kernel launch");
+    // the workspace is per device, not per stream: calls are serialised by finishing this one
+    if (e = hipStreamSynchronize(stream); e != hipSuccess) return (int)failed(e, "hipStreamSynchronize(stream)");
+    return 0;
 }

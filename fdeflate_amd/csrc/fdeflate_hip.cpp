@@ -21,10 +21,9 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
-int hip_fail(hipError_t e, const char* what) {
-    return fail(e == hipErrorOutOfMemory ? FDH_ERR_OUT_OF_MEMORY : FDH_ERR_HIP,
-                std::string(what) + ": " + hipGetErrorString(e));
-}
+int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? FDH_ERR_OUT_OF_MEMORY : FDH_ERR_HIP; }
+
+int hip_fail(hipError_t e, const char* what) { return fail(hip_code(e), std::string(what) + ": " + hipGetErrorString(e)); }
 
 #define HIP_TRY(expr)                                  \
     do {                                               \
@@ -506,35 +505,6 @@ int fdh_png_frame_mixed_batch(uint8_t* file, const uint64_t* file_off, const uin
                     file_len, png_status, n, stream_of(hip_stream)));
 }
 
-// ---- general encoder (levels 1-3 / RLE): per-device workspace, grown on demand, never shrunk ----
-namespace {
-struct GenWork {
-    std::mutex mutex;         // the workspace is shared by the calls on ITS device only
-    void* hash = nullptr;     // per resident lane of the parser one 64 Ki-entry table (level 1), + a 32 Ki-entry link ring (levels 2, 3)
-    void* matches = nullptr;  // what the parser hands to the block writer, sliced per stream
-    void* blocks = nullptr;
-    void* nblocks = nullptr;
-    size_t hash_bytes = 0, match_bytes = 0, block_bytes = 0, nblock_bytes = 0;
-};
-GenWork g_gen_work[64];
-
-int grow(void** p, size_t* have, size_t want, const char* what, bool headroom = true) {
-    if (*have >= want) return FDH_SUCCESS;
-    HIP_TRY(hipDeviceSynchronize());  // nobody may still be using the old buffer
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    const size_t sz = headroom ? want + want / 4 : want;  // headroom: batches of similar size do not reallocate
-    hipError_t e = hipMalloc(p, sz);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return hip_fail(e, what);
-    }
-    *have = sz;
-    return FDH_SUCCESS;
-}
-}  // namespace
-
 uint64_t fdh_compress_bound(uint64_t len) { return len + len / 2 + 1024; }
 
 int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
@@ -542,17 +512,14 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
     if (n == 0) return FDH_SUCCESS;
     if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
     if (!out) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");  // (`in` may be null for a batch of empty inputs: below)
-    if (mode != FDH_MODE_LEVEL1 && mode != FDH_MODE_RLE && mode != FDH_MODE_LEVEL2 && mode != FDH_MODE_LEVEL3)
-        return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
+    if (!fdh::gen_mode(mode)) return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call");
     if (!have_device()) return no_device();
     hipStream_t stream = stream_of(hip_stream);
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) return fail(FDH_ERR_INVALID_ARGUMENT, "device ordinal out of range");
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    // the record arrays are sized by the bytes the batch spans
+    // the launcher sizes its record arrays by the bytes the batch spans
     uint64_t ends[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&ends[0], in_off, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipMemcpyAsync(&ends[1], in_off + n, 8, hipMemcpyDeviceToHost, stream));
@@ -561,62 +528,9 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
     const uint64_t total_in = ends[1] - ends[0];
     // an empty input has a defined encoding (78 01 03 00 00 00 00 01), and a zero-element buffer has no address
     if (!in && total_in != 0) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");
-    // The parser runs one stream per lane and is bound by the latency of dependent loads: what helps is wavefronts in
-    // flight.  A batch that does not fill the device with full wavefronts is given fewer lanes per wavefront and more
-    // wavefronts -- 8 per CU at level 1 (201 VGPRs: two per SIMD), 16 per CU for the RLE parser (126 VGPRs, no hash
-    // tables) -- and at level 1 the streams in flight are capped so that their hash tables (256 KiB each) stay below
-    // 16 GiB.  (Round 5: the cap was 8 GiB and applied to the RLE parser too, which has no tables: 65 536 streams ran as
-    // 1 024 wavefronts of 32 lanes in two rounds, one wavefront per SIMD.  All of them in flight: level 1 39.2 -> 31.7 ms,
-    // RLE 25.4 -> 21.9 ms.)
-    // Levels 2 and 3 run the same parser with the hash-chain finder, one stream per lane as well: a head table and a
-    // link ring per stream (384 KiB), so fewer streams are resident under the same 16 GiB (43 690 instead of 65 536).
-    const bool rle = mode == FDH_MODE_RLE;
-    const int kind = rle ? 1 : mode == FDH_MODE_LEVEL2 ? 2 : mode == FDH_MODE_LEVEL3 ? 3 : 0;  // the launcher's numbering
-    const size_t table_bytes = fdh_deflate_general_hash_bytes(kind);
-    const uint64_t table_cap = rle ? (1ull << 40) : (16ull << 30) / table_bytes;
-    unsigned lanes = 64;
-    // (the chain parsers: 204 VGPRs, 8 wavefronts per CU resident like level 1, but asked for twice as many, i.e. half as
-    // many lanes each: 65 536 streams as 16 lanes x 2 730 wavefronts ran 42.9 / 499.7 ms at levels 2 / 3, as 32 lanes x 1 365
-    // -- all that 16 GiB of tables allow at that width -- 48.3 / 562.6 ms)
-    const uint64_t want_waves = (uint64_t)cus * (kind == 0 ? 8 : 16);
-    while (lanes > 4 && (n + lanes - 1) / lanes < want_waves) lanes /= 2;
-    if (const char* e = std::getenv("FDH_GEN_LANES")) {
-        const int v = std::atoi(e);
-        if (v >= 1 && v <= 64) lanes = (unsigned)v;
-    }
-    uint64_t max_resident = table_cap;
-    if (const char* e = std::getenv("FDH_GEN_RESIDENT")) {
-        const long long v = std::atoll(e);
-        if (v >= 64 && v <= (1 << 20)) max_resident = kind >= 2 ? std::min<uint64_t>((uint64_t)v, table_cap) : (uint64_t)v;  // (the new modes keep the 16 GiB)
-    }
-    unsigned waves = (unsigned)std::min<uint64_t>((n + lanes - 1) / lanes, std::max<uint64_t>(1, max_resident / lanes));
-    GenWork& w = g_gen_work[dev];
-    std::lock_guard<std::mutex> lock(w.mutex);
-    int rc = FDH_SUCCESS;
-    if (!rle) {
-        // exactly the resident lanes' tables (no headroom: at the cap that is the documented 8 GiB);
-        // on a smaller or busy device the batch runs with fewer resident wavefronts instead of failing
-        for (;;) {
-            rc = grow(&w.hash, &w.hash_bytes, (size_t)waves * lanes * table_bytes, "hipMalloc(hash tables)", false);
-            if (rc == FDH_SUCCESS || waves <= 1) break;
-            (void)hipGetLastError();
-            waves /= 2;
-        }
-    }
-    if (rc == FDH_SUCCESS)
-        rc = grow(&w.matches, &w.match_bytes, fdh_deflate_general_match_records(total_in, n) * fdh_deflate_general_match_record_bytes(),
-                  "hipMalloc(back-reference records)");
-    if (rc == FDH_SUCCESS)
-        rc = grow(&w.blocks, &w.block_bytes, fdh_deflate_general_block_records(total_in, n) * fdh_deflate_general_block_record_bytes(),
-                  "hipMalloc(block records)");
-    if (rc == FDH_SUCCESS) rc = grow(&w.nblocks, &w.nblock_bytes, (size_t)n * 4, "hipMalloc(block counts)");
-    if (rc != FDH_SUCCESS) return rc;
-    rc = launched("general-encoder kernel launch", fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, kind, w.hash, w.matches,
-                                                                          w.blocks, static_cast<uint32_t*>(w.nblocks), waves, lanes, stream));
-    if (rc != FDH_SUCCESS) return rc;
-    // the workspace is per device, not per stream: calls are serialised by finishing this one
-    HIP_TRY(hipStreamSynchronize(stream));
-    return FDH_SUCCESS;
+    // the launcher (deflate_general.hip) plans the launch, keeps the workspace and has left the text of a failure
+    const int rc = fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, mode, total_in, stream);
+    return rc == 0 ? FDH_SUCCESS : hip_code(static_cast<hipError_t>(rc));
 }
 
 // ---- single-buffer conveniences (host memory) --------------------------------------------
@@ -694,12 +608,19 @@ int fdh_decompress_to_vec(const uint8_t* input, size_t input_len, uint8_t** outp
     return inflate_growing(input, input_len, 0xFFFFFFF0ull, output, output_len, stream_status);
 }
 
-static int compress_one(int kind, const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
-    const bool stored = kind == 1;
+// which encoder a host call runs: the ultra-fast one, the stored one, or the general one in an FDH_MODE_*
+struct Encoder {
+    enum Type { kUltraFast, kStored, kGeneral } type;
+    uint32_t mode = 0;
+};
+
+static int compress_one(Encoder enc, const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
     if (!output || !output_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null result pointer");
     if (input_len >= 0xFFFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "buffer too large (>= 4 GiB)");
     if (!have_device()) return no_device();
-    size_t cap = (size_t)(stored ? fdh_stored_size(input_len) : (kind == 0 ? fdh_ultrafast_bound(input_len) : fdh_compress_bound(input_len)));
+    const size_t cap = (size_t)(enc.type == Encoder::kStored      ? fdh_stored_size(input_len)
+                                : enc.type == Encoder::kUltraFast ? fdh_ultrafast_bound(input_len)
+                                                                  : fdh_compress_bound(input_len));
     DevBuf d_in, d_out, d_meta;
     HIP_TRY(d_in.alloc(input_len));
     HIP_TRY(d_out.alloc(cap));
@@ -709,11 +630,9 @@ static int compress_one(int kind, const uint8_t* input, size_t input_len, uint8_
     HIP_TRY(hipMemcpy(d_meta.p, meta, sizeof(meta), hipMemcpyHostToDevice));
     uint64_t* m = d_meta.as<uint64_t>();
     uint32_t* res = reinterpret_cast<uint32_t*>(m + 4);
-    int rc = stored      ? fdh_deflate_stored_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
-             : kind == 0 ? fdh_deflate_ultrafast_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
-                         : fdh_deflate_general_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1,
-                                                     kind == 2 ? FDH_MODE_LEVEL1 : kind == 3 ? FDH_MODE_RLE : kind == 4 ? FDH_MODE_LEVEL2 : FDH_MODE_LEVEL3,
-                                                     nullptr);
+    int rc = enc.type == Encoder::kStored      ? fdh_deflate_stored_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
+             : enc.type == Encoder::kUltraFast ? fdh_deflate_ultrafast_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
+                                               : fdh_deflate_general_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, enc.mode, nullptr);
     if (rc != FDH_SUCCESS) return rc;
     HIP_TRY(hipDeviceSynchronize());
     uint32_t n32 = 0;
@@ -734,32 +653,28 @@ static int compress_one(int kind, const uint8_t* input, size_t input_len, uint8_
 }
 
 int fdh_compress_to_vec_ultra_fast(const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
-    return compress_one(0, input, input_len, output, output_len);
+    return compress_one({Encoder::kUltraFast}, input, input_len, output, output_len);
 }
 
 int fdh_compress_to_vec_stored(const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
-    return compress_one(1, input, input_len, output, output_len);
+    return compress_one({Encoder::kStored}, input, input_len, output, output_len);
 }
 
 int fdh_compress_to_vec(const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
-    return compress_one(2, input, input_len, output, output_len);
+    return compress_one({Encoder::kGeneral, FDH_MODE_LEVEL1}, input, input_len, output, output_len);
 }
 
 int fdh_compress_to_vec_rle(const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
-    return compress_one(3, input, input_len, output, output_len);
+    return compress_one({Encoder::kGeneral, FDH_MODE_RLE}, input, input_len, output, output_len);
 }
 
 int fdh_compress_to_vec_with_level(const uint8_t* input, size_t input_len, uint32_t level, uint8_t** output,
                                    size_t* output_len) {
-    switch (level) {
-        case 0: return compress_one(1, input, input_len, output, output_len);
-        case 1: return compress_one(2, input, input_len, output, output_len);
-        case 2: return compress_one(4, input, input_len, output, output_len);
-        case 3: return compress_one(5, input, input_len, output, output_len);
-        default:
-            return fail(FDH_ERR_INVALID_ARGUMENT,
-                        "compression level not provided: levels 0, 1, 2 and 3 are (4-9, the lazy parser, are not)");
-    }
+    static const Encoder kLevels[] = {{Encoder::kStored}, {Encoder::kGeneral, FDH_MODE_LEVEL1}, {Encoder::kGeneral, FDH_MODE_LEVEL2},
+                                      {Encoder::kGeneral, FDH_MODE_LEVEL3}};
+    if (level > 3)
+        return fail(FDH_ERR_INVALID_ARGUMENT, "compression level not provided: levels 0, 1, 2 and 3 are (4-9, the lazy parser, are not)");
+    return compress_one(kLevels[level], input, input_len, output, output_len);
 }
 
 void fdh_free(void* p) { std::free(p); }

@@ -36,15 +36,10 @@ int fdh_launch_png_filter_deflate_ultrafast(const uint8_t* pix, const uint64_t* 
 int fdh_launch_png_filter_deflate_ultrafast_mixed(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
                                                   uint8_t* out, const uint64_t* out_off, uint32_t* out_len, const fdh_png_info* info,
                                                   const uint32_t* upstream, uint32_t* png_status, uint64_t n, hipStream_t stream);
-// deflate_general.hip
+// deflate_general.hip: `mode` is an FDH_MODE_*, `total_in` = in_off[n] - in_off[0].  Plans the launch, grows the device's
+// workspace, and returns when both kernels have finished; on failure fdh_last_error's text names the step that failed.
 int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
-                               uint64_t n, int kind, void* hash, void* matches, void* blocks, uint32_t* nblocks, unsigned waves,
-                               unsigned lanes, hipStream_t stream);
-size_t fdh_deflate_general_hash_bytes(int kind);
-size_t fdh_deflate_general_match_records(uint64_t total_in, uint64_t n);
-size_t fdh_deflate_general_block_records(uint64_t total_in, uint64_t n);
-size_t fdh_deflate_general_match_record_bytes(void);
-size_t fdh_deflate_general_block_record_bytes(void);
+                               uint64_t n, uint32_t mode, uint64_t total_in, hipStream_t stream);
 // png_filter.hip
 int fdh_launch_png_unfilter(const uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, uint32_t* status,
                             const uint32_t* gate, const uint32_t* gate_len, uint64_t n, uint32_t row_bytes, uint32_t bpp,
@@ -131,6 +126,22 @@ inline int env_int(const char* name, int fallback) {
     const char* e = std::getenv(name);
     return e ? std::atoi(e) : fallback;
 }
+
+// The general encoder's modes, by FDH_MODE_* (gen_mode: nullptr for any other number).
+struct GenMode {
+    bool rle;               // RleParser: runs only, no match finder and no tables
+    int chain;              // 0: HashTableMatchFinder; 2 / 3: the level whose HashChainMatchFinder the parser uses
+    uint64_t table_bytes;   // per resident stream: a 64 Ki-entry table, at levels 2 and 3 also a 32 Ki-entry link ring
+    unsigned waves_per_cu;  // the parser's wavefronts wanted per CU before a wavefront is given more streams
+    uint64_t max_resident;  // streams in flight: 16 GiB of tables at the most
+};
+constexpr GenMode gen_mode_of(bool rle, int chain) {
+    const uint64_t table_bytes = rle ? 0 : (65536u + (chain ? 32768u : 0u)) * 4;
+    return {rle, chain, table_bytes, !rle && !chain ? 8u : 16u, rle ? 1ull << 40 : (16ull << 30) / table_bytes};
+}
+constexpr GenMode kGenModes[] = {gen_mode_of(false, 0), gen_mode_of(true, 0), gen_mode_of(false, 2), gen_mode_of(false, 3)};
+static_assert(FDH_MODE_LEVEL1 == 1 && FDH_MODE_RLE == 2 && FDH_MODE_LEVEL2 == 3 && FDH_MODE_LEVEL3 == 4, "kGenModes' order");
+inline const GenMode* gen_mode(uint32_t mode) { return mode >= 1 && mode <= 4 ? &kGenModes[mode - 1] : nullptr; }
 
 // Wavefronts per range / threads per file in the kernels of png_file.hip and png_mixed.hip that serve one file per
 // workgroup: a batch that fills the device by its count alone gets one wavefront per item.

@@ -3,7 +3,7 @@ streams, no compiled code.
 
 The oracle (oracle/fdeflate_oracle.c) has level 1 and RLE only, so the expected bytes of levels 2 and 3
 come from here.  tests/test_level_model.py pins this model against the oracle where the two overlap
-(level 1 and RLE over the oracle tests' encoder inputs): that pins the parser, the runs,
+(level 1 and RLE over the oracle tests' encoder inputs and the run-edge inputs): that pins the parser, the runs,
 match_length::<true>, block cutting and the whole block writer.  What no second implementation pins is
 HashChainMatchFinder (hashchain.rs) and match_length::<false> (matchfinder/mod.rs:71-76), about 150
 lines here (`Chain`, and the `min8 = False` branch of `match_length`).
@@ -23,8 +23,11 @@ the last call are in `last_counters` (a dict, empty for level 1 and RLE):
   alias     visits of a candidate at exactly ip - 32768 (its link slot was just overwritten)
   unwritten reads of a link slot never written in this stream
   maxsteps  the longest walk
+and `last_exits` counts, for the last call at any level, how the device's counter of equal bytes (equal_bytes in
+deflate_general.hip) would have ended each of its calls: (use, exit) -> calls, see `_note_exit`.
 """
 import bisect
+import collections
 import functools
 import zlib
 
@@ -51,6 +54,29 @@ for _s in range(28):
 LENGTH_TO_SYMBOL[255] = 285     # 258 has a symbol of its own
 
 last_counters = {}
+last_exits = collections.Counter()
+_exits = collections.Counter()      # of the call that is running
+
+USES = ("match_back", "match_fwd", "run_back", "run_fwd")       # the walks from a match / inside a run, either way
+EXITS = ("group32", "group8", "wide", "bytes", "limit")
+
+
+def _note_exit(use, limit, n, room):
+    """The device counts equal bytes 32 at a time (four loads in flight), then 8 at a time, then takes a tail shorter
+    than 8 with one wide load where 8 bytes are readable (`room`: the bytes readable in the walking direction), byte
+    by byte where not.  A call that may test `limit` bytes and finds n equal ends at the limit, or at a difference
+    inside a group of 32, a group of 8, the wide tail or the byte tail.  A call with nothing to test is not counted."""
+    assert 0 <= n <= limit <= room, (use, limit, n, room)
+    if limit == 0:
+        return
+    whole = limit - limit % 8
+    if n == limit:
+        e = "limit"
+    elif n < whole:
+        e = "group32" if n < limit - limit % 32 else "group8"
+    else:
+        e = "wide" if whole + 8 <= room else "bytes"
+    _exits[use, e] += 1
 
 
 def ld64(d, i):
@@ -96,14 +122,19 @@ def match_length(min8, value, data, anchor, ip, prev):
         x = value ^ pv
         length = 8 if x == 0 else _tz8(x)      # u64::trailing_zeros of 0 is 64
     # while length < 258 && ip > anchor && prev_index > 0 && data[ip - 1] == data[prev_index - 1]
-    n = _equal_back(data, ip, prev, min(258 - length, ip - anchor, prev))
+    first8 = length == 8
+    lim = min(258 - length, ip - anchor, prev)
+    n = _equal_back(data, ip, prev, lim)
+    _note_exit("match_back", lim, n, prev)
     length += n
     ip -= n
     prev -= n
     # chunks of 8, then the remainder byte by byte: the count of equal bytes either way
     sl = min(len(data) - ip - length, 258 - length)
-    length += _equal_fwd(data, ip + length, prev + length, sl)
-    return length, ip
+    k = _equal_fwd(data, ip + length, prev + length, sl)
+    if first8:      # (fewer than 8: the next byte is the one that differed, the device does not look)
+        _note_exit("match_fwd", sl, k, len(data) - ip - length)
+    return length + k, ip
 
 
 def rle_match(data, last_match, ip):
@@ -114,10 +145,12 @@ def rle_match(data, last_match, ip):
     while start > min_start and data[start - 2] == value:
         start -= 1
         length += 1
+    _note_exit("run_back", max(ip + 1 - min_start, 0), length - 4, ip)
     e = start + length
     lim = min(len(data) - e, 258 - length)
     run = data[e:e + lim]
     k = len(run) - len(run.lstrip(bytes([value]))) if lim > 0 else 0
+    _note_exit("run_fwd", lim, k, len(data) - e)
     return [length + k, 1, start]
 
 
@@ -423,11 +456,14 @@ class Parser:
             return m
         anchor = self.ip if fizzle else self.last_match
         m = self.mf.get_and_insert(data, base, anchor, self.ip, cur)
-        if fizzle:
+        if fizzle and m[0]:
+            start, prev = m[2], m[2] - m[1]
+            lim = min(258 - m[0], start - self.last_match, max(prev - 1, 0))
             while (m[0] < 258 and m[2] > self.last_match and m[2] > m[1] + 1
                    and data[m[2] - 1] == data[m[2] - m[1] - 1]):
                 m[0] += 1
                 m[2] -= 1
+            _note_exit("match_back", lim, start - m[2], prev)
         assert m[0] == 0 or self.last_match <= m[2]
         self.ip += 1
         return m
@@ -518,7 +554,8 @@ class Parser:
 
 
 def _compress(data, shift, mf, rle):
-    global last_counters
+    global last_counters, last_exits
+    _exits.clear()
     data = bytes(data)
     assert len(data) <= 1 << 30
     w = BitWriter()
@@ -531,6 +568,7 @@ def _compress(data, shift, mf, rle):
     w.flush()
     w.raw((zlib.adler32(data) & 0xFFFFFFFF).to_bytes(4, "big"))
     last_counters = dict(mf.c)
+    last_exits = collections.Counter(_exits)
     return bytes(w.out)
 
 
@@ -552,15 +590,31 @@ def compress_rle(data):
 
 @functools.lru_cache(maxsize=None)
 def model_results():
-    """level -> (list of (input, stream, counters)) over the encoder inputs and the chain inputs of tests/streams.py;
-    computed once per process (the GPU tests use the same streams as expected bytes)."""
+    """level -> (list of (input, stream, counters)) over the encoder inputs, the chain inputs and the run-edge inputs
+    of tests/streams.py, and "exits" -> the sum of last_exits over all of them; computed once per process (the GPU
+    tests use the same streams as expected bytes)."""
     import streams
-    inputs = streams.encoder_inputs() + streams.chain_inputs()
-    res = {}
+    inputs = streams.encoder_inputs() + streams.chain_inputs() + streams.run_edge_inputs()
+    res = {"exits": collections.Counter()}
     for level in (2, 3):
         rows = []
         for x in inputs:
             out = compress(x, level)
             rows.append((x, out, dict(last_counters)))
+            res["exits"] += last_exits
         res[level] = rows
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_level_results():
+    """Level 1 and RLE, which the oracle has too, over the encoder inputs and the run-edge inputs: "inputs", 1 and
+    "rle" -> the model's streams in that order, "exits" -> the sum of last_exits; computed once per process."""
+    import streams
+    res = {"inputs": streams.encoder_inputs() + streams.run_edge_inputs(), 1: [], "rle": [], "exits": collections.Counter()}
+    for x in res["inputs"]:
+        res[1].append(compress(x, 1))
+        res["exits"] += last_exits
+        res["rle"].append(compress_rle(x))
+        res["exits"] += last_exits
     return res

@@ -503,3 +503,34 @@ def chain_inputs():
     out.append(b"abcdefgh" * 5000)
     out.append(bytes(range(256)) * 300)
     return out
+
+
+def late_match_inputs():
+    """24 streams whose first match comes late and reaches far back: 1 100 .. 6 000 random bytes, then a copy of their
+    own bytes 100..400 (a 300-byte match whose walk backwards has hundreds of bytes of room), then 0, 3, 9 or 40
+    random bytes."""
+    r = np.random.default_rng(29)
+    out = []
+    for lead in (1100, 1500, 2100, 3000, 4200, 6000):
+        for tail in (0, 3, 9, 40):
+            head = bytes(r.integers(0, 256, lead, dtype=np.uint8))
+            out.append(head + head[100:400] + bytes(r.integers(0, 256, tail, dtype=np.uint8)))
+    return out
+
+
+def run_edge_inputs():
+    """Inputs for the parser's counters of equal bytes (runs, and matches of period 3) at the edges of a stream: a
+    periodic body of distinct bytes below 200, of every length around the counters' group sizes (8, 32) and the longest
+    match (258), with 0 .. 9 random bytes from 200..255 in front of it and behind it, so that a count starts or ends
+    fewer than 8 bytes from either end of the buffer; then late_match_inputs().  3 948 + 24 streams, about 400 KB."""
+    r = np.random.default_rng(23)
+    lengths = list(range(4, 21)) + list(range(31, 42)) + list(range(63, 74)) + list(range(255, 263))
+    out = []
+    for period in (1, 3):
+        for lead in (0, 1, 2, 3, 7, 8, 9):
+            for tail in (0, 1, 2, 7, 8, 9):
+                for n in lengths:
+                    unit = bytes(r.choice(200, period, replace=False).astype(np.uint8))
+                    body = (unit * (n // period + 1))[:n]
+                    out.append(bytes(r.integers(200, 256, lead, dtype=np.uint8)) + body + bytes(r.integers(200, 256, tail, dtype=np.uint8)))
+    return out + late_match_inputs()

@@ -223,3 +223,39 @@ def test_levels_2_and_3_roundtrip_at_scale(harness):
         trailer = (tr[:, 0] << 24) | (tr[:, 1] << 16) | (tr[:, 2] << 8) | tr[:, 3]
         assert torch.equal(trailer, adler.to(torch.int64) & 0xFFFFFFFF), level
         del comp, out
+
+
+@pytest.fixture(scope="module")
+def edge_cases():
+    """(inputs, mode -> expected streams) over streams.run_edge_inputs(), which ends with the late-match family: the
+    oracle's bytes at level 1 and RLE, the model's at levels 2 and 3 (the tail of level_model.model_results())."""
+    import fdeflate_amd as fd
+    raws = streams.run_edge_inputs()
+    want = {fd.MODE_LEVEL1: [ob.compress_level1(x) for x in raws], fd.MODE_RLE: [ob.compress_rle(x) for x in raws]}
+    for level, mode in _modes():
+        rows = lm.model_results()[level][-len(raws):]
+        assert [x for x, _, _ in rows] == raws
+        want[mode] = [o for _, o, _ in rows]
+    return raws, want
+
+
+@pytest.mark.parametrize("lanes", [None, "1"])
+def test_run_edge_inputs_bit_exact_in_all_four_modes(harness, edge_cases, lanes, monkeypatch):
+    """The inputs that take the parser's counter of equal bytes through every exit (tests/test_level_model.py counts
+    them), one batch per mode with guard bytes behind every slot: bit-exact at the library's own launch shape and with
+    one stream per wavefront."""
+    import fdeflate_amd as fd
+    monkeypatch.delenv("FDH_GEN_RESIDENT", raising=False)
+    if lanes is None:
+        monkeypatch.delenv("FDH_GEN_LANES", raising=False)
+    else:
+        monkeypatch.setenv("FDH_GEN_LANES", lanes)
+    raws, want = edge_cases
+    caps = [fd.compress_bound(len(x)) for x in raws]
+    for mode in (fd.MODE_LEVEL1, fd.MODE_RLE, fd.MODE_LEVEL2, fd.MODE_LEVEL3):
+        ln, slots, faults = harness.gpu_encode_slots(
+            lambda a, b, c, d: fd.deflate_general_batch(a, b, c, d, mode), raws, caps, EMPTY)
+        assert not faults, (mode, lanes, faults[:8])
+        for i, w in enumerate(want[mode]):
+            assert int(ln[i]) == len(w) and slots[i][:len(w)].tobytes() == w, (mode, lanes, i, len(raws[i]), int(ln[i]), len(w))
+            assert np.all(slots[i][len(w):] == 0x5A), (mode, lanes, i, "wrote behind its stream")

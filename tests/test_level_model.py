@@ -3,11 +3,15 @@ encoder levels 2 and 3 (the oracle has level 1 and RLE only), and of the level-s
 behaviour without a GPU.
 
 - the pin: the model equals the oracle, byte for byte, at level 1 and in RLE mode over the oracle
-  tests' encoder inputs -- parser, runs, match_length::<true>, block cutting, the block writer;
+  tests' encoder inputs and the run-edge inputs -- parser, runs, match_length::<true>, block cutting,
+  the block writer;
 - levels 2 and 3 round-trip through zlib and stay inside fdh_compress_bound's formula;
 - the chain inputs reach every exit of the chain search at both levels (coverage is asserted, not hoped
-  for).  What stays unpinned by a second implementation is the chain finder and match_length::<false>.
+  for).  What stays unpinned by a second implementation is the chain finder and match_length::<false>;
+- the inputs reach every exit of the device's counter of equal bytes in each of its four uses;
+- the general encoder's launch plan (lanes, wavefronts), through the library's hook: no device needed.
 """
+import ctypes as C
 import zlib
 
 import pytest
@@ -23,9 +27,11 @@ def compress_bound(n):
 
 
 def test_model_is_pinned_by_the_oracle_at_level1_and_rle():
-    for i, x in enumerate(streams.encoder_inputs()):
-        assert lm.compress(x, 1) == ob.compress_level1(x), ("level 1", i, len(x))
-        assert lm.compress_rle(x) == ob.compress_rle(x), ("rle", i, len(x))
+    res = lm.oracle_level_results()
+    assert len(res["inputs"]) == len(streams.encoder_inputs()) + 3948 + 24
+    for i, x in enumerate(res["inputs"]):
+        assert res[1][i] == ob.compress_level1(x), ("level 1", i, len(x))
+        assert res["rle"][i] == ob.compress_rle(x), ("rle", i, len(x))
 
 
 def test_model_empty_input_kat():
@@ -53,6 +59,50 @@ def test_chain_inputs_reach_every_exit_of_the_search(level):
         assert tot[k] > 0, (level, k, tot)
     assert tot["maxsteps"] == 16, (level, tot)
     assert tot["unwritten"] == 0, (level, tot)
+
+
+def test_inputs_reach_every_exit_of_the_counter_of_equal_bytes():
+    """encoder_inputs() + chain_inputs() + run_edge_inputs() at levels 2 and 3, the first and the last of them at
+    level 1 and RLE as well: each of the counter's four uses ends at a difference in a group of 32, in a group of 8,
+    in the wide tail and in the byte tail, and at its limit."""
+    tot = lm.model_results()["exits"] + lm.oracle_level_results()["exits"]
+    for use in lm.USES:
+        print("%-10s %s" % (use, "  ".join("%s %d" % (e, tot[use, e]) for e in lm.EXITS)))
+    for use in lm.USES:
+        for e in lm.EXITS:
+            assert tot[use, e] > 0, (use, e)
+
+
+def _general_plan(n, mode, cus=256):
+    from fdeflate_amd import _lib
+    out = (C.c_uint32 * 2)()
+    assert _lib.lib().fdh_debug_general_plan(C.c_uint64(n), C.c_int(cus), C.c_uint32(mode), out) == 0
+    return out[0], out[1]
+
+
+def test_general_plan_is_pinned(monkeypatch):
+    """(lanes, wavefronts) of the parser's launch on 256 CUs.  By hand: lanes halve from 64 down to 4 while
+    ceil(n / lanes) is below 256 x 8 = 2 048 wavefronts at level 1, 256 x 16 = 4 096 otherwise; the wavefronts are
+    ceil(n / lanes), at most (streams resident) / lanes, where 16 GiB of tables hold 65 536 streams at level 1
+    (256 KiB each), 43 690 at levels 2 and 3 (384 KiB), and RLE has no tables."""
+    import fdeflate_amd as fd
+    monkeypatch.delenv("FDH_GEN_LANES", raising=False)
+    monkeypatch.delenv("FDH_GEN_RESIDENT", raising=False)
+    assert _general_plan(1, fd.MODE_LEVEL1) == (4, 1)
+    assert _general_plan(8192, fd.MODE_LEVEL1) == (4, 2048)
+    assert _general_plan(65536, fd.MODE_LEVEL1) == (32, 2048)
+    assert _general_plan(200000, fd.MODE_LEVEL1) == (64, 1024)      # 3 125 wanted, 65 536 / 64 resident
+    assert _general_plan(65536, fd.MODE_RLE) == (16, 4096)
+    assert _general_plan(1000000, fd.MODE_RLE) == (64, 15625)
+    assert _general_plan(65536, fd.MODE_LEVEL2) == (16, 2730)       # 43 690 / 16
+    assert _general_plan(100, fd.MODE_LEVEL3) == (4, 25)
+    monkeypatch.setenv("FDH_GEN_LANES", "1")
+    assert _general_plan(70, fd.MODE_LEVEL1) == (1, 70)
+    monkeypatch.setenv("FDH_GEN_LANES", "16")
+    monkeypatch.setenv("FDH_GEN_RESIDENT", "64")
+    assert _general_plan(100, fd.MODE_LEVEL2) == (16, 4)            # ceil(100 / 16) = 7 wanted, 64 / 16 resident
+    from fdeflate_amd import _lib
+    assert "fdh_debug_general_plan" not in _lib.SIGNATURES
 
 
 def test_level_entry_point_refuses_levels_not_provided():
