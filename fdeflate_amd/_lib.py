@@ -101,11 +101,24 @@ EXTENSION_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name,
     "fdh_png_expand16_mixed_batch": "int 1 8 1 8 4 4 4 4 4 u64 stream",
     "fdh_png_pack16_batch": "int 1 8 1 8 4 4 u64 u32 u32 stream",
 }.items()}
+# include/fdeflate_hip_png16_encode.h, the calls behind fdeflate_amd.png16_encode (tests/test_abi_png16_encode.py compares).
+PNG16_ENCODE_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
+    "fdh_png_analyse16_mixed_batch": "int 1 8 4 4 4 4 4 4 4 u64 u32 stream",
+    "fdh_png_encode16_plan_one": "u32 host host host u32 u32 u32 host",
+    "fdh_png_encode16_plan_batch": "int 4 4 4 4 4 u32 8 8 8 8 4 u64 stream",
+    "fdh_png_pack16_mixed_batch": "int 1 8 1 8 4 4 4 4 4 u64 stream",
+}.items()}
+# Every table by the header that declares its symbols: signature() and lib() walk this.
+TABLES = {"fdeflate_hip.h": SIGNATURES, "fdeflate_hip_png16.h": EXTENSION_SIGNATURES,
+          "fdeflate_hip_png16_encode.h": PNG16_ENCODE_SIGNATURES}
 
 
 def signature(symbol):
-    """(result, parameters) of a symbol of either table."""
-    return SIGNATURES.get(symbol) or EXTENSION_SIGNATURES[symbol]
+    """(result, parameters) of a symbol of any table."""
+    for table in TABLES.values():
+        if symbol in table:
+            return table[symbol]
+    raise KeyError(symbol)
 
 
 def lib():
@@ -117,10 +130,11 @@ def lib():
             "%s is missing: the HIP extension has not been built (make -C fdeflate_amd/csrc); "
             "fdeflate_amd has no CPU fallback" % SO_PATH)
     L = C.CDLL(SO_PATH)
-    for name, (result, params) in list(SIGNATURES.items()) + list(EXTENSION_SIGNATURES.items()):
-        fn = getattr(L, name)
-        fn.restype = _CTYPES[result]
-        fn.argtypes = [_CTYPES[p] for p in params]
+    for table in TABLES.values():
+        for name, (result, params) in table.items():
+            fn = getattr(L, name)
+            fn.restype = _CTYPES[result]
+            fn.argtypes = [_CTYPES[p] for p in params]
     _lib = L
     return L
 

@@ -257,8 +257,7 @@ _PROTOTYPES = {}   # symbol -> (function, (position, dtypes a tensor may have th
 
 
 def _prototype(symbol):
-    """The entry of _lib.SIGNATURES or _lib.EXTENSION_SIGNATURES for `symbol` as _call wants it, worked out at a
-    symbol's first call."""
+    """The entry of `symbol` in one of _lib.TABLES as _call wants it, worked out at a symbol's first call."""
     import torch
     ints = {1: (torch.uint8, torch.int8), 4: (torch.int32, getattr(torch, "uint32", None)),
             8: (torch.int64, getattr(torch, "uint64", None))}

@@ -391,6 +391,41 @@ int fdh_png_pack16_batch(const uint8_t* rgba16, const uint64_t* rgba16_off, uint
                     colour_type, stream_of(hip_stream)));
 }
 
+// ---- PNG encode: mixed batches of RGBA16 pictures (include/fdeflate_hip_png16_encode.h): png_encode16_mixed.hip, and the
+// plan kernel of png_encode_mixed.hip ----
+// (fdh_png_encode16_plan_one stands beside fdh_png_encode_plan_one below)
+int fdh_png_analyse16_mixed_batch(const uint8_t* rgba16, const uint64_t* rgba16_off, const fdh_png_info* info, const uint32_t* upstream,
+                                  uint32_t* pal, uint32_t* colour, uint32_t* trns_len, uint32_t* summary, uint32_t* png_status, uint64_t n,
+                                  uint32_t max_colours, void* hip_stream) {
+    if (max_colours == 0 || max_colours > 256) return fail(FDH_ERR_INVALID_ARGUMENT, "max_colours must be 1 .. 256");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({rgba16, rgba16_off, info, colour, trns_len, summary, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed RGBA16 analysis kernel launch", fdh_launch_png_analyse16_mixed(rgba16, rgba16_off, info, upstream, pal, colour,
+                    trns_len, summary, png_status, n, max_colours, stream_of(hip_stream)));
+}
+
+int fdh_png_encode16_plan_batch(fdh_png_info* info, const uint32_t* colour, const uint32_t* trns_len, const uint32_t* summary,
+                                const uint32_t* analyse_status, uint32_t allowed, uint64_t* pix_size, uint64_t* types_size, uint64_t* prefix,
+                                uint64_t* file_size, uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (allowed & ~0x5Du) return fail(FDH_ERR_INVALID_ARGUMENT, "allowed may hold the bits of colour types 0, 2, 3, 4 and 6 only");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many records in one call (max 2^31-1)");
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({info}, "null pointer", n, "records")) return rc;
+    return launched("RGBA16 encode plan kernel launch", fdh_launch_png_encode_plan(info, colour, trns_len, summary, analyse_status, allowed,
+                    pix_size, types_size, prefix, file_size, png_status, n, 1, stream_of(hip_stream)));
+}
+
+int fdh_png_pack16_mixed_batch(const uint8_t* rgba16, const uint64_t* rgba16_off, uint8_t* pix, const uint64_t* pix_off,
+                               const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
+                               uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
+    if (n == 0) return FDH_SUCCESS;
+    if (int rc = batch_ok({rgba16, rgba16_off, pix, pix_off, info, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed RGBA16 packing kernel launch", fdh_launch_png_pack16_mixed(rgba16, rgba16_off, pix, pix_off, info, pal, colour,
+                    upstream, png_status, n, stream_of(hip_stream)));
+}
+
 // ---- PNG encode from RGBA8: analysis and packing (png_pack.hip), palette framing (png_file.hip) ----
 int fdh_png_analyse_batch(const uint8_t* rgba, const uint64_t* rgba_off, uint32_t* pal, uint32_t* colour, uint32_t* trns_len,
                           uint32_t* summary, uint32_t* png_status, uint64_t n, uint32_t width, uint32_t max_colours, void* hip_stream) {
@@ -433,20 +468,32 @@ int fdh_png_frame_palette_batch(uint8_t* file, const uint64_t* file_off, const u
 }
 
 // ---- PNG encode: mixed batches (png_encode_mixed.hip; the fused encoder in deflate_ultrafast.hip, the framing in png_file.hip) ----
-uint32_t fdh_png_encode_plan_one(fdh_png_info* rec, const uint32_t* colour_count, const uint32_t* trns_len, uint32_t summary,
-                                 uint32_t analyse_status, uint32_t allowed, uint64_t sizes[4]) {
+// (the plan of one record for RGBA8 pictures and, rgba16, for RGBA16 ones: include/fdeflate_hip_png16_encode.h)
+static uint32_t encode_plan_one(bool rgba16, fdh_png_info* rec, const uint32_t* colour_count, const uint32_t* trns_len, uint32_t summary,
+                                uint32_t analyse_status, uint32_t allowed, uint64_t sizes[4]) {
     uint64_t s[4] = {0, 0, 0, 0};
     uint32_t st = FDH_PNG_STATUS_SKIPPED;
     if (rec) {
         const bool dimension = fdh::png_dimension_record(rec->status, rec->width, rec->height, rec->bit_depth, rec->colour_type, rec->interlace);
         const bool have_colour = colour_count && trns_len;
         uint32_t depth = rec->bit_depth, colour = rec->colour_type;
-        st = fdh::png_encode_plan(rec->status, rec->width, rec->height, depth, colour, rec->interlace, have_colour, have_colour ? *colour_count : 0u,
-                                  have_colour ? *trns_len : 0u, summary, analyse_status, allowed, s[0], s[1], s[2], s[3]);
+        const auto plan = rgba16 ? fdh::png_encode16_plan : fdh::png_encode_plan;
+        st = plan(rec->status, rec->width, rec->height, depth, colour, rec->interlace, have_colour, have_colour ? *colour_count : 0u,
+                  have_colour ? *trns_len : 0u, summary, analyse_status, allowed, s[0], s[1], s[2], s[3]);
         if (st == FDH_PNG_STATUS_OK && dimension) rec->bit_depth = (uint8_t)depth, rec->colour_type = (uint8_t)colour;
     }
     if (sizes) std::copy(s, s + 4, sizes);
     return st;
+}
+
+uint32_t fdh_png_encode_plan_one(fdh_png_info* rec, const uint32_t* colour_count, const uint32_t* trns_len, uint32_t summary,
+                                 uint32_t analyse_status, uint32_t allowed, uint64_t sizes[4]) {
+    return encode_plan_one(false, rec, colour_count, trns_len, summary, analyse_status, allowed, sizes);
+}
+
+uint32_t fdh_png_encode16_plan_one(fdh_png_info* rec, const uint32_t* colour_count, const uint32_t* trns_len, uint32_t summary,
+                                   uint32_t analyse_status, uint32_t allowed, uint64_t sizes[4]) {
+    return encode_plan_one(true, rec, colour_count, trns_len, summary, analyse_status, allowed, sizes);
 }
 
 int fdh_png_encode_plan_batch(fdh_png_info* info, const uint32_t* colour, const uint32_t* trns_len, const uint32_t* summary,
@@ -456,7 +503,7 @@ int fdh_png_encode_plan_batch(fdh_png_info* info, const uint32_t* colour, const 
     if (n == 0) return FDH_SUCCESS;
     if (int rc = batch_ok({info}, "null pointer", n, "records")) return rc;
     return launched("PNG encode plan kernel launch", fdh_launch_png_encode_plan(info, colour, trns_len, summary, analyse_status, allowed,
-                    pix_size, types_size, prefix, file_size, png_status, n, stream_of(hip_stream)));
+                    pix_size, types_size, prefix, file_size, png_status, n, 0, stream_of(hip_stream)));
 }
 
 int fdh_png_analyse_mixed_batch(const uint8_t* rgba, const uint64_t* rgba_off, const fdh_png_info* info, const uint32_t* upstream,

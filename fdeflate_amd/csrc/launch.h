@@ -11,6 +11,7 @@
 
 #include "../../include/fdeflate_hip.h"
 #include "../../include/fdeflate_hip_png16.h"
+#include "../../include/fdeflate_hip_png16_encode.h"
 
 namespace fdh { struct SegArgs; }
 int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);  // inflate_seg3.hip, for inflate.hip
@@ -95,10 +96,10 @@ int fdh_launch_png_unfilter_mixed(uint8_t* filt, const uint64_t* filt_off, uint8
 int fdh_launch_png_expand_mixed(const uint8_t* pix, const uint64_t* pix_off, uint8_t* rgba, const uint64_t* rgba_off,
                                 const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
                                 uint32_t* status, uint64_t n, hipStream_t stream);
-// png_encode_mixed.hip
+// png_encode_mixed.hip (rgba16: the plan of include/fdeflate_hip_png16_encode.h)
 int fdh_launch_png_encode_plan(fdh_png_info* info, const uint32_t* colour, const uint32_t* trns_len, const uint32_t* summary,
                                const uint32_t* analyse_status, uint32_t allowed, uint64_t* pix_size, uint64_t* types_size, uint64_t* prefix,
-                               uint64_t* file_size, uint32_t* png_status, uint64_t n, hipStream_t stream);
+                               uint64_t* file_size, uint32_t* png_status, uint64_t n, int rgba16, hipStream_t stream);
 int fdh_launch_png_analyse_mixed(const uint8_t* rgba, const uint64_t* rgba_off, const fdh_png_info* info, const uint32_t* upstream,
                                  uint32_t* pal, uint32_t* colour, uint32_t* trns_len, uint32_t* summary, uint32_t* status, uint64_t n,
                                  uint32_t max_colours, hipStream_t stream);
@@ -117,6 +118,13 @@ int fdh_launch_png_expand16_mixed(const uint8_t* pix, const uint64_t* pix_off, u
 int fdh_launch_png_pack16(const uint8_t* rgba16, const uint64_t* rgba16_off, uint8_t* pix, const uint64_t* pix_off,
                           const uint32_t* upstream, uint32_t* status, uint64_t n, uint32_t width, uint32_t colour_type,
                           hipStream_t stream);
+// png_encode16_mixed.hip (include/fdeflate_hip_png16_encode.h)
+int fdh_launch_png_analyse16_mixed(const uint8_t* rgba16, const uint64_t* rgba16_off, const fdh_png_info* info, const uint32_t* upstream,
+                                   uint32_t* pal, uint32_t* colour, uint32_t* trns_len, uint32_t* summary, uint32_t* status, uint64_t n,
+                                   uint32_t max_colours, hipStream_t stream);
+int fdh_launch_png_pack16_mixed(const uint8_t* rgba16, const uint64_t* rgba16_off, uint8_t* pix, const uint64_t* pix_off,
+                                const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
+                                uint32_t* status, uint64_t n, hipStream_t stream);
 }
 
 namespace fdh {

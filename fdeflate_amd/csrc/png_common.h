@@ -209,6 +209,41 @@ FDH_PNG_FN uint32_t png_encode_plan(uint32_t status, uint32_t width, uint32_t he
     return kPngOk;
 }
 
+// The encode plan of one RGBA16 image (include/fdeflate_hip_png16_encode.h): png_encode_plan with the summary and
+// analyse_status of fdh_png_analyse16_mixed_batch.  An encodable record keeps its pair, and a dimension record whose
+// summary has bit 2 (every sample is narrow: the picture of the high bytes holds it) is planned as that RGBA8 picture:
+// both are png_encode_plan itself.  A dimension record with bit 2 clear has no palette and no depth below 16:
+//   candidates   grey (0, 16): summary bits 0 and 1; RGB (2, 16): bit 0; grey-alpha (4, 16): bit 1; RGBA (6, 16) always
+//   cost         height * row_bytes: the smallest wins, the lower colour type on equal cost.  The height is every
+//                candidate's, so the row bytes are compared (the product may pass 2^64 at 64 bits per pixel)
+// and analyse_status kPngTooManyColours is what the analysis says of every such picture, not an error.  The sizes, and
+// kPngBadSizes, are png_encode_plan's for the pair that won.
+FDH_PNG_FN uint32_t png_encode16_plan(uint32_t status, uint32_t width, uint32_t height, uint32_t& depth, uint32_t& colour, uint32_t interlace,
+                                      bool have_colour, uint32_t count, uint32_t trns_len, uint32_t summary, uint32_t analyse_status,
+                                      uint32_t allowed, uint64_t& pix, uint64_t& types, uint64_t& prefix, uint64_t& file) {
+    if ((summary & 4u) != 0 || !png_dimension_record(status, width, height, depth, colour, interlace))
+        return png_encode_plan(status, width, height, depth, colour, interlace, have_colour, count, trns_len, summary & 0xFF03u, analyse_status,
+                               allowed, pix, types, prefix, file);
+    pix = types = prefix = file = 0;
+    if (analyse_status != kPngOk && analyse_status != kPngTooManyColours) return analyse_status;
+    if (allowed == 0) allowed = 0x5Du;
+    const bool opaque = (summary & 1u) != 0, grey = (summary & 2u) != 0;
+    const uint32_t cand_colour[4] = {0, 2, 4, 6};
+    const bool cand_ok[4] = {opaque && grey, opaque, grey, true};
+    uint32_t c = 0;
+    uint64_t least = 0;
+    for (int k = 0; k < 4; k++) {
+        if (!cand_ok[k] || !((allowed >> cand_colour[k]) & 1u)) continue;
+        const uint64_t rb = png_row_bytes(width, png_pixel_bits(16, cand_colour[k]));
+        if (least == 0 || rb < least) least = rb, c = cand_colour[k];  // (ascending colour types; a row has bytes)
+    }
+    if (least == 0) return kPngNotRepresentable;
+    uint32_t d = 16;
+    const uint32_t st = png_encode_plan(status, width, height, d, c, interlace, false, 0, 0, 0, kPngOk, 0, pix, types, prefix, file);
+    if (st == kPngOk) depth = d, colour = c;
+    return st;
+}
+
 // ---- values that follow from the specification ----
 static_assert(png_encode_prefix(0, 7, 7) == 41 && png_encode_prefix(3, 1, 0) == 56 && png_encode_prefix(3, 256, 256) == 41 + 12 + 768 + 12 + 256,
               "the exact-palette prefix");

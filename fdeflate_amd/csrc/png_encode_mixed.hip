@@ -23,7 +23,7 @@
 
 namespace fdh {
 
-// ---- fdh_png_encode_plan_batch ----
+// ---- fdh_png_encode_plan_batch, fdh_png_encode16_plan_batch ----
 struct EncodePlanArgs {
     PngInfo* info;                  // in, out: a dimension record gets its pair
     const uint32_t* colour;         // nullable: word 0 of 4 is the palette's count
@@ -36,6 +36,8 @@ struct EncodePlanArgs {
     uint32_t allowed;
 };
 
+// RGBA16: the pictures are RGBA16 and summary / analyse_status fdh_png_analyse16_mixed_batch's (png_encode16_plan)
+template <bool RGBA16>
 __global__ __launch_bounds__(256) void png_encode_plan_kernel(EncodePlanArgs a) {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
@@ -44,10 +46,13 @@ __global__ __launch_bounds__(256) void png_encode_plan_kernel(EncodePlanArgs a) 
     const bool dimension = png_dimension_record(r.status, r.width, r.height, r.bit_depth, r.colour_type, r.interlace);
     uint32_t depth = r.bit_depth, colour = r.colour_type;
     uint64_t s[4];
-    const uint32_t st = png_encode_plan(r.status, r.width, r.height, depth, colour, r.interlace, have_colour, have_colour ? a.colour[4 * i] : 0u,
-                                        have_colour ? a.trns_len[i] : 0u, a.summary ? a.summary[i] : 0u,
-                                        a.analyse_status ? a.analyse_status[i] : dimension ? kPngTooManyColours : kPngOk, a.allowed, s[0], s[1],
-                                        s[2], s[3]);
+    const uint32_t count = have_colour ? a.colour[4 * i] : 0u, trns_len = have_colour ? a.trns_len[i] : 0u;
+    const uint32_t summary = a.summary ? a.summary[i] : 0u;
+    const uint32_t analysed = a.analyse_status ? a.analyse_status[i] : dimension ? kPngTooManyColours : kPngOk;
+    const uint32_t st = RGBA16 ? png_encode16_plan(r.status, r.width, r.height, depth, colour, r.interlace, have_colour, count, trns_len, summary,
+                                                   analysed, a.allowed, s[0], s[1], s[2], s[3])
+                               : png_encode_plan(r.status, r.width, r.height, depth, colour, r.interlace, have_colour, count, trns_len, summary,
+                                                 analysed, a.allowed, s[0], s[1], s[2], s[3]);
     if (st == kPngOk && dimension) {
         a.info[i].bit_depth = (uint8_t)depth;
         a.info[i].colour_type = (uint8_t)colour;
@@ -173,10 +178,13 @@ __global__ __launch_bounds__(kWave) void png_mixed_choose_kernel(MixedChooseArgs
 // ---- launchers ----
 extern "C" int fdh_launch_png_encode_plan(fdh_png_info* info, const uint32_t* colour, const uint32_t* trns_len, const uint32_t* summary,
                                           const uint32_t* analyse_status, uint32_t allowed, uint64_t* pix_size, uint64_t* types_size,
-                                          uint64_t* prefix, uint64_t* file_size, uint32_t* png_status, uint64_t n, hipStream_t stream) {
+                                          uint64_t* prefix, uint64_t* file_size, uint32_t* png_status, uint64_t n, int rgba16,
+                                          hipStream_t stream) {
     if (n == 0) return 0;
     fdh::EncodePlanArgs a{info, colour, trns_len, summary, analyse_status, {pix_size, types_size, prefix, file_size}, png_status, n, allowed};
-    hipLaunchKernelGGL(fdh::png_encode_plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (rgba16) hipLaunchKernelGGL(fdh::png_encode_plan_kernel<true>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(fdh::png_encode_plan_kernel<false>, grid, block, 0, stream, a);
     return (int)hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 // its sorted palette (png_analyse_image), and RGBA8 to the packed scanlines of a depth / colour pair (png_pack_image),
 // the exact inverse of png_expand_body.h, as device functions of one image: png_pack.hip (one geometry per call) and
 // png_encode_mixed.hip (the geometry of each image in its fdh_png_info record) run the same code behind their own
-// checks.  tests/png_pack_model.py is the authority on every value.
+// checks.  tests/png_pack_model.py is the authority on every value.  png_encode16_mixed.hip runs the same two bodies on
+// RGBA16 pictures (include/fdeflate_hip_png16_encode.h): PixelSource below is all that differs.
 //
 // Analysis: one workgroup per image, 1 .. 16 wavefronts.  The distinct pixel words live in an LDS open-addressed table
 // (linear probing, insertion by compare-and-swap); a lane reads four pixels with one 16-byte load and probes only for a
@@ -32,6 +33,55 @@ __device__ __forceinline__ uint32_t colour_hash(uint32_t w, uint32_t bits) { ret
 
 __device__ __forceinline__ uint32_t lds_load(const uint32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
 
+// ---- where the pixel words come from ----
+// Both bodies below work on pixel words R | G << 8 | B << 16 | A << 24 and read them through PixelSource<SPX>, SPX the
+// bytes of a pixel in memory.  4: RGBA8, the word is the pixel.  8: RGBA16 (include/fdeflate_hip_png16_encode.h), two
+// words x = R | G << 16, y = B | A << 16 of samples in the device's byte order: the pixel word is their four high bytes,
+// moved together by one v_perm_b32, and Seen keeps what the high bytes do not show -- which samples are not narrow (the
+// two bytes differ: (w ^ (w >> 8)) & 0x00FF00FF on a word of two samples), R ^ G and G ^ B on all 16 bits, and the AND of
+// the y words (alpha).  Four pixels are one 16-byte load or two.  A body that does not read a field of Seen does not
+// pay for it.
+template <int SPX>
+struct PixelSource;
+
+template <>
+struct PixelSource<4> {
+    struct Seen {};
+    template <int N>
+    static __device__ __forceinline__ void load(const uint8_t* in, uint64_t x, uint32_t (&v)[N], Seen&) {
+        __builtin_memcpy(v, in + 4 * x, 4 * N);
+    }
+};
+
+template <>
+struct PixelSource<8> {
+    struct Seen {
+        uint32_t wide = 0;          // byte 0, 2, 1, 3: the bits in which the two bytes of an R, G, B, A differed
+        uint32_t grey = 0;          // (R ^ G) | (G ^ B), 16 bits
+        uint32_t all = 0xFFFFFFFFu; // AND of B | A << 16
+    };
+    template <int N>
+    static __device__ __forceinline__ void load(const uint8_t* in, uint64_t x, uint32_t (&v)[N], Seen& s) {
+        uint32_t t[2 * N];
+        __builtin_memcpy(t, in + 8 * x, 8 * N);
+#pragma unroll
+        for (int j = 0; j < N; j++) {
+            const uint32_t rg = t[2 * j], ba = t[2 * j + 1];
+            s.wide |= ((rg ^ (rg >> 8)) & 0x00FF00FFu) | ((ba ^ (ba >> 8)) & 0x00FF00FFu) << 8;
+            s.grey |= ((rg ^ (rg >> 16)) | ((rg >> 16) ^ ba)) & 0xFFFFu;
+            s.all &= ba;
+            v[j] = __builtin_amdgcn_perm(ba, rg, 0x07050301u);  // bytes 1 and 3 of rg, then of ba
+        }
+    }
+};
+
+// the pixels in front of the first 16-byte boundary of a run at `at`, handled alone so that the wide loads are aligned:
+// up to three of four bytes, at most one of eight; none where the run is not even aligned to its own pixels
+template <int SPX>
+__device__ __forceinline__ uint64_t pixels_in_front(uintptr_t at) {
+    return (at & (SPX - 1)) ? 0 : ((0 - at) & 15) / SPX;
+}
+
 // ---- fdh_png_analyse_batch ----
 // 256 keys that count, and at most one more per lane that passed the overflow test before the count moved: 1280 of 2048.
 constexpr uint32_t kAnalyseSlotBits = 11, kAnalyseSlots = 1u << kAnalyseSlotBits, kAnalyseMaxThreads = 1024;
@@ -51,19 +101,27 @@ struct PngAnalyseArgs {
 };
 
 enum AnalyseWord { kAwCount, kAwWhite, kAwAnd, kAwGrey, kAwD4, kAwD2, kAwD1, kAwKeys, kAwTrns, kAwWords };
+constexpr uint32_t kAwWide = kAwWords, kAwWords16 = kAwWords + 1;  // RGBA16: one word more, PixelSource<8>::Seen::wide
 
-// Image i of the call; table (kAnalyseSlots words), keys (256) and sh (kAwWords) are the workgroup's LDS.
+// Image i of the call; table (kAnalyseSlots words), keys (256) and sh (kAwWords; kAwWords16 where SPX is 8) are the
+// workgroup's LDS.  SPX = 8 (fdh_png_analyse16_mixed_batch): a.rgba holds RGBA16 pictures; the set, the palette and the
+// depth masks are those of the high bytes, opaque and grey are decided on all 16 bits, the depth is 16 once an R, G or B
+// is not narrow, and a picture with any sample that is not narrow ends as one with too many colours does.
+template <int SPX = 4>
 __device__ __forceinline__ void png_analyse_image(const PngAnalyseArgs& a, uint64_t i, uint32_t* table, uint32_t* keys, uint32_t* sh) {
+    using Src = PixelSource<SPX>;
     const uint32_t tid = threadIdx.x, T = blockDim.x, lane = tid & 63;
     const uint64_t o0 = a.rgba_off[i], bytes = a.rgba_off[i + 1] - o0;
-    if (bytes % ((uint64_t)a.width * 4) != 0) {
+    if (bytes % ((uint64_t)a.width * SPX) != 0) {
         if (tid == 0) a.status[i] = kPngBadSizes;
         return;
     }
     for (uint32_t s = tid; s < kAnalyseSlots; s += T) table[s] = kEmptyKey;
-    if (tid < kAwWords) sh[tid] = tid == kAwAnd ? 0xFFFFFFFFu : 0u;
+    if (tid < (SPX == 8 ? kAwWords16 : kAwWords)) sh[tid] = tid == kAwAnd ? 0xFFFFFFFFu : 0u;
     __syncthreads();
     const uint32_t maxc = a.max_colours;
+    typename Src::Seen seen;
+    bool told = false;  // (SPX 8) this lane has said that it saw a sample that is not narrow
     uint32_t all = 0xFFFFFFFFu, grey = 0, d4 = 0, d2 = 0, d1 = 0;
     bool white = false;
     // every pixel: the AND of the words (alpha), R ^ G and G ^ B, and which bits of R, G, B differ from the bits that a
@@ -82,6 +140,10 @@ __device__ __forceinline__ void png_analyse_image(const PngAnalyseArgs& a, uint6
             return;
         }
         if (lds_load(&sh[kAwCount]) > maxc) return;  // overflow is decided: only the summary goes on
+        if constexpr (SPX == 8) {  // ... and so it is once the workgroup has seen a sample that is not narrow
+            if (seen.wide && !told) atomicOr(&sh[kAwWide], seen.wide), told = true;
+            if (lds_load(&sh[kAwWide])) return;
+        }
         uint32_t h = colour_hash(w, kAnalyseSlotBits);
         for (uint32_t p = 0; p < kAnalyseSlots; p++, h = (h + 1) & (kAnalyseSlots - 1)) {
             uint32_t cur = lds_load(&table[h]);
@@ -96,18 +158,17 @@ __device__ __forceinline__ void png_analyse_image(const PngAnalyseArgs& a, uint6
         }
     };
     const uint8_t* img = a.rgba + o0;
-    uint64_t npix = bytes / 4;
-    {  // up to three pixels alone, so that the wide loads are aligned
-        const uintptr_t at = reinterpret_cast<uintptr_t>(img);
-        uint64_t head = (at & 3) ? 0 : ((0 - at) & 15) >> 2;
+    uint64_t npix = bytes / SPX;
+    {  // up to three pixels alone (one of eight bytes), so that the wide loads are aligned
+        uint64_t head = pixels_in_front<SPX>(reinterpret_cast<uintptr_t>(img));
         if (head > npix) head = npix;
         if (tid < head) {
-            uint32_t w;
-            __builtin_memcpy(&w, img + 4 * tid, 4);
-            note(w);
-            insert(w);
+            uint32_t w[1];
+            Src::load(img, tid, w, seen);
+            note(w[0]);
+            insert(w[0]);
         }
-        img += 4 * head;
+        img += SPX * head;
         npix -= head;
     }
     const uint64_t quads = npix / 4;
@@ -115,7 +176,7 @@ __device__ __forceinline__ void png_analyse_image(const PngAnalyseArgs& a, uint6
         const uint64_t q = base + tid;
         const bool active = q < quads;
         uint32_t v[4] = {0, 0, 0, 0};
-        if (active) __builtin_memcpy(v, img + 16 * q, 16);
+        if (active) Src::load(img, 4 * q, v, seen);
         const uint32_t before = (uint32_t)__shfl_up((int)v[3], 1, 64);  // the last pixel of the lane in front
         if (active) {
 #pragma unroll
@@ -127,10 +188,14 @@ __device__ __forceinline__ void png_analyse_image(const PngAnalyseArgs& a, uint6
         }
     }
     if (tid < npix - 4 * quads) {  // the last one to three pixels
-        uint32_t w;
-        __builtin_memcpy(&w, img + 4 * (4 * quads + tid), 4);
-        note(w);
-        insert(w);
+        uint32_t w[1];
+        Src::load(img, 4 * quads + tid, w, seen);
+        note(w[0]);
+        insert(w[0]);
+    }
+    if constexpr (SPX == 8) {  // alpha and grey on all 16 bits
+        all = seen.all, grey = seen.grey;
+        if (seen.wide) atomicOr(&sh[kAwWide], seen.wide);
     }
     if (all != 0xFFFFFFFFu) atomicAnd(&sh[kAwAnd], all);
     if (grey) atomicOr(&sh[kAwGrey], grey);
@@ -139,10 +204,12 @@ __device__ __forceinline__ void png_analyse_image(const PngAnalyseArgs& a, uint6
     if (d1) atomicOr(&sh[kAwD1], d1);
     __syncthreads();
     const uint32_t count = sh[kAwCount];
-    const bool over = count > maxc;
+    const uint32_t wide = SPX == 8 ? sh[kAwWide] : 0u;
+    const bool over = count > maxc || wide != 0;
     if (tid == 0) {
-        const uint32_t depth = sh[kAwD4] ? 8u : sh[kAwD2] ? 4u : sh[kAwD1] ? 2u : 1u;
-        a.summary[i] = ((sh[kAwAnd] >> 24) == 0xFFu ? 1u : 0u) | (sh[kAwGrey] == 0 ? 2u : 0u) | depth << 8;
+        const uint32_t depth = (wide & 0x00FFFFFFu) ? 16u : sh[kAwD4] ? 8u : sh[kAwD2] ? 4u : sh[kAwD1] ? 2u : 1u;
+        const bool opaque = SPX == 8 ? (sh[kAwAnd] >> 16) == 0xFFFFu : (sh[kAwAnd] >> 24) == 0xFFu;
+        a.summary[i] = (opaque ? 1u : 0u) | (sh[kAwGrey] == 0 ? 2u : 0u) | (SPX == 8 && wide == 0 ? 4u : 0u) | depth << 8;
         a.status[i] = over ? kPngTooManyColours : kPngOk;
     }
     if (over) {  // (not specified; the same words whatever the scheduling was)
@@ -232,8 +299,10 @@ struct PackBytes {
     __device__ __forceinline__ void store(uint8_t* p) const { __builtin_memcpy(p, w, N); }  // any alignment
 };
 
-template <int DEPTH, int COLOUR>
+template <int DEPTH, int COLOUR, int SPX = 4>
 struct Pack {
+    using Src = PixelSource<SPX>;
+    using Seen = typename Src::Seen;
     static constexpr int CH = (int)png_channels(COLOUR);
     static constexpr int BITS = (int)png_pixel_bits(DEPTH, COLOUR);  // per pixel
     static constexpr int PIXEL = BITS >= 8 ? BITS / 8 : 1;           // bytes of one pixel where it has whole ones
@@ -283,21 +352,21 @@ struct Pack {
         }
     }
 
-    // pixels x .. x + 3 of the run at `in`: one 16-byte load, one store of 4 * PIXEL bytes
-    static __device__ __forceinline__ void quad(const uint8_t* in, uint64_t x, uint8_t* out, PackLut& lut, bool& bad) {
+    // pixels x .. x + 3 of the run at `in`: one 16-byte load (two from RGBA16), one store of 4 * PIXEL bytes
+    static __device__ __forceinline__ void quad(const uint8_t* in, uint64_t x, uint8_t* out, PackLut& lut, Seen& seen, bool& bad) {
         uint32_t v[4];
-        __builtin_memcpy(v, in + 4 * x, 16);
+        Src::load(in, x, v, seen);
         PackBytes<4 * PIXEL> o;
 #pragma unroll
         for (int j = 0; j < 4; j++) emit(o, j * PIXEL, v[j], lut, bad);
         o.store(out + x * PIXEL);
     }
 
-    static __device__ __forceinline__ void one(const uint8_t* in, uint64_t x, uint8_t* out, PackLut& lut, bool& bad) {
-        uint32_t w;
-        __builtin_memcpy(&w, in + 4 * x, 4);
+    static __device__ __forceinline__ void one(const uint8_t* in, uint64_t x, uint8_t* out, PackLut& lut, Seen& seen, bool& bad) {
+        uint32_t w[1];
+        Src::load(in, x, w, seen);
         PackBytes<PIXEL> o;
-        emit(o, 0, w, lut, bad);
+        emit(o, 0, w[0], lut, bad);
         o.store(out + x * PIXEL);
     }
 
@@ -305,17 +374,22 @@ struct Pack {
     // most significant first, zeros for pixels behind the run; the bytes go to `out`, the run's first byte.  Every lane
     // of the wavefront comes here together, `active` or not: at depth 1 the odd lane's four bits move to the even lane.
     static __device__ __forceinline__ void narrow(const uint8_t* in, uint64_t npix, uint64_t q, bool active, uint8_t* out, PackLut& lut,
-                                                  bool& bad) {
+                                                  Seen& seen, bool& bad) {
         uint32_t bits = 0, have = 0;
         if (active) {
             const uint64_t x = 4 * q;
             have = npix - x >= 4 ? 4u : (uint32_t)(npix - x);
             uint32_t v[4] = {0, 0, 0, 0};
-            if (have == 4) __builtin_memcpy(v, in + 4 * x, 16);
+            if (have == 4) Src::load(in, x, v, seen);
             else {
 #pragma unroll
-                for (int j = 0; j < 3; j++)  // (constant indices: v stays in registers)
-                    if ((uint32_t)j < have) __builtin_memcpy(&v[j], in + 4 * (x + j), 4);
+                for (int j = 0; j < 3; j++) {  // (constant indices: v stays in registers)
+                    if ((uint32_t)j < have) {
+                        uint32_t w[1];
+                        Src::load(in, x + j, w, seen);
+                        v[j] = w[0];
+                    }
+                }
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -344,15 +418,18 @@ struct Pack {
 
 // Image i of the call at a.width and a.row_bytes, behind the caller's look at upstream: the slots' check, the bands
 // blockIdx.y, blockIdx.y + gridDim.y, ..  pal (256 words) and slot (kPackSlots words where COLOUR is 3) are the
-// workgroup's LDS; only colour type 3 touches them.
-template <int DEPTH, int COLOUR>
+// workgroup's LDS; only colour type 3 touches them.  SPX = 8 (fdh_png_pack16_mixed_batch, the pairs below depth 16):
+// a.rgba holds RGBA16 pictures at even addresses, the picture of the high bytes is packed, and a sample that is not
+// narrow is a pixel without a lossless representation.
+template <int DEPTH, int COLOUR, int SPX = 4>
 __device__ __forceinline__ void png_pack_image(const PngPackArgs& a, uint64_t i, uint32_t lane, uint32_t* pal, uint32_t* slot) {
-    using P = Pack<DEPTH, COLOUR>;
+    using P = Pack<DEPTH, COLOUR, SPX>;
+    static_assert(SPX == 4 || DEPTH <= 8, "depth 16 from RGBA16 is png_pack16_image");
     const bool first = blockIdx.y == 0 && lane == 0;
     const uint64_t s0 = a.rgba_off[i], s1 = a.rgba_off[i + 1], o0 = a.pix_off[i], o1 = a.pix_off[i + 1];
     const uint64_t rb = a.row_bytes, width = a.width;
-    const uint64_t rows = (s1 - s0) / (width * 4);
-    const bool fits = rows * width * 4 == s1 - s0 && o1 - o0 == rows * rb;
+    const uint64_t rows = (s1 - s0) / (width * SPX);
+    const bool fits = rows * width * SPX == s1 - s0 && o1 - o0 == rows * rb && (SPX == 4 || (reinterpret_cast<uintptr_t>(a.rgba + s0) & 1) == 0);
     if (!fits) {
         if (first) a.status[i] = kPngBadSizes;
         return;
@@ -388,30 +465,31 @@ __device__ __forceinline__ void png_pack_image(const PngPackArgs& a, uint64_t i,
     uint8_t* const __restrict__ dst = a.pix + o0;
     const bool flat = (width * P::BITS & 7) == 0;  // no padding bits: a band is one run of pixels
     bool bad = false;
+    typename P::Seen seen;
     for (uint64_t band = blockIdx.y; band < bands; band += gridDim.y) {
         const uint64_t r0 = band * kPackBand, r1 = min(rows, r0 + kPackBand);
         if constexpr (P::BITS >= 8) {  // (always flat)
-            const uint8_t* in = img + r0 * width * 4;
+            const uint8_t* in = img + r0 * width * SPX;
             uint8_t* out = dst + r0 * rb;
             uint64_t npix = (r1 - r0) * width;
-            const uintptr_t at = reinterpret_cast<uintptr_t>(in);  // up to three pixels alone: the wide loads are aligned
-            uint64_t head = (at & 3) ? 0 : ((0 - at) & 15) >> 2;
+            uint64_t head = pixels_in_front<SPX>(reinterpret_cast<uintptr_t>(in));  // alone: the wide loads are aligned
             if (head > npix) head = npix;
-            if (lane < head) P::one(in, lane, out, lut, bad);
-            in += head * 4;
+            if (lane < head) P::one(in, lane, out, lut, seen, bad);
+            in += head * SPX;
             out += head * P::PIXEL;
             npix -= head;
             const uint64_t quads = (npix + 3) / 4;
 #pragma unroll 2
             for (uint64_t qx = lane; qx < quads; qx += kWave) {
-                if (npix - 4 * qx >= 4) P::quad(in, 4 * qx, out, lut, bad);
+                if (npix - 4 * qx >= 4) P::quad(in, 4 * qx, out, lut, seen, bad);
                 else
-                    for (uint64_t p = 4 * qx; p < npix; p++) P::one(in, p, out, lut, bad);
+                    for (uint64_t p = 4 * qx; p < npix; p++) P::one(in, p, out, lut, seen, bad);
             }
         } else if (flat) {
-            const uint8_t* in = img + r0 * width * 4;
+            const uint8_t* in = img + r0 * width * SPX;
             const uint64_t npix = (r1 - r0) * width, quads = (npix + 3) / 4;
-            for (uint64_t base = 0; base < quads; base += kWave) P::narrow(in, npix, base + lane, base + lane < quads, dst + r0 * rb, lut, bad);
+            for (uint64_t base = 0; base < quads; base += kWave)
+                P::narrow(in, npix, base + lane, base + lane < quads, dst + r0 * rb, lut, seen, bad);
         } else {
             // rows with padding bits, row by row; at depth 1 a row takes an even number of lanes, so that the two
             // halves of a byte sit in an even lane and the odd one behind it
@@ -419,7 +497,7 @@ __device__ __forceinline__ void png_pack_image(const PngPackArgs& a, uint64_t i,
             if (span >= kWave) {
                 for (uint64_t r = r0; r < r1; r++)
                     for (uint64_t base = 0; base < qpr; base += kWave)
-                        P::narrow(img + r * width * 4, width, base + lane, base + lane < qpr, dst + r * rb, lut, bad);
+                        P::narrow(img + r * width * SPX, width, base + lane, base + lane < qpr, dst + r * rb, lut, seen, bad);
             } else {
                 const uint32_t s32 = (uint32_t)span, per = kWave / s32;  // rows per step
                 const uint32_t lr = lane / s32, lq = lane - lr * s32;
@@ -427,11 +505,12 @@ __device__ __forceinline__ void png_pack_image(const PngPackArgs& a, uint64_t i,
                     const uint64_t r = rr + lr;
                     const bool active = lr < per && r < r1 && lq < qpr;
                     const uint64_t ra = active ? r : r0;  // (a row that exists: nothing of it is touched)
-                    P::narrow(img + ra * width * 4, width, lq, active, dst + ra * rb, lut, bad);
+                    P::narrow(img + ra * width * SPX, width, lq, active, dst + ra * rb, lut, seen, bad);
                 }
             }
         }
     }
+    if constexpr (SPX == 8) bad = bad || seen.wide != 0;
     if (__any(bad) && lane == 0) atomicOr(&a.status[i], kPngNotRepresentable);
 }
 
