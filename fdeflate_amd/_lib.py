@@ -112,10 +112,20 @@ PNG16_ENCODE_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for na
 TABLES = {"fdeflate_hip.h": SIGNATURES, "fdeflate_hip_png16.h": EXTENSION_SIGNATURES,
           "fdeflate_hip_png16_encode.h": PNG16_ENCODE_SIGNATURES}
 
+# include/fdeflate_hip_levels.h, the calls behind fdeflate_amd.levels (tests/test_abi_levels.py compares).  Not a key of
+# TABLES: a merged test (tests/test_abi_png16_encode.py) pins that dict at exactly the three headers above, so this
+# table stands beside it and signature() and lib() walk _ALL_TABLES.
+LEVELS_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
+    "fdh_deflate_level_batch": "int 1 8 1 8 4 u64 u32 stream",
+    "fdh_compress_to_vec_level": "int host size u32 host host",
+    "fdh_debug_level_plan": "int u64 int u32 host",
+}.items()}
+_ALL_TABLES = (*TABLES.values(), LEVELS_SIGNATURES)
+
 
 def signature(symbol):
     """(result, parameters) of a symbol of any table."""
-    for table in TABLES.values():
+    for table in _ALL_TABLES:
         if symbol in table:
             return table[symbol]
     raise KeyError(symbol)
@@ -130,7 +140,7 @@ def lib():
             "%s is missing: the HIP extension has not been built (make -C fdeflate_amd/csrc); "
             "fdeflate_amd has no CPU fallback" % SO_PATH)
     L = C.CDLL(SO_PATH)
-    for table in TABLES.values():
+    for table in _ALL_TABLES:
         for name, (result, params) in table.items():
             fn = getattr(L, name)
             fn.restype = _CTYPES[result]

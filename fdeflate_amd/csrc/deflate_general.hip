@@ -598,6 +598,12 @@ __global__ __launch_bounds__(kWave) void deflate_parse_kernel(GParseArgs a) {
     }
 }
 
+}  // namespace fdh
+
+#include "deflate_lazy.h"  // levels 4-9: GLazyParser and deflate_lazy_parse_kernel, over the pieces above
+
+namespace fdh {
+
 // ============================ kernel 2: the block writer, one stream per wavefront ============================
 
 constexpr uint32_t kGChunk = 1024;  // positions per refill of the marks
@@ -1472,6 +1478,7 @@ using fdh::GenMode;
 
 static_assert(fdh::kGenModes[FDH_MODE_LEVEL1 - 1].table_bytes == fdh::kGHashSize * 4 &&
               fdh::kGenModes[FDH_MODE_LEVEL2 - 1].table_bytes == (fdh::kGHashSize + fdh::kGWindow) * 4, "launch.h's table sizes");
+static_assert(fdh::kLazyMode.table_bytes == (2 * fdh::kGHashSize + fdh::kGWindow) * 4, "launch.h's table sizes");
 
 // The parser runs one stream per lane and is bound by the latency of dependent loads: what helps is wavefronts in
 // flight.  A batch that does not fill the device with full wavefronts is given fewer lanes per wavefront and more
@@ -1485,7 +1492,8 @@ static_assert(fdh::kGenModes[FDH_MODE_LEVEL1 - 1].table_bytes == fdh::kGHashSize
 // The chain parsers (211 VGPRs) have 8 wavefronts per CU resident like level 1, but are asked for twice as many, i.e.
 // half as many lanes each: 65 536 streams as 16 lanes x 2 730 wavefronts ran 42.9 / 499.7 ms at levels 2 / 3, as 32
 // lanes x 1 365 -- all that 16 GiB of tables allow at that width -- 48.3 / 562.6 ms.
-// FDH_GEN_LANES (1..64) sets the lanes, FDH_GEN_RESIDENT (64..2^20; levels 2 and 3 keep the 16 GiB) the streams in flight.
+// Levels 4-9 (deflate_lazy.h) follow the chain parsers' rule with 640 KiB of tables per stream: 26 214 resident.
+// FDH_GEN_LANES (1..64) sets the lanes, FDH_GEN_RESIDENT (64..2^20; levels 2 and above keep the 16 GiB) the streams in flight.
 struct GenPlan {
     unsigned lanes, waves;  // streams per wavefront of the parser, wavefronts
 };
@@ -1543,9 +1551,19 @@ extern "C" int fdh_debug_general_plan(uint64_t n, int cus, uint32_t mode, uint32
     return 0;
 }
 
-extern "C" int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                                          uint32_t* out_len, uint64_t n, uint32_t mode, uint64_t total_in, hipStream_t stream) {
-    const GenMode* m = fdh::gen_mode(mode);
+// what general_plan gives a lazy level, 4 .. 9 (include/fdeflate_hip_levels.h)
+extern "C" int fdh_debug_level_plan(uint64_t n, int cus, uint32_t level, uint32_t* out) {
+    if (!fdh::lazy_params(level) || !out || n == 0) return -1;
+    const GenPlan p = general_plan(n, cus, fdh::kLazyMode);
+    out[0] = p.lanes;
+    out[1] = p.waves;
+    return 0;
+}
+
+// Both launchers: the parser of the mode `m` -- with `lazy`, the lazy parser of kLazyMode with these parameters -- then
+// the block writer.
+static int launch_encoder(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint64_t n,
+                          const GenMode* m, const fdh::LazyParams* lazy, uint64_t total_in, hipStream_t stream) {
     if (n == 0) return 0;
     if (!m) return -1;
     int dev = 0, cus = 0;
@@ -1578,7 +1596,9 @@ extern "C" int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_
     fdh::GParseArgs p{in, in_off, n, static_cast<uint32_t*>(w.hash), static_cast<fdh::GMatchRec*>(w.matches),
                       static_cast<fdh::GBlockRec*>(w.blocks), nblocks, plan.lanes};
     const dim3 grid(plan.waves), block(fdh::kWave);
-    if (m->rle)
+    if (lazy)
+        hipLaunchKernelGGL(fdh::deflate_lazy_parse_kernel, grid, block, 0, stream, p, *lazy);
+    else if (m->rle)
         hipLaunchKernelGGL(fdh::deflate_parse_kernel<true>, grid, block, 0, stream, p);
     else if (m->chain == 2)
         hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 2>), grid, block, 0, stream, p);
@@ -1592,4 +1612,15 @@ extern "C" int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_
     // the workspace is per device, not per stream: calls are serialised by finishing this one
     if (e = hipStreamSynchronize(stream); e != hipSuccess) return (int)failed(e, "hipStreamSynchronize(stream)");
     return 0;
+}
+
+extern "C" int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
+                                          uint32_t* out_len, uint64_t n, uint32_t mode, uint64_t total_in, hipStream_t stream) {
+    return launch_encoder(in, in_off, out, out_off, out_len, n, fdh::gen_mode(mode), nullptr, total_in, stream);
+}
+
+extern "C" int fdh_launch_deflate_level(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
+                                        uint32_t* out_len, uint64_t n, uint32_t level, uint64_t total_in, hipStream_t stream) {
+    const fdh::LazyParams* lazy = fdh::lazy_params(level);
+    return launch_encoder(in, in_off, out, out_off, out_len, n, lazy ? &fdh::kLazyMode : nullptr, lazy, total_in, stream);
 }

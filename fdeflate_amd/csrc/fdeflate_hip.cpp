@@ -554,12 +554,14 @@ int fdh_png_frame_mixed_batch(uint8_t* file, const uint64_t* file_off, const uin
 
 uint64_t fdh_compress_bound(uint64_t len) { return len + len / 2 + 1024; }
 
-int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                              uint32_t* out_len, uint64_t n, uint32_t mode, void* hip_stream) {
+// fdh_deflate_general_batch (`lazy_level` 0: the FDH_MODE_* `mode`) and the lazy levels of fdh_deflate_level_batch
+// (`lazy_level` 4 .. 9, include/fdeflate_hip_levels.h): one contract, one body
+static int general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint64_t n,
+                         uint32_t mode, uint32_t lazy_level, void* hip_stream) {
     if (n == 0) return FDH_SUCCESS;
     if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
     if (!out) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");  // (`in` may be null for a batch of empty inputs: below)
-    if (!fdh::gen_mode(mode)) return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
+    if (!lazy_level && !fdh::gen_mode(mode)) return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call");
     if (!have_device()) return no_device();
     hipStream_t stream = stream_of(hip_stream);
@@ -576,8 +578,29 @@ int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t
     // an empty input has a defined encoding (78 01 03 00 00 00 00 01), and a zero-element buffer has no address
     if (!in && total_in != 0) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");
     // the launcher (deflate_general.hip) plans the launch, keeps the workspace and has left the text of a failure
-    const int rc = fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, mode, total_in, stream);
+    const int rc = lazy_level ? fdh_launch_deflate_level(in, in_off, out, out_off, out_len, n, lazy_level, total_in, stream)
+                              : fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, mode, total_in, stream);
     return rc == 0 ? FDH_SUCCESS : hip_code(static_cast<hipError_t>(rc));
+}
+
+int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
+                              uint32_t* out_len, uint64_t n, uint32_t mode, void* hip_stream) {
+    return general_batch(in, in_off, out, out_off, out_len, n, mode, 0, hip_stream);
+}
+
+// include/fdeflate_hip_levels.h: levels 0-3 are the calls above, 4-9 the lazy parser
+static const uint32_t kLevelModes[] = {0, FDH_MODE_LEVEL1, FDH_MODE_LEVEL2, FDH_MODE_LEVEL3};
+static int bad_level() { return fail(FDH_ERR_INVALID_ARGUMENT, "compression level above 9: levels 0 .. 9 exist"); }
+
+int fdh_deflate_level_batch(const uint8_t* raw, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                            uint64_t n, uint32_t level, void* hip_stream) {
+    if (level > 9) return bad_level();
+    if (n == 0) return FDH_SUCCESS;
+    if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call");
+    if (level == 0) return fdh_deflate_stored_batch(raw, in_off, out, out_off, out_len, n, hip_stream);
+    return level <= 3 ? general_batch(raw, in_off, out, out_off, out_len, n, kLevelModes[level], 0, hip_stream)
+                      : general_batch(raw, in_off, out, out_off, out_len, n, 0, level, hip_stream);
 }
 
 // ---- single-buffer conveniences (host memory) --------------------------------------------
@@ -657,8 +680,8 @@ int fdh_decompress_to_vec(const uint8_t* input, size_t input_len, uint8_t** outp
 
 // which encoder a host call runs: the ultra-fast one, the stored one, or the general one in an FDH_MODE_*
 struct Encoder {
-    enum Type { kUltraFast, kStored, kGeneral } type;
-    uint32_t mode = 0;
+    enum Type { kUltraFast, kStored, kGeneral, kLazy } type;
+    uint32_t mode = 0;  // kLazy: the level, 4 .. 9 (include/fdeflate_hip_levels.h)
 };
 
 static int compress_one(Encoder enc, const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
@@ -679,6 +702,7 @@ static int compress_one(Encoder enc, const uint8_t* input, size_t input_len, uin
     uint32_t* res = reinterpret_cast<uint32_t*>(m + 4);
     int rc = enc.type == Encoder::kStored      ? fdh_deflate_stored_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
              : enc.type == Encoder::kUltraFast ? fdh_deflate_ultrafast_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
+             : enc.type == Encoder::kLazy      ? fdh_deflate_level_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, enc.mode, nullptr)
                                                : fdh_deflate_general_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, enc.mode, nullptr);
     if (rc != FDH_SUCCESS) return rc;
     HIP_TRY(hipDeviceSynchronize());
@@ -720,8 +744,15 @@ int fdh_compress_to_vec_with_level(const uint8_t* input, size_t input_len, uint3
     static const Encoder kLevels[] = {{Encoder::kStored}, {Encoder::kGeneral, FDH_MODE_LEVEL1}, {Encoder::kGeneral, FDH_MODE_LEVEL2},
                                       {Encoder::kGeneral, FDH_MODE_LEVEL3}};
     if (level > 3)
-        return fail(FDH_ERR_INVALID_ARGUMENT, "compression level not provided: levels 0, 1, 2 and 3 are (4-9, the lazy parser, are not)");
+        return fail(FDH_ERR_INVALID_ARGUMENT, "compression level not provided by this call: levels 0, 1, 2 and 3 are (4-9, the lazy parser: "
+                                              "fdh_compress_to_vec_level of fdeflate_hip_levels.h)");
     return compress_one(kLevels[level], input, input_len, output, output_len);
+}
+
+int fdh_compress_to_vec_level(const uint8_t* input, size_t input_len, uint32_t level, uint8_t** output, size_t* output_len) {
+    if (level > 9) return bad_level();
+    if (level <= 3) return fdh_compress_to_vec_with_level(input, input_len, level, output, output_len);
+    return compress_one({Encoder::kLazy, level}, input, input_len, output, output_len);
 }
 
 void fdh_free(void* p) { std::free(p); }

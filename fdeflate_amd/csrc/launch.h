@@ -12,6 +12,7 @@
 #include "../../include/fdeflate_hip.h"
 #include "../../include/fdeflate_hip_png16.h"
 #include "../../include/fdeflate_hip_png16_encode.h"
+#include "../../include/fdeflate_hip_levels.h"
 
 namespace fdh { struct SegArgs; }
 int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);  // inflate_seg3.hip, for inflate.hip
@@ -41,6 +42,9 @@ int fdh_launch_png_filter_deflate_ultrafast_mixed(const uint8_t* pix, const uint
 // workspace, and returns when both kernels have finished; on failure fdh_last_error's text names the step that failed.
 int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
                                uint64_t n, uint32_t mode, uint64_t total_in, hipStream_t stream);
+// the same for a lazy level, 4 .. 9 (include/fdeflate_hip_levels.h): the parser kernel of deflate_lazy.h, the same block writer
+int fdh_launch_deflate_level(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
+                             uint64_t n, uint32_t level, uint64_t total_in, hipStream_t stream);
 // png_filter.hip
 int fdh_launch_png_unfilter(const uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, uint32_t* status,
                             const uint32_t* gate, const uint32_t* gate_len, uint64_t n, uint32_t row_bytes, uint32_t bpp,
@@ -138,7 +142,7 @@ inline int env_int(const char* name, int fallback) {
 // The general encoder's modes, by FDH_MODE_* (gen_mode: nullptr for any other number).
 struct GenMode {
     bool rle;               // RleParser: runs only, no match finder and no tables
-    int chain;              // 0: HashTableMatchFinder; 2 / 3: the level whose HashChainMatchFinder the parser uses
+    int chain;              // 0: HashTableMatchFinder; 2 / 3: the level whose HashChainMatchFinder the parser uses; 4: kLazyMode
     uint64_t table_bytes;   // per resident stream: a 64 Ki-entry table, at levels 2 and 3 also a 32 Ki-entry link ring
     unsigned waves_per_cu;  // the parser's wavefronts wanted per CU before a wavefront is given more streams
     uint64_t max_resident;  // streams in flight: 16 GiB of tables at the most
@@ -150,6 +154,20 @@ constexpr GenMode gen_mode_of(bool rle, int chain) {
 constexpr GenMode kGenModes[] = {gen_mode_of(false, 0), gen_mode_of(true, 0), gen_mode_of(false, 2), gen_mode_of(false, 3)};
 static_assert(FDH_MODE_LEVEL1 == 1 && FDH_MODE_RLE == 2 && FDH_MODE_LEVEL2 == 3 && FDH_MODE_LEVEL3 == 4, "kGenModes' order");
 inline const GenMode* gen_mode(uint32_t mode) { return mode >= 1 && mode <= 4 ? &kGenModes[mode - 1] : nullptr; }
+
+// Levels 4-9 (include/fdeflate_hip_levels.h) are no FDH_MODE_*: a table beside kGenModes.  One launch class -- the
+// HybridMatchFinder's two 64 Ki-entry tables and its 32 Ki-entry link ring, 640 KiB per resident stream, 26 214 of them
+// under the 16 GiB; wavefronts wanted as for the chain parsers -- and the parameters of the level, which the parser
+// kernel takes as arguments (compress/mod.rs:80-87: LazyParser::new(skip_ahead_shift, max_lazy,
+// HybridMatchFinder::new(min_match, search_depth, nice_length)); `7.. =>` is one set).
+constexpr uint64_t kLazyTableBytes = (2 * 65536u + 32768u) * 4;
+constexpr GenMode kLazyMode = {false, 4 /* neither chain level: the hybrid finder */, kLazyTableBytes, 16u, (16ull << 30) / kLazyTableBytes};
+static_assert(kLazyMode.max_resident == 26214, "16 GiB / 640 KiB");
+struct LazyParams {
+    uint32_t shift, max_lazy, min_match, depth, nice;
+};
+constexpr LazyParams kLazyParams[] = {{9, 12, 5, 16, 32}, {9, 16, 5, 64, 64}, {9, 16, 4, 128, 128}, {12, 256, 4, 256, 258}};
+inline const LazyParams* lazy_params(uint32_t level) { return level >= 4 && level <= 9 ? &kLazyParams[level < 7 ? level - 4 : 3] : nullptr; }
 
 // Wavefronts per range / threads per file in the kernels of png_file.hip and png_mixed.hip that serve one file per
 // workgroup: a batch that fills the device by its count alone gets one wavefront per item.

@@ -191,7 +191,8 @@ uint64_t fdh_stored_size(uint64_t len);
  *   FDH_MODE_LEVEL3  `compress_to_vec_with_level(input, 3)` (src/compress/mod.rs:79: GreedyParser,
  *                    skip_ahead_shift 6, HashChainMatchFinder::<false>::new(6, 16, 32), 4-byte
  *                    match_length src/compress/matchfinder/mod.rs:51-110)
- * Levels 4-9 (LazyParser + HybridMatchFinder, src/compress/mod.rs:80-99) are not provided.  Levels 2
+ * Levels 4-9 (LazyParser + HybridMatchFinder, src/compress/mod.rs:80-99) are not provided by this call or by
+ * fdh_compress_to_vec_with_level: the extension fdeflate_hip_levels.h has them (fdh_deflate_level_batch).  Levels 2
  * and 3 are pinned by tests/level_model.py, a restatement that is itself pinned against the oracle
  * at level 1 and RLE; the oracle has no chain finder.
  * Same argument convention as fdh_deflate_ultrafast_batch; slots of at least fdh_compress_bound(len_i)
