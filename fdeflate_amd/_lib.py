@@ -120,7 +120,14 @@ LEVELS_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, si
     "fdh_compress_to_vec_level": "int host size u32 host host",
     "fdh_debug_level_plan": "int u64 int u32 host",
 }.items()}
-_ALL_TABLES = (*TABLES.values(), LEVELS_SIGNATURES)
+# include/fdeflate_hip_png_levels.h, the calls behind fdeflate_amd.png_levels (tests/test_abi_png_levels.py compares):
+# beside TABLES for the same reason.
+PNG_LEVELS_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
+    "fdh_png_filter_mixed_batch": "int 1 8 1 8 1 8 4 4 u32 4 u64 stream",
+    "fdh_png_level_bound": "u64 u64 u32",
+    "fdh_png_level_file_bound": "u64 u64 u64 u32 u64",
+}.items()}
+_ALL_TABLES = (*TABLES.values(), LEVELS_SIGNATURES, PNG_LEVELS_SIGNATURES)
 
 
 def signature(symbol):

@@ -1033,6 +1033,45 @@ def png_frame_mixed_batch(file, file_off, idat_len, info, pal=None, colour=None,
     return file_len, png_status
 
 
+def _png_encode_mixed_front(pictures, pictures_off, width, height, allowed, pairs, file, file_off, analyse, plan, pack, file_size=None):
+    """What the mixed encode pipelines share in front of the filters, for RGBA8 pictures and (png16_encode) RGBA16 ones:
+    the records, `analyse`, `plan`, the three running sums with the ONE read-back of 24 bytes, the file slots (the
+    caller's, checked against prefix + 16, or the plan's) and `pack`.  file_size(pix_size, types_size, prefix, planned) ->
+    the default file slots where they are not the plan's (png_levels).
+    -> the five results of an empty batch, or (pix, offs, total_types, file, file_off, prefix, status, info, pal, colour,
+    trns_len): offs[0] / offs[1] / offs[2] the offsets of the packed scanlines, the filter types and the default file slots."""
+    import torch
+    n = pictures_off.numel() - 1
+    dev = pictures.device
+    if (file is None) != (file_off is None):
+        raise ValueError("file and file_off go together")
+    info = png_encode_records(width, height, pairs)
+    if n == 0:
+        e = torch.empty(0, dtype=torch.int32, device=dev)
+        return (file if file is not None else torch.empty(0, dtype=torch.uint8, device=dev),
+                file_off if file_off is not None else torch.zeros(1, dtype=torch.int64, device=dev), e, e.clone(), info)
+    pal, colour, trns_len, summary, analysed = analyse(pictures, pictures_off, info)
+    pix_size, types_size, prefix, file_sizes, planned = plan(info, colour, trns_len, summary, analysed, allowed)
+    if pairs is not None:   # a forced palette pair with too many colours: the analysis' finding, not the plan's "no count"
+        overflow = (analysed == PNG_TOO_MANY_COLOURS) & (((info[:, 3] >> 8) & 0xFF) == 3) & (planned == PNG_BAD_PLTE)
+        planned = torch.where(overflow, analysed, planned)
+    if file_size is not None:
+        file_sizes = file_size(pix_size, types_size, prefix, planned)
+    offs = torch.zeros((3, n + 1), dtype=torch.int64, device=dev)
+    torch.cumsum(torch.stack((pix_size, types_size, file_sizes)), 1, out=offs[:, 1:])
+    total_pix, total_types, total_file = _read_back(offs[:, n])                    # the one read-back: 24 bytes
+    pix = torch.empty(max(1, total_pix), dtype=torch.uint8, device=dev)
+    if file is None:
+        file = torch.empty(max(1, total_file), dtype=torch.uint8, device=dev)
+        file_off = offs[2]
+    else:
+        slot = file_off[1:] - file_off[:-1]
+        planned = torch.where((planned == 0) & (slot < prefix + PNG_FILE_SUFFIX), torch.full_like(planned, PNG_BAD_SIZES), planned)
+        prefix = torch.minimum(prefix, slot)
+    status = pack(pictures, pictures_off, pix, offs[0], info, pal=pal, colour=colour, upstream=planned)
+    return pix, offs, total_types, file, file_off, prefix, status, info, pal, colour, trns_len
+
+
 def png_encode_mixed_rgba_files_batch(rgba, rgba_off, width, height, allowed=0, pairs=None, file=None, file_off=None):
     """RGBA8 pictures of any size in, PNG files out, each with the smallest of the depth / colour pairs that holds it (or with
     the pair `pairs` names, see png_encode_records), on torch's current stream: png_analyse_mixed_batch,
@@ -1050,33 +1089,12 @@ def png_encode_mixed_rgba_files_batch(rgba, rgba_off, width, height, allowed=0, 
     written to afterwards -- and the last one ends 16 bytes in front of its slot's end.  A caller's slot that is shorter
     than its prefix + 16 is status 2 before anything is written to it."""
     import torch
-    n = rgba_off.numel() - 1
-    dev = rgba.device
-    if (file is None) != (file_off is None):
-        raise ValueError("file and file_off go together")
-    info = png_encode_records(width, height, pairs)
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=dev)
-        return (file if file is not None else torch.empty(0, dtype=torch.uint8, device=dev),
-                file_off if file_off is not None else torch.zeros(1, dtype=torch.int64, device=dev), e, e.clone(), info)
-    pal, colour, trns_len, summary, analysed = png_analyse_mixed_batch(rgba, rgba_off, info)
-    pix_size, types_size, prefix, file_size, planned = png_encode_plan_batch(info, colour, trns_len, summary, analysed, allowed)
-    if pairs is not None:   # a forced palette pair with too many colours: the analysis' finding, not the plan's "no count"
-        overflow = (analysed == PNG_TOO_MANY_COLOURS) & (((info[:, 3] >> 8) & 0xFF) == 3) & (planned == PNG_BAD_PLTE)
-        planned = torch.where(overflow, analysed, planned)
-    offs = torch.zeros((3, n + 1), dtype=torch.int64, device=dev)
-    torch.cumsum(torch.stack((pix_size, types_size, file_size)), 1, out=offs[:, 1:])
-    total_pix, total_types, total_file = _read_back(offs[:, n])                    # the one read-back: 24 bytes
-    pix = torch.empty(max(1, total_pix), dtype=torch.uint8, device=dev)
-    types = torch.empty(max(1, total_types), dtype=torch.uint8, device=dev)
-    if file is None:
-        file = torch.empty(max(1, total_file), dtype=torch.uint8, device=dev)
-        file_off = offs[2]
-    else:
-        slot = file_off[1:] - file_off[:-1]
-        planned = torch.where((planned == 0) & (slot < prefix + PNG_FILE_SUFFIX), torch.full_like(planned, PNG_BAD_SIZES), planned)
-        prefix = torch.minimum(prefix, slot)
-    status = png_pack_mixed_batch(rgba, rgba_off, pix, offs[0], info, pal=pal, colour=colour, upstream=planned)
+    front = _png_encode_mixed_front(rgba, rgba_off, width, height, allowed, pairs, file, file_off, png_analyse_mixed_batch,
+                                    png_encode_plan_batch, png_pack_mixed_batch)
+    if len(front) == 5:
+        return front
+    pix, offs, total_types, file, file_off, prefix, status, info, pal, colour, trns_len = front
+    types = torch.empty(max(1, total_types), dtype=torch.uint8, device=rgba.device)
     status = png_choose_filters_mixed_batch(pix, offs[0], types, offs[1], info, upstream=status)
     enc_off = _enc_off(file_off, prefix)
     idat_len, status = png_filter_deflate_ultrafast_mixed_batch(pix, offs[0], types, offs[1], file, enc_off, info, upstream=status)

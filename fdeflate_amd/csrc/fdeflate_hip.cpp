@@ -603,6 +603,28 @@ int fdh_deflate_level_batch(const uint8_t* raw, const uint64_t* in_off, uint8_t*
                       : general_batch(raw, in_off, out, out_off, out_len, n, 0, level, hip_stream);
 }
 
+// ---- PNG encode at a compression level (include/fdeflate_hip_png_levels.h): png_filter_mixed.hip ----
+int fdh_png_filter_mixed_batch(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off, uint8_t* filt,
+                               const uint64_t* filt_off, const fdh_png_info* info, const uint32_t* upstream, uint32_t flags,
+                               uint32_t* png_status, uint64_t n, void* hip_stream) {
+    if (flags & ~FDH_PNG_FILTER_GIVEN_TYPES) return fail(FDH_ERR_INVALID_ARGUMENT, "unknown flags (bit 0, FDH_PNG_FILTER_GIVEN_TYPES, is the only one)");
+    if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many images in one call (max 2^31-1)");
+    if (n == 0) return FDH_SUCCESS;
+    if (!types != !types_off) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer: types and types_off go together");
+    if ((flags & FDH_PNG_FILTER_GIVEN_TYPES) && !types) return fail(FDH_ERR_INVALID_ARGUMENT, "null pointer: the given types");
+    if (int rc = batch_ok({pix, pix_off, filt, filt_off, info, png_status}, "null pointer", n, "images")) return rc;
+    return launched("mixed filter kernel launch", fdh_launch_png_filter_mixed(pix, pix_off, types, types_off, filt, filt_off, info, upstream,
+                    flags, png_status, n, stream_of(hip_stream)));
+}
+
+uint64_t fdh_png_level_bound(uint64_t len, uint32_t level) {
+    return level > 9 ? 0 : level == 0 ? fdh_stored_size(len) : fdh_compress_bound(len);
+}
+
+uint64_t fdh_png_level_file_bound(uint64_t rows, uint64_t row_bytes, uint32_t level, uint64_t prefix) {
+    return level > 9 ? 0 : prefix + fdh_png_level_bound(rows * (row_bytes + 1), level) + FDH_PNG_FILE_SUFFIX;
+}
+
 // ---- single-buffer conveniences (host memory) --------------------------------------------
 
 // One decode of a host buffer into a device slot of `cap` bytes; the decoded (or partial) bytes

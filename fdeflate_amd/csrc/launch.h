@@ -13,6 +13,7 @@
 #include "../../include/fdeflate_hip_png16.h"
 #include "../../include/fdeflate_hip_png16_encode.h"
 #include "../../include/fdeflate_hip_levels.h"
+#include "../../include/fdeflate_hip_png_levels.h"
 
 namespace fdh { struct SegArgs; }
 int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);  // inflate_seg3.hip, for inflate.hip
@@ -128,6 +129,10 @@ int fdh_launch_png_analyse16_mixed(const uint8_t* rgba16, const uint64_t* rgba16
                                    uint32_t max_colours, hipStream_t stream);
 int fdh_launch_png_pack16_mixed(const uint8_t* rgba16, const uint64_t* rgba16_off, uint8_t* pix, const uint64_t* pix_off,
                                 const fdh_png_info* info, const uint32_t* pal, const uint32_t* colour, const uint32_t* upstream,
+                                uint32_t* status, uint64_t n, hipStream_t stream);
+// png_filter_mixed.hip (include/fdeflate_hip_png_levels.h); clears `status` first
+int fdh_launch_png_filter_mixed(const uint8_t* pix, const uint64_t* pix_off, uint8_t* types, const uint64_t* types_off, uint8_t* filt,
+                                const uint64_t* filt_off, const fdh_png_info* info, const uint32_t* upstream, uint32_t flags,
                                 uint32_t* status, uint64_t n, hipStream_t stream);
 }
 

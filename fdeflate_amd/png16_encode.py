@@ -10,7 +10,7 @@ batched entry point, and no fallback where the library or the GPU is missing.
 import ctypes as C
 
 from . import _lib, api
-from .api import PNG_BAD_PLTE, PNG_BAD_SIZES, PNG_FILE_SUFFIX, PNG_INFO_WORDS, PNG_TOO_MANY_COLOURS, _call, _i32
+from .api import PNG_INFO_WORDS, _call, _i32
 
 __all__ = ["png_analyse16_mixed_batch", "png_encode16_plan_one", "png_encode16_plan_batch", "png_pack16_mixed_batch",
            "png_encode_mixed_rgba16_files_batch"]
@@ -90,33 +90,12 @@ def png_encode_mixed_rgba16_files_batch(rgba16, rgba16_off, width, height, allow
     -> (file, file_off, file_len, png_status, info) as there; png16.png_decode_mixed_files_rgba16_batch gives the pictures
     back."""
     import torch
-    n = rgba16_off.numel() - 1
-    dev = rgba16.device
-    if (file is None) != (file_off is None):
-        raise ValueError("file and file_off go together")
-    info = api.png_encode_records(width, height, pairs)
-    if n == 0:
-        e = torch.empty(0, dtype=torch.int32, device=dev)
-        return (file if file is not None else torch.empty(0, dtype=torch.uint8, device=dev),
-                file_off if file_off is not None else torch.zeros(1, dtype=torch.int64, device=dev), e, e.clone(), info)
-    pal, colour, trns_len, summary, analysed = png_analyse16_mixed_batch(rgba16, rgba16_off, info)
-    pix_size, types_size, prefix, file_size, planned = png_encode16_plan_batch(info, colour, trns_len, summary, analysed, allowed)
-    if pairs is not None:   # a forced palette pair that the analysis refused: its finding, not the plan's "no count"
-        overflow = (analysed == PNG_TOO_MANY_COLOURS) & (((info[:, 3] >> 8) & 0xFF) == 3) & (planned == PNG_BAD_PLTE)
-        planned = torch.where(overflow, analysed, planned)
-    offs = torch.zeros((3, n + 1), dtype=torch.int64, device=dev)
-    torch.cumsum(torch.stack((pix_size, types_size, file_size)), 1, out=offs[:, 1:])
-    total_pix, total_types, total_file = api._read_back(offs[:, n])                # the one read-back: 24 bytes
-    pix = torch.empty(max(1, total_pix), dtype=torch.uint8, device=dev)
-    types = torch.empty(max(1, total_types), dtype=torch.uint8, device=dev)
-    if file is None:
-        file = torch.empty(max(1, total_file), dtype=torch.uint8, device=dev)
-        file_off = offs[2]
-    else:
-        slot = file_off[1:] - file_off[:-1]
-        planned = torch.where((planned == 0) & (slot < prefix + PNG_FILE_SUFFIX), torch.full_like(planned, PNG_BAD_SIZES), planned)
-        prefix = torch.minimum(prefix, slot)
-    status = png_pack16_mixed_batch(rgba16, rgba16_off, pix, offs[0], info, pal=pal, colour=colour, upstream=planned)
+    front = api._png_encode_mixed_front(rgba16, rgba16_off, width, height, allowed, pairs, file, file_off, png_analyse16_mixed_batch,
+                                        png_encode16_plan_batch, png_pack16_mixed_batch)
+    if len(front) == 5:
+        return front
+    pix, offs, total_types, file, file_off, prefix, status, info, pal, colour, trns_len = front
+    types = torch.empty(max(1, total_types), dtype=torch.uint8, device=rgba16.device)
     status = api.png_choose_filters_mixed_batch(pix, offs[0], types, offs[1], info, upstream=status)
     enc_off = api._enc_off(file_off, prefix)
     idat_len, status = api.png_filter_deflate_ultrafast_mixed_batch(pix, offs[0], types, offs[1], file, enc_off, info, upstream=status)
