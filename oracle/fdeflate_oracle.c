@@ -1484,6 +1484,8 @@ typedef struct {
     uint64_t n;
     int ignore_adler32, encode;
     volatile uint64_t *next;
+    void *(*worker)(void *); /* NULL: batch_worker */
+    void *ctx;               /* the worker's own */
 } BatchJob;
 
 static void *batch_worker(void *arg) {
@@ -1516,22 +1518,23 @@ static void *batch_worker(void *arg) {
 static void run_batch(BatchJob *job, int nthreads) {
     volatile uint64_t next = 0;
     job->next = &next;
+    void *(*worker)(void *) = job->worker ? job->worker : batch_worker;
     if (nthreads <= 1) {
-        batch_worker(job);
+        worker(job);
         return;
     }
     pthread_t *th = (pthread_t *)malloc(sizeof(pthread_t) * (size_t)nthreads);
     int started = 0;
     if (th) {
         for (int t = 0; t < nthreads; t++) {
-            if (pthread_create(&th[started], NULL, batch_worker, job) != 0) {
+            if (pthread_create(&th[started], NULL, worker, job) != 0) {
                 break; /* fewer threads than asked for: the ones that exist share the work */
             }
             started++;
         }
     }
     if (started == 0) {
-        batch_worker(job);
+        worker(job);
     }
     for (int t = 0; t < started; t++) {
         pthread_join(th[t], NULL);
@@ -1543,7 +1546,7 @@ void fdo_inflate_batch(const uint8_t *in, const uint64_t *in_off, uint8_t *out,
                        const uint64_t *out_off, uint32_t *out_len, uint32_t *status,
                        uint32_t *adler, uint64_t n, int ignore_adler32, int nthreads) {
     ensure_tables();
-    BatchJob job = {in, in_off, out, out_off, out_len, status, adler, n, ignore_adler32, 0, NULL};
+    BatchJob job = {in, in_off, out, out_off, out_len, status, adler, n, ignore_adler32, 0, NULL, NULL, NULL};
     run_batch(&job, nthreads);
 }
 
@@ -1551,7 +1554,7 @@ void fdo_deflate_ultrafast_batch(const uint8_t *in, const uint64_t *in_off, uint
                                  const uint64_t *out_off, uint32_t *out_len, uint64_t n,
                                  int nthreads) {
     ensure_tables();
-    BatchJob job = {in, in_off, out, out_off, out_len, NULL, NULL, n, 0, 1, NULL};
+    BatchJob job = {in, in_off, out, out_off, out_len, NULL, NULL, n, 0, 1, NULL, NULL, NULL};
     run_batch(&job, nthreads);
 }
 
@@ -1670,12 +1673,15 @@ double fdo_timed_inflate(const uint8_t *in, const uint64_t *in_off, uint8_t *out
 }
 
 /* ========================================================================= */
-/* General encoder, levels 1 ("fast") and RLE                                 */
+/* General encoder, levels 1 ("fast") to 9 and RLE                            */
 /*   Compressor            src/compress/mod.rs:47-217                         */
 /*   GreedyParser          src/compress/parse/greedy.rs:10-92                 */
+/*   LazyParser            src/compress/parse/lazy.rs:9-118                   */
 /*   RleParser             src/compress/parse/rle.rs:5-48                     */
 /*   ParserInner           src/compress/parse/mod.rs:18-181                   */
 /*   HashTableMatchFinder  src/compress/matchfinder/hashtable.rs:5-63         */
+/*   HashChainMatchFinder  src/compress/matchfinder/hashchain.rs:8-125        */
+/*   HybridMatchFinder     src/compress/matchfinder/hybrid.rs:8-176           */
 /*   match_length/rle_match src/compress/matchfinder/mod.rs:42-145            */
 /*   write_block / build_huffman_tree  src/compress/bitstream.rs:41-325       */
 /*   BitWriter             src/compress/bitwriter.rs:3-51                     */
@@ -1684,7 +1690,10 @@ double fdo_timed_inflate(const uint8_t *in, const uint64_t *in_off, uint8_t *out
 /* for these encoders (only round-trip tests, src/decompress.rs:1235-1259, and */
 /* the empty-input bytes 78 01 03 00 00 00 00 01, src/compress/mod.rs:71,      */
 /* 234-238), and it cannot be built here.  Pinned by restatement + the KAT +   */
-/* zlib round trips (tests/test_oracle_golden.py).  Two library behaviours the */
+/* zlib round trips (tests/test_oracle_golden.py), and at levels 2-9 by a      */
+/* second reading of the same Rust, the Python models of tests/, with which    */
+/* this one agrees in bytes and branch counts (tests/test_oracle_levels.py).   */
+/* Two library behaviours the                                                  */
 /* reference inherits from Rust's std are restated as the std documents /      */
 /* implements them: BinaryHeap (rebuild, pop = sift_down_to_bottom + sift_up,  */
 /* PeekMut drop = sift_down) for tie-breaking in build_huffman_tree, and       */
@@ -1893,7 +1902,7 @@ static int g_build_huffman_tree(const uint32_t *freq, size_t n, uint8_t *lengths
         }
     }
     if (max_length > length_limit) {
-        fdo_length_limit_events[length_limit == 7 ? 1 : 0]++;
+        __atomic_fetch_add(&fdo_length_limit_events[length_limit == 7 ? 1 : 0], 1, __ATOMIC_RELAXED); /* batches run on threads */
         uint32_t counts[16] = {0};
         for (size_t i = 0; i < n; i++) {
             counts[lengths[i] < length_limit ? lengths[i] : length_limit]++;
@@ -2159,22 +2168,251 @@ static GMatch g_rle_match(const uint8_t *data, size_t len, size_t last_match, si
     return m;
 }
 
+/* match_length::<false> (matchfinder/mod.rs:51-110): the variant of HashChainMatchFinder<false> (level 3) and of
+ * HybridMatchFinder (levels 4-9).  Four equal bytes are required, the first eight count. */
+static void g_match_length4(uint64_t value, const uint8_t *data, size_t len, size_t anchor, size_t ip, size_t prev_index,
+                            uint16_t *out_len, size_t *out_start) {
+    uint64_t prev = g_load64(data + prev_index); /* :63 */
+    if ((uint32_t)value != (uint32_t)prev) {     /* :72-74 */
+        *out_len = 0;
+        *out_start = ip;
+        return;
+    }
+    uint64_t diff = value ^ prev;
+    size_t length = diff ? (size_t)__builtin_ctzll(diff) / 8 : 8; /* :75, trailing_zeros(0) == 64 */
+    /* :79-83 backwards */
+    while (length < 258 && ip > anchor && prev_index > 0 && data[ip - 1] == data[prev_index - 1]) {
+        length++;
+        ip--;
+        prev_index--;
+    }
+    /* :86-107 forwards, eight at a time and then the remainder; a difference inside a chunk skips the remainder */
+    size_t slice = len - ip - length;
+    if (slice > 258 - length) {
+        slice = 258 - length;
+    }
+    const uint8_t *a = data + ip + length, *b = data + prev_index + length;
+    size_t whole = slice - slice % 8, k = 0;
+    for (; k < whole; k += 8) {
+        uint64_t x = g_load64(a + k), y = g_load64(b + k);
+        if (x != y) {
+            length += (size_t)__builtin_ctzll(x ^ y) / 8;
+            *out_len = (uint16_t)length;
+            *out_start = ip;
+            return;
+        }
+        length += 8;
+    }
+    for (; k < slice && a[k] == b[k]; k++) {
+        length++;
+    }
+    *out_len = (uint16_t)length;
+    *out_start = ip;
+}
+
+/* ---- coverage counters of levels 2-9 (test instrumentation; names as tests/lazy_model.py has them) ---- */
+enum {
+    GC_STEPS2, GC_NICE, GC_EOD, GC_DEPTH, GC_ALIAS, GC_MAXSTEPS, GC_QUARTER, GC_RESCUE_HIT, GC_RESCUE_MISS, GC_RESCUE_ZERO,
+    GC_M0_EMPTY, GC_M0_EARLIER, GC_M0_LONGER, GC_M0_KEPT, GC_M0_INSERTED, GC_M0_CUT, GC_M0_DROPPED, GC_M2_SAME_START,
+    GC_PENDING, GC_RESUMED, GC_BLOCKS, GC_MAX_BLOCK_SYMBOLS, GC_PASS2_BASE,
+    GC_SKIP_NONZERO, GC_SCAN_END_IN_SKIP, GC_RLE_EVENTS,
+    GC_COUNT
+};
+_Static_assert(GC_COUNT == FDO_LEVEL_COUNTERS, "fdeflate_oracle.h names another number of level counters");
+static int gc_is_max(int k) { return k == GC_MAXSTEPS || k == GC_MAX_BLOCK_SYMBOLS || k == GC_PASS2_BASE; }
+
+/* which MatchFinder the parser holds (compress/mod.rs:75-88, :113) */
+enum { G_FINDER_NULL, G_FINDER_TABLE, G_FINDER_CHAIN, G_FINDER_HYBRID };
+
 #define G_MAX_SYMBOLS (16384 + 8)
 typedef struct {
-    int use_hash;         /* 1: HashTableMatchFinder (level 1), 0: NullMatchFinder (RLE) */
+    int finder;           /* G_FINDER_*: Null (RLE), HashTable (level 1), HashChain (2, 3), Hybrid (4-9) */
     uint32_t *hash_table; /* CACHE_SIZE = 1 << 16 entries */
+    uint32_t *links;      /* WINDOW_SIZE = 1 << 15 entries: HashChain and Hybrid */
+    uint32_t *hash4_table; /* CACHE_SIZE entries: Hybrid */
+    uint16_t search_depth, nice_length, min_match;
+    int min_match8; /* HashChainMatchFinder<true> */
+    uint64_t mask, mask4;
     uint8_t skip_ahead_shift;
     GSymbol *symbols;
-    size_t nsym;
+    size_t nsym, sym_cap;
+    int alloc_failed;
     size_t ip, last_match, last_block_end;
     uint32_t last_index;
     GMatch m; /* GreedyParser::m */
+    uint16_t max_lazy;
+    GMatch m0, m1; /* LazyParser::m0, m1 */
+    uint64_t c[GC_COUNT];
 } GParser;
 
-/* HashTableMatchFinder::get_and_insert (hashtable.rs:16-50) / NullMatchFinder */
+/* Vec::push: the lazy loop reaches write_block_if_ready only after a deferral, so a block can hold far more than 16 384
+ * symbols (lazy.rs:95, :98 `continue` past :111) */
+static void g_symbols_room(GParser *ps) {
+    if (ps->nsym + 2 <= ps->sym_cap) {
+        return;
+    }
+    GSymbol *grown = (GSymbol *)realloc(ps->symbols, sizeof(GSymbol) * ps->sym_cap * 2);
+    if (!grown) {
+        ps->alloc_failed = 1;
+        ps->nsym = 0; /* the stream is given up (the caller returns 0); go on writing inside the buffer */
+        return;
+    }
+    ps->symbols = grown;
+    ps->sym_cap *= 2;
+}
+
+/* the walk both chained finders share: hashchain.rs:68-96 and hybrid.rs:75-103 are the same statements.  `best_length`
+ * comes in as the length to beat. */
+static void g_walk_chain(GParser *ps, const uint8_t *data, size_t len, uint32_t base_index, size_t anchor, size_t ip,
+                         uint64_t value, uint32_t offset, uint32_t min_offset, uint16_t n, uint16_t *best_length,
+                         uint32_t *best_offset, size_t *best_start) {
+    uint32_t new_offset = (uint32_t)ip + base_index;
+    uint64_t steps = 0;
+    for (;;) {
+        if (offset < min_offset) {
+            break;
+        }
+        steps++;
+        if (steps >= 2) {
+            ps->c[GC_STEPS2]++;
+        }
+        if (new_offset >= 32768 && offset == new_offset - 32768) {
+            ps->c[GC_ALIAS]++; /* this candidate's link slot is the one the insert just overwrote */
+        }
+        uint16_t length;
+        size_t start;
+        if (ps->min_match8) {
+            g_match_length8(value, data, len, anchor, ip, (size_t)(offset - base_index), &length, &start);
+        } else {
+            g_match_length4(value, data, len, anchor, ip, (size_t)(offset - base_index), &length, &start);
+        }
+        if (length > *best_length) {
+            *best_length = length;
+            *best_offset = offset;
+            *best_start = start;
+        }
+        if (length >= ps->nice_length) {
+            ps->c[GC_NICE]++;
+            break;
+        }
+        if (ip + length == len) {
+            ps->c[GC_EOD]++;
+            break;
+        }
+        n--;
+        if (n == 0) {
+            ps->c[GC_DEPTH]++;
+            break;
+        }
+        offset = ps->links[offset % 32768u];
+    }
+    if (steps > ps->c[GC_MAXSTEPS]) {
+        ps->c[GC_MAXSTEPS] = steps;
+    }
+}
+
+static uint32_t g_min_offset(uint32_t base_index, size_t ip) {
+    uint32_t sub = (uint32_t)ip > 32768 ? (uint32_t)ip - 32768 : 0; /* saturating_sub */
+    uint32_t min_offset = base_index + sub;
+    return min_offset < 1 ? 1 : min_offset;
+}
+
+/* HashChainMatchFinder::get_and_insert (hashchain.rs:40-107) */
+static GMatch g_chain_get_and_insert(GParser *ps, const uint8_t *data, size_t len, uint32_t base_index, size_t anchor,
+                                     size_t ip, uint64_t value) {
+    uint32_t min_offset = g_min_offset(base_index, ip); /* :48 */
+    uint32_t best_offset = 0;
+    uint16_t best_length = (uint16_t)(ps->min_match - 1);
+    size_t best_start = 0;
+    uint32_t hash_index = g_compute_hash(value & ps->mask) % 65536u; /* :59-61 */
+    uint32_t offset = ps->hash_table[hash_index];
+    uint32_t new_offset = (uint32_t)ip + base_index; /* :64-66 */
+    ps->hash_table[hash_index] = new_offset;
+    ps->links[new_offset % 32768u] = offset;
+    g_walk_chain(ps, data, len, base_index, anchor, ip, value, offset, min_offset, ps->search_depth, &best_length,
+                 &best_offset, &best_start);
+    if (best_length >= ps->min_match) { /* :98-104 */
+        GMatch m = {best_length, (uint16_t)(ip - (size_t)(best_offset - base_index)), best_start};
+        return m;
+    }
+    return gm_empty();
+}
+
+/* HybridMatchFinder::lookup (hybrid.rs:40-127); get_and_insert calls it with min_match 4 (:151), get_and_insert_lazy
+ * with the caller's (:138) */
+static GMatch g_hybrid_lookup(GParser *ps, const uint8_t *data, size_t len, uint32_t base_index, size_t anchor, size_t ip,
+                              uint64_t value, uint16_t min_match) {
+    uint32_t min_offset = g_min_offset(base_index, ip); /* :49 */
+    uint32_t best_offset = 0;
+    uint16_t best_length = (uint16_t)(min_match - 1); /* :52: the CALL's min_match */
+    size_t best_start = 0;
+    uint16_t n = ps->search_depth;
+    if (min_match > ps->min_match) { /* :56-58 */
+        n >>= 2;
+        ps->c[GC_QUARTER]++;
+    }
+    uint32_t hash4_index = g_compute_hash(value & ps->mask4) % 65536u; /* :60-62 */
+    uint32_t offset4 = ps->hash4_table[hash4_index];
+    uint32_t hash_index = g_compute_hash(value & ps->mask) % 65536u; /* :64-66 */
+    uint32_t offset = ps->hash_table[hash_index];
+    uint32_t new_offset = (uint32_t)ip + base_index; /* :69-73 */
+    ps->hash_table[hash_index] = new_offset;
+    ps->links[new_offset % 32768u] = offset;
+    ps->hash4_table[hash4_index] = new_offset;
+    g_walk_chain(ps, data, len, base_index, anchor, ip, value, offset, min_offset, n, &best_length, &best_offset,
+                 &best_start);
+    /* :105-116: the walk leaves at `offset < min_offset`, this asks `offset4 > min_offset`; and what the 4-table's
+     * candidate gives REPLACES the walk's best, shorter or not */
+    if (best_length < ps->min_match && offset4 > min_offset) {
+        uint16_t length;
+        size_t start;
+        g_match_length4(value, data, len, anchor, ip, (size_t)(offset4 - base_index), &length, &start);
+        best_length = length;
+        best_offset = offset4;
+        best_start = start;
+        ps->c[length >= min_match ? GC_RESCUE_HIT : GC_RESCUE_MISS]++;
+        if (length == 0) {
+            ps->c[GC_RESCUE_ZERO]++;
+        }
+    }
+    if (best_length >= min_match) { /* :118-124 */
+        GMatch m = {best_length, (uint16_t)(ip - (size_t)(best_offset - base_index)), best_start};
+        return m;
+    }
+    return gm_empty();
+}
+
+/* MatchFinder::insert: hashtable.rs:52-55, hashchain.rs:109-114, hybrid.rs:154-162 */
+static void g_finder_insert(GParser *ps, uint64_t value, uint32_t offset) {
+    switch (ps->finder) {
+    case G_FINDER_TABLE:
+        ps->hash_table[g_compute_hash(value) % 65536u] = offset;
+        break;
+    case G_FINDER_HYBRID:
+        ps->hash4_table[g_compute_hash(value & ps->mask4) % 65536u] = offset;
+        __attribute__((fallthrough)); /* the rest is the chain's insert */
+    case G_FINDER_CHAIN: {
+        uint32_t hash_index = g_compute_hash(value & ps->mask) % 65536u;
+        uint32_t prev_offset = ps->hash_table[hash_index];
+        ps->hash_table[hash_index] = offset;
+        ps->links[offset % 32768u] = prev_offset;
+        break;
+    }
+    default:
+        break;
+    }
+}
+
+/* HashTableMatchFinder::get_and_insert (hashtable.rs:16-50) / NullMatchFinder, or one of the finders above */
 static GMatch g_get_and_insert(GParser *ps, const uint8_t *data, size_t len, uint32_t base_index, size_t anchor,
                                size_t ip, uint64_t value) {
-    if (!ps->use_hash) {
+    if (ps->finder == G_FINDER_CHAIN) {
+        return g_chain_get_and_insert(ps, data, len, base_index, anchor, ip, value);
+    }
+    if (ps->finder == G_FINDER_HYBRID) {
+        return g_hybrid_lookup(ps, data, len, base_index, anchor, ip, value, 4);
+    }
+    if (ps->finder == G_FINDER_NULL) {
         return gm_empty();
     }
     uint32_t sub = (uint32_t)ip > 32768 ? (uint32_t)ip - 32768 : 0;
@@ -2203,6 +2441,7 @@ static GMatch g_get_match(GParser *ps, const uint8_t *data, size_t len, uint32_t
     if ((uint32_t)current == (uint32_t)(current >> 8)) {
         GMatch m = g_rle_match(data, len, ps->last_match, ps->ip);
         ps->ip = gm_end(m) - 3;
+        ps->c[GC_RLE_EVENTS]++;
         return m;
     }
     size_t anchor = fizzle ? ps->ip : ps->last_match;
@@ -2225,7 +2464,14 @@ static GMatch g_advance_to_match(GParser *ps, const uint8_t *data, size_t len, u
         if (m.length != 0) {
             return m;
         }
-        ps->ip += (ps->ip - ps->last_match) >> ps->skip_ahead_shift;
+        size_t skip = (ps->ip - ps->last_match) >> ps->skip_ahead_shift;
+        if (skip > 0) {
+            ps->c[GC_SKIP_NONZERO]++;
+            if (skip >= 2 && ps->ip < max_ip && ps->ip + skip >= max_ip) {
+                ps->c[GC_SCAN_END_IN_SKIP]++;
+            }
+        }
+        ps->ip += skip;
     }
     return gm_empty();
 }
@@ -2233,9 +2479,9 @@ static GMatch g_advance_to_match(GParser *ps, const uint8_t *data, size_t len, u
 /* ParserInner::advance (parse/mod.rs:105-114) */
 static void g_advance(GParser *ps, const uint8_t *data, size_t len, uint32_t base_index, size_t end) {
     size_t stop = end < len - 8 ? end : len - 8;
-    if (ps->use_hash) {
+    if (ps->finder != G_FINDER_NULL) {
         for (size_t j = ps->ip; j < stop; j++) {
-            ps->hash_table[g_compute_hash(g_load64(data + j)) % 65536u] = base_index + (uint32_t)j;
+            g_finder_insert(ps, g_load64(data + j), base_index + (uint32_t)j);
         }
     }
     if (end > ps->ip) {
@@ -2245,6 +2491,7 @@ static void g_advance(GParser *ps, const uint8_t *data, size_t len, uint32_t bas
 
 /* ParserInner::insert_match (parse/mod.rs:117-131) */
 static void g_insert_match(GParser *ps, uint32_t base_index, GMatch m) {
+    g_symbols_room(ps);
     if (m.start > ps->last_match) {
         ps->symbols[ps->nsym].a = base_index + (uint32_t)ps->last_match;
         ps->symbols[ps->nsym].b = base_index + (uint32_t)m.start;
@@ -2260,6 +2507,10 @@ static void g_insert_match(GParser *ps, uint32_t base_index, GMatch m) {
 static void g_write_block_if_ready(GParser *ps, GBitWriter *w, const uint8_t *data, size_t len, uint32_t base_index,
                                    int finish) {
     if (ps->nsym >= 16384) {
+        ps->c[GC_BLOCKS]++;
+        if (ps->nsym > ps->c[GC_MAX_BLOCK_SYMBOLS]) {
+            ps->c[GC_MAX_BLOCK_SYMBOLS] = ps->nsym;
+        }
         int last_block = finish && ps->last_match == len;
         g_write_block(w, data, base_index, ps->symbols, ps->nsym, last_block);
         ps->nsym = 0;
@@ -2283,6 +2534,7 @@ static size_t g_end_compress(GParser *ps, GBitWriter *w, const uint8_t *data, si
             ps->ip = len;
         }
         if (ps->last_match < len) {
+            g_symbols_room(ps);
             ps->symbols[ps->nsym].a = base_index + (uint32_t)ps->last_match;
             ps->symbols[ps->nsym].b = base_index + (uint32_t)len;
             ps->nsym++;
@@ -2302,6 +2554,7 @@ static size_t g_greedy_compress(GParser *ps, GBitWriter *w, const uint8_t *data,
     size_t delta = g_start_compress(ps, base_index, start);
     if (ps->m.length != 0) {
         ps->m.start -= delta;
+        ps->c[GC_RESUMED]++;
     }
     size_t lookahead = finish ? 7 : 258 + 8;
     size_t max_ip = len > lookahead ? len - lookahead : 0;
@@ -2317,6 +2570,7 @@ static size_t g_greedy_compress(GParser *ps, GBitWriter *w, const uint8_t *data,
         if (ps->ip < max_ip) {
             m2 = g_get_match(ps, data, len, base_index, 1);
         } else if (!finish) {
+            ps->c[GC_PENDING]++;
             break;
         }
         if (m2.length == 0 || m2.start > ps->m.start + 1) {
@@ -2353,7 +2607,86 @@ static size_t g_rle_compress(GParser *ps, GBitWriter *w, const uint8_t *data, si
     return g_end_compress(ps, w, data, len, base_index, start, finish);
 }
 
-/* CompressorInner::compress (compress/mod.rs:226-290) for the Fast / Rle variants */
+/* LazyParser::compress (parse/lazy.rs:31-117).  m1 is the match in hand, m2 the one found one byte on, m0 a match that
+ * was displaced by a later, longer one and may still go out in front of it. */
+static size_t g_lazy_compress(GParser *ps, GBitWriter *w, const uint8_t *data, size_t len, uint32_t base_index,
+                              size_t start, int finish) {
+    size_t delta = g_start_compress(ps, base_index, start); /* :39-45 */
+    if (ps->m0.length != 0) {
+        ps->m0.start -= delta;
+    }
+    if (ps->m1.length != 0) {
+        ps->m1.start -= delta;
+        ps->c[GC_RESUMED]++;
+    }
+    size_t lookahead = finish ? 7 : 258 + 8; /* :47-48 */
+    size_t max_ip = len > lookahead ? len - lookahead : 0;
+    for (;;) {
+        if (ps->m1.length == 0) { /* :51-56 */
+            ps->m1 = g_advance_to_match(ps, data, len, base_index, max_ip);
+            if (ps->m1.length == 0) {
+                break;
+            }
+        }
+        GMatch m2 = gm_empty(); /* :61-81 */
+        if (ps->m1.length <= ps->max_lazy) {
+            if (ps->ip < max_ip) {
+                uint64_t value = g_load64(data + ps->ip);
+                m2 = g_hybrid_lookup(ps, data, len, base_index, ps->last_match, ps->ip, value,
+                                     (uint16_t)(ps->m1.length + 1));
+                ps->ip++;
+                if (m2.length <= ps->m1.length) {
+                    m2 = gm_empty();
+                }
+            } else if (!finish) {
+                ps->c[GC_PENDING]++; /* m1 stays in the parser for the next pass */
+                break;
+            }
+        }
+        if (m2.length == 0) { /* :83-95 */
+            g_advance(ps, data, len, base_index, gm_end(ps->m1));
+            if (ps->m0.length != 0) {
+                if (ps->m0.start + 4 <= ps->m1.start) {
+                    uint16_t gap = (uint16_t)(ps->m1.start - ps->m0.start); /* `as u16`, :87 */
+                    ps->c[GC_M0_INSERTED]++;
+                    if (gap < ps->m0.length) {
+                        ps->m0.length = gap;
+                        ps->c[GC_M0_CUT]++;
+                    }
+                    g_insert_match(ps, base_index, ps->m0);
+                } else {
+                    ps->c[GC_M0_DROPPED]++;
+                }
+            }
+            g_insert_match(ps, base_index, ps->m1);
+            ps->m0 = gm_empty();
+            ps->m1 = gm_empty();
+            continue; /* past write_block_if_ready */
+        } else if (m2.start <= ps->m1.start) { /* :96-98 */
+            ps->c[GC_M2_SAME_START]++;
+            ps->m1 = m2;
+            continue;
+        } else { /* :99-109 */
+            if (ps->m0.length == 0) {
+                ps->c[GC_M0_EMPTY]++;
+                ps->m0 = ps->m1;
+            } else if (ps->m1.start < ps->m0.start) {
+                ps->c[GC_M0_EARLIER]++;
+                ps->m0 = ps->m1;
+            } else if (ps->m1.start == ps->m0.start && ps->m1.length > ps->m0.length) {
+                ps->c[GC_M0_LONGER]++;
+                ps->m0 = ps->m1;
+            } else {
+                ps->c[GC_M0_KEPT]++;
+            }
+            ps->m1 = m2;
+        }
+        g_write_block_if_ready(ps, w, data, len, base_index, finish); /* :111-112 */
+    }
+    return g_end_compress(ps, w, data, len, base_index, start, finish); /* :115-116 */
+}
+
+/* CompressorInner::compress (compress/mod.rs:226-290) for the Rle, Fast, MediumFast, Medium and High variants */
 static size_t g_inner_compress(GParser *ps, GBitWriter *w, const uint8_t *data, size_t len, uint32_t base_index,
                                size_t start, int finish) {
     if (finish && len == start) { /* :234-238 */
@@ -2361,16 +2694,73 @@ static size_t g_inner_compress(GParser *ps, GBitWriter *w, const uint8_t *data, 
         gbw_flush(w);
         return 0;
     }
-    return ps->use_hash ? g_greedy_compress(ps, w, data, len, base_index, start, finish)
-                        : g_rle_compress(ps, w, data, len, base_index, start, finish);
+    if (finish) {
+        ps->c[GC_PASS2_BASE] = base_index;
+    }
+    switch (ps->finder) {
+    case G_FINDER_NULL:
+        return g_rle_compress(ps, w, data, len, base_index, start, finish);
+    case G_FINDER_HYBRID:
+        return g_lazy_compress(ps, w, data, len, base_index, start, finish);
+    default:
+        return g_greedy_compress(ps, w, data, len, base_index, start, finish);
+    }
 }
 
-/* compress_to_vec (level 1, compress/mod.rs:294-303) / compress_to_vec_rle (:306-310):
+/* Compressor::new's level table (compress/mod.rs:75-88) and new_rle (:113): the parser's skip_ahead_shift, LazyParser's
+ * max_lazy, and the finder's (min_match, search_depth, nice_length).  Index 0 is RLE; 7 stands for `7..`. */
+typedef struct {
+    uint8_t finder, skip_ahead_shift;
+    uint16_t max_lazy, min_match, search_depth, nice_length;
+} GLevel;
+static const GLevel G_LEVELS[8] = {
+    {G_FINDER_NULL, 5, 0, 0, 0, 0},          /* :113 RleParser::new(5) */
+    {G_FINDER_TABLE, 5, 0, 0, 0, 0},         /* :77 */
+    {G_FINDER_CHAIN, 6, 0, 8, 16, 64},       /* :78 */
+    {G_FINDER_CHAIN, 6, 0, 6, 16, 32},       /* :79 */
+    {G_FINDER_HYBRID, 9, 12, 5, 16, 32},     /* :80 */
+    {G_FINDER_HYBRID, 9, 16, 5, 64, 64},     /* :81 */
+    {G_FINDER_HYBRID, 9, 16, 4, 128, 128},   /* :82 */
+    {G_FINDER_HYBRID, 12, 256, 4, 256, 258}, /* :83-87 */
+};
+
+static pthread_mutex_t g_level_counters_lock = PTHREAD_MUTEX_INITIALIZER;
+static uint64_t g_level_counters[GC_COUNT];
+
+/* one stream's counters into the process's: sums, and maxima where the name says so */
+static void g_counters_merge(const uint64_t *c) {
+    pthread_mutex_lock(&g_level_counters_lock);
+    for (int k = 0; k < GC_COUNT; k++) {
+        if (!gc_is_max(k)) {
+            g_level_counters[k] += c[k];
+        } else if (c[k] > g_level_counters[k]) {
+            g_level_counters[k] = c[k];
+        }
+    }
+    pthread_mutex_unlock(&g_level_counters_lock);
+}
+
+void fdo_level_counters(uint64_t *out, size_t n) {
+    pthread_mutex_lock(&g_level_counters_lock);
+    for (size_t k = 0; k < n && k < GC_COUNT; k++) {
+        out[k] = g_level_counters[k];
+    }
+    pthread_mutex_unlock(&g_level_counters_lock);
+}
+
+void fdo_level_counters_reset(void) {
+    pthread_mutex_lock(&g_level_counters_lock);
+    memset(g_level_counters, 0, sizeof(g_level_counters));
+    pthread_mutex_unlock(&g_level_counters_lock);
+}
+
+/* compress_to_vec_with_level (compress/mod.rs:299-303) / compress_to_vec_rle (:306-310):
  * Compressor::new / new_rle (:69-123), ONE write_data (:126-190, the "no buffered input" branch:
  * the parser runs over the caller's buffer with Flush::None, then the window tail is kept), then
- * finish (:194-214) over the kept tail with Flush::Finish.  Returns bytes written, 0 if out_cap is
- * too small. */
-static size_t g_compress(const uint8_t *input, size_t len, uint8_t *out, size_t out_cap, int rle) {
+ * finish (:194-214) over the kept tail with Flush::Finish.  `lv` is a row of G_LEVELS.  Returns bytes
+ * written, 0 if out_cap is too small.  The stream's counters go to `counters` (GC_COUNT values) if given. */
+static size_t g_compress(const uint8_t *input, size_t len, uint8_t *out, size_t out_cap, const GLevel *lv,
+                         uint64_t *counters) {
     ensure_tables();
     if (len > (1u << 30)) {
         return 0; /* write_data splits inputs above 1 GiB into several calls (:130-136): not restated */
@@ -2380,11 +2770,35 @@ static size_t g_compress(const uint8_t *input, size_t len, uint8_t *out, size_t 
     gbw_raw(&w, hdr, 2);
     GParser ps;
     memset(&ps, 0, sizeof(ps));
-    ps.use_hash = !rle;
-    ps.skip_ahead_shift = 5; /* GreedyParser::new(5, ..) :76 / RleParser::new(5) :114 */
+    int rle = lv->finder == G_FINDER_NULL, chained = lv->finder == G_FINDER_CHAIN || lv->finder == G_FINDER_HYBRID;
+    ps.finder = lv->finder;
+    ps.skip_ahead_shift = lv->skip_ahead_shift;
+    ps.max_lazy = lv->max_lazy;
+    ps.search_depth = lv->search_depth;
+    ps.nice_length = lv->nice_length;
+    ps.min_match = lv->min_match;
+    if (lv->finder == G_FINDER_CHAIN) { /* HashChainMatchFinder::new (hashchain.rs:23-36) */
+        ps.min_match8 = lv->min_match == 8;
+        ps.mask = UINT64_MAX >> (8 * (8 - lv->min_match));
+    } else if (lv->finder == G_FINDER_HYBRID) { /* HybridMatchFinder::new (hybrid.rs:24-38) */
+        unsigned m1 = lv->min_match + 1u < 8 ? lv->min_match + 1u : 8;
+        ps.mask = UINT64_MAX >> (8 * (8 - m1));
+        ps.mask4 = UINT64_MAX >> (8 * (8 - lv->min_match));
+    }
     ps.hash_table = rle ? NULL : (uint32_t *)calloc(65536, sizeof(uint32_t));
-    ps.symbols = (GSymbol *)malloc(sizeof(GSymbol) * G_MAX_SYMBOLS);
-    size_t window_size = rle ? 1 : 32768;
+    ps.links = chained ? (uint32_t *)calloc(32768, sizeof(uint32_t)) : NULL;
+    ps.hash4_table = lv->finder == G_FINDER_HYBRID ? (uint32_t *)calloc(65536, sizeof(uint32_t)) : NULL;
+    ps.sym_cap = G_MAX_SYMBOLS;
+    ps.symbols = (GSymbol *)malloc(sizeof(GSymbol) * ps.sym_cap);
+    if (!ps.symbols || (!rle && !ps.hash_table) || (chained && !ps.links) ||
+        (lv->finder == G_FINDER_HYBRID && !ps.hash4_table)) {
+        free(ps.hash_table);
+        free(ps.links);
+        free(ps.hash4_table);
+        free(ps.symbols);
+        return 0;
+    }
+    size_t window_size = rle ? 1 : 32768; /* :98, :120 */
     uint32_t adler = fdo_adler32(input, len);
     /* write_data */
     size_t written = g_inner_compress(&ps, &w, input, len, 0, 0, 0);
@@ -2399,16 +2813,94 @@ static size_t g_compress(const uint8_t *input, size_t len, uint8_t *out, size_t 
     const uint8_t tr[4] = {(uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler};
     gbw_raw(&w, tr, 4);
     free(ps.hash_table);
+    free(ps.links);
+    free(ps.hash4_table);
     free(ps.symbols);
-    return w.overflow ? 0 : w.pos;
+    if (counters) {
+        memcpy(counters, ps.c, sizeof(ps.c));
+    }
+    return (w.overflow || ps.alloc_failed) ? 0 : w.pos;
 }
 
 size_t fdo_compress_bound(size_t len) { return len + len / 2 + 1024; }
 size_t fdo_compress_level1(const uint8_t *input, size_t len, uint8_t *out, size_t out_cap) {
-    return g_compress(input, len, out, out_cap, 0);
+    return g_compress(input, len, out, out_cap, &G_LEVELS[1], NULL);
 }
 size_t fdo_compress_rle(const uint8_t *input, size_t len, uint8_t *out, size_t out_cap) {
-    return g_compress(input, len, out, out_cap, 1);
+    return g_compress(input, len, out, out_cap, &G_LEVELS[0], NULL);
+}
+
+/* compress_to_vec_with_level (compress/mod.rs:299-303): 0 stored, 1 as fdo_compress_level1, 2..6 their rows of the
+ * table, `7..` one row.  The stream's coverage counters are added to the process's (fdo_level_counters). */
+size_t fdo_compress_level(const uint8_t *input, size_t len, unsigned level, uint8_t *out, size_t out_cap) {
+    if (len > (1u << 30)) {
+        return 0;
+    }
+    if (level == 0) {
+        if (out_cap < len + 5 * (len / 65535 + 1) + 6) {
+            return 0; /* fdo_compress_stored does not check its capacity */
+        }
+        return fdo_compress_stored(input, len, out, out_cap);
+    }
+    if (level == 1) {
+        return fdo_compress_level1(input, len, out, out_cap);
+    }
+    uint64_t c[GC_COUNT];
+    size_t n = g_compress(input, len, out, out_cap, &G_LEVELS[level > 7 ? 7 : level], c);
+    if (n) {
+        g_counters_merge(c);
+    }
+    return n;
+}
+
+/* one stream per task, as fdo_deflate_ultrafast_batch; a stream that does not fit its slot gets length 0 */
+typedef struct {
+    BatchJob job;
+    unsigned level;
+} LevelBatchJob;
+
+static void *level_batch_worker(void *arg) {
+    LevelBatchJob *lj = (LevelBatchJob *)((BatchJob *)arg)->ctx;
+    BatchJob *j = &lj->job;
+    uint64_t total[GC_COUNT] = {0}, c[GC_COUNT];
+    for (;;) {
+        uint64_t i = __atomic_fetch_add(j->next, 1, __ATOMIC_RELAXED);
+        if (i >= j->n) {
+            break;
+        }
+        const uint8_t *src = j->in + j->in_off[i];
+        size_t src_len = (size_t)(j->in_off[i + 1] - j->in_off[i]);
+        uint8_t *dst = j->out + j->out_off[i];
+        size_t cap = (size_t)(j->out_off[i + 1] - j->out_off[i]);
+        if (lj->level < 2) {
+            j->out_len[i] = (uint32_t)fdo_compress_level(src, src_len, lj->level, dst, cap);
+            continue;
+        }
+        size_t n = g_compress(src, src_len, dst, cap, &G_LEVELS[lj->level > 7 ? 7 : lj->level], c);
+        j->out_len[i] = (uint32_t)n;
+        for (int k = 0; n && k < GC_COUNT; k++) { /* per thread, then summed */
+            total[k] = gc_is_max(k) ? (c[k] > total[k] ? c[k] : total[k]) : total[k] + c[k];
+        }
+    }
+    g_counters_merge(total);
+    return NULL;
+}
+
+void fdo_deflate_level_batch(const uint8_t *in, const uint64_t *in_off, uint8_t *out, const uint64_t *out_off,
+                             uint32_t *out_len, uint64_t n, unsigned level, int nthreads) {
+    ensure_tables();
+    LevelBatchJob lj;
+    memset(&lj, 0, sizeof(lj));
+    lj.job.in = in;
+    lj.job.in_off = in_off;
+    lj.job.out = out;
+    lj.job.out_off = out_off;
+    lj.job.out_len = out_len;
+    lj.job.n = n;
+    lj.job.ctx = &lj;
+    lj.job.worker = level_batch_worker;
+    lj.level = level;
+    run_batch(&lj.job, nthreads > 16 ? 16 : nthreads);
 }
 
 /* ========================================================================= */

@@ -17,6 +17,12 @@
  * and checksum tests (src/decompress.rs:1261-1325) and the ultra-fast HEADER
  * (src/compress/ultrafast.rs:82-86).
  *
+ * The general encoder of every level 0..9 (fdo_compress_level) is a restatement too.  For the bytes of levels 2..9
+ * there is a second reading of the same Rust, written apart from this one: the pure-Python models tests/level_model.py
+ * and tests/lazy_model.py.  tests/test_oracle_levels.py holds the two to the same bytes and to the same branch counts
+ * (fdo_level_counters) over every shared input.  That pins each against a slip of its own, not against a misreading
+ * both share: the real crate still cannot be run here.
+ *
  * Every function cites the reference file:line it follows.
  */
 #ifndef FDEFLATE_ORACLE_H
@@ -121,6 +127,28 @@ size_t fdo_compress_rle(const uint8_t *input, size_t len, uint8_t *out, size_t o
 /* test instrumentation: trees shortened so far, [0] to 15 bits, [1] to 7 bits */
 extern unsigned long fdo_length_limit_events[2];
 
+/* ---- general encoder, every level (src/compress/mod.rs:75-88, :299-303): compress_to_vec_with_level.
+ * Level 0 is the stored encoder, 1 is fdo_compress_level1, 2 and 3 GreedyParser over HashChainMatchFinder
+ * (matchfinder/hashchain.rs), 4..9 LazyParser (parse/lazy.rs) over HybridMatchFinder (matchfinder/hybrid.rs);
+ * `7..` is one parameter set there, so 7, 8, 9 and anything above give the same bytes.  Returns bytes written,
+ * 0 if out_cap is too small or len > 2^30.  Parity pin: restated from the Rust, and byte- and branch-count-equal
+ * to the pure-Python models tests/level_model.py and tests/lazy_model.py, which are another reading of the same
+ * text (tests/test_oracle_levels.py); the crate itself cannot be run here. */
+size_t fdo_compress_level(const uint8_t *input, size_t len, unsigned level, uint8_t *out, size_t out_cap);
+
+/* Coverage counters of levels 2..9, summed over every stream compressed through fdo_compress_level and
+ * fdo_deflate_level_batch since the last reset (maxsteps, max_block_symbols and pass2_base are maxima).
+ * Order: steps2 nice eod depth alias maxsteps quarter rescue_hit rescue_miss rescue_zero
+ *        m0_empty m0_earlier m0_longer m0_kept m0_inserted m0_cut m0_dropped m2_same_start
+ *        pending resumed blocks max_block_symbols pass2_base
+ *        skip_nonzero scan_end_in_skip rle_events
+ * The first 23 mean what tests/lazy_model.py's docstring says; skip_nonzero: advance_to_match skipped ahead by
+ * more than zero; scan_end_in_skip: a skip of 2 or more took the scan to max_ip or past it; rle_events: runs
+ * matched by get_match. */
+#define FDO_LEVEL_COUNTERS 26
+void fdo_level_counters(uint64_t *out, size_t n);
+void fdo_level_counters_reset(void);
+
 /* ---- PNG scanline filters (PNG specification section 9; the png crate's step either side of the
  * codec).  filt = rows x (1 + row_bytes) with the filter-type byte first, pix = rows x row_bytes.
  * Return 0 ok, 1 filter type > 4, 2 size not a whole number of rows. */
@@ -134,6 +162,11 @@ void fdo_inflate_batch(const uint8_t *in, const uint64_t *in_off, uint8_t *out,
 void fdo_deflate_ultrafast_batch(const uint8_t *in, const uint64_t *in_off, uint8_t *out,
                                  const uint64_t *out_off, uint32_t *out_len, uint64_t n,
                                  int nthreads);
+/* fdo_compress_level over a batch; at most 16 threads are used.  A stream that does not fit its slot gets
+ * out_len 0. */
+void fdo_deflate_level_batch(const uint8_t *in, const uint64_t *in_off, uint8_t *out,
+                             const uint64_t *out_off, uint32_t *out_len, uint64_t n, unsigned level,
+                             int nthreads);
 
 /* Timed CPU baseline: threads created once, thread t decodes streams t, t+T, ... `passes` times;
  * returns the seconds between start and finish barrier (< 0: failure).  kind 0 = this oracle,

@@ -4,8 +4,10 @@ over HybridMatchFinder (src/compress/matchfinder/hybrid.rs:40-162), whole zlib s
 Everything the lazy levels share with levels 1-3 is tests/level_model.py's and is imported from there: ParserInner's
 pieces (`Parser.get_match`, `advance_to_match`, `advance`, `insert_match`, `write_block_if_ready`), `match_length`,
 `rle_match`, `write_block`, `BitWriter` and the two-pass driver `_compress` -- all pinned against the oracle at level 1
-and RLE by tests/test_level_model.py.  What is stated here, and has NO second implementation (the oracle has neither,
-and there is no Rust toolchain to run the reference), is `Hybrid` and `LazyParser.compress`: about 150 lines.
+and RLE by tests/test_level_model.py.  What is stated here is `Hybrid` and `LazyParser.compress`, about 150 lines.  The
+oracle restates the same two pieces in C from the Rust (fdo_compress_level, levels 4..9), written apart from this
+file: two readings, which tests/test_oracle_levels.py holds to the same bytes and, counter by counter, to the same
+branch counts over shared_inputs().  A misreading both share stays possible: there is no Rust toolchain to run the crate.
 
 `compress(data, level)` serves levels 4..9 (7, 8 and 9 are one parameter set, compress/mod.rs:80-87).  The counters of
 the last call are in `last_counters`:

@@ -1,12 +1,13 @@
 """Pure-Python restatement of the reference's general encoder for levels 1, 2 and 3 and RLE: whole zlib
 streams, no compiled code.
 
-The oracle (oracle/fdeflate_oracle.c) has level 1 and RLE only, so the expected bytes of levels 2 and 3
-come from here.  tests/test_level_model.py pins this model against the oracle where the two overlap
-(level 1 and RLE over the oracle tests' encoder inputs and the run-edge inputs): that pins the parser, the runs,
-match_length::<true>, block cutting and the whole block writer.  What no second implementation pins is
-HashChainMatchFinder (hashchain.rs) and match_length::<false> (matchfinder/mod.rs:71-76), about 150
-lines here (`Chain`, and the `min8 = False` branch of `match_length`).
+The expected bytes of levels 2 and 3 in the GPU tests of those levels come from here.  tests/test_level_model.py pins
+this model against the oracle (oracle/fdeflate_oracle.c) at level 1 and RLE over the oracle tests' encoder inputs and
+the run-edge inputs: that pins the parser, the runs, match_length::<true>, block cutting and the whole block writer.
+HashChainMatchFinder (hashchain.rs) and match_length::<false> (matchfinder/mod.rs:71-76), about 150 lines here
+(`Chain`, and the `min8 = False` branch of `match_length`), are stated a second time in the oracle's C
+(fdo_compress_level, written from the Rust apart from this file); tests/test_oracle_levels.py holds the two readings
+to the same bytes and the same counts of the finder's exits.  The real crate cannot be run here.
 
 Reference: Compressor::write_data + finish for one buffer (src/compress/mod.rs:126-214), ParserInner
 (parse/mod.rs), GreedyParser (parse/greedy.rs), RleParser (parse/rle.rs), HashTableMatchFinder

@@ -88,6 +88,15 @@ def lib():
         L.fdo_deflate_ultrafast_batch.restype = None
         L.fdo_deflate_ultrafast_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p, C.c_uint64, C.c_int]
+        L.fdo_compress_level.restype = C.c_size_t
+        L.fdo_compress_level.argtypes = [C.c_void_p, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t]
+        L.fdo_deflate_level_batch.restype = None
+        L.fdo_deflate_level_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint64, C.c_uint, C.c_int]
+        L.fdo_level_counters.restype = None
+        L.fdo_level_counters.argtypes = [C.c_void_p, C.c_size_t]
+        L.fdo_level_counters_reset.restype = None
+        L.fdo_level_counters_reset.argtypes = []
         _lib = L
     return _lib
 
@@ -155,6 +164,48 @@ def length_limit_events():
 def compress_rle(data):
     """compress_to_vec_rle (src/compress/mod.rs:306)"""
     return _compress_general(lib().fdo_compress_rle, data)
+
+
+LEVEL_COUNTERS = ("steps2", "nice", "eod", "depth", "alias", "maxsteps", "quarter", "rescue_hit", "rescue_miss",
+                  "rescue_zero", "m0_empty", "m0_earlier", "m0_longer", "m0_kept", "m0_inserted", "m0_cut", "m0_dropped",
+                  "m2_same_start", "pending", "resumed", "blocks", "max_block_symbols", "pass2_base",
+                  "skip_nonzero", "scan_end_in_skip", "rle_events")     # the order of fdo_level_counters
+
+
+def compress_level(data, level):
+    """compress_to_vec_with_level (src/compress/mod.rs:299): level 0..9 and above"""
+    a, p = _buf(data)
+    cap = lib().fdo_compress_bound(a.size)
+    out = np.zeros(cap, dtype=np.uint8)
+    n = lib().fdo_compress_level(p if a.size else None, a.size, level, out.ctypes.data_as(C.c_void_p), cap)
+    assert n > 0
+    return out[:n].tobytes()
+
+
+def deflate_level_batch(in_buf, in_off, out_buf, out_off, level, nthreads=16):
+    """fdo_compress_level of stream i = in_buf[in_off[i]:in_off[i+1]] into out_buf[out_off[i]:out_off[i+1]];
+    -> the lengths written (0: the slot was too small)"""
+    n = len(in_off) - 1
+    out_len = np.zeros(n, dtype=np.uint32)
+    in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+    out_off = np.ascontiguousarray(out_off, dtype=np.uint64)
+    lib().fdo_deflate_level_batch(in_buf.ctypes.data_as(C.c_void_p), in_off.ctypes.data_as(C.c_void_p),
+                                  out_buf.ctypes.data_as(C.c_void_p), out_off.ctypes.data_as(C.c_void_p),
+                                  out_len.ctypes.data_as(C.c_void_p), n, level, min(int(nthreads), 16))
+    return out_len
+
+
+def level_counters(reset=False):
+    """The oracle's coverage counters of levels 2..9 since the last reset, as a dict over LEVEL_COUNTERS."""
+    v = np.zeros(len(LEVEL_COUNTERS), dtype=np.uint64)
+    lib().fdo_level_counters(v.ctypes.data_as(C.c_void_p), v.size)
+    if reset:
+        lib().fdo_level_counters_reset()
+    return {k: int(x) for k, x in zip(LEVEL_COUNTERS, v)}
+
+
+def level_counters_reset():
+    lib().fdo_level_counters_reset()
 
 
 def png_unfilter(filt, row_bytes, bpp):

@@ -505,6 +505,188 @@ def chain_inputs():
     return out
 
 
+VOLUME_FAMILIES = "abcdefgh"
+
+
+def _vol_noise(r, n):
+    """a: noise over an alphabet of 2, 3, 4, 16 or 256 (long chains, depth exits, quarter depth)"""
+    a = (2, 3, 4, 16, 256)[int(r.integers(0, 5))]
+    return bytes(r.integers(0, a, n, dtype=np.uint8))
+
+
+def _vol_text(r, n, words=None):
+    """b: text over 6..40 words of 2..9 bytes that share prefixes (deferrals, every m0 clause)"""
+    k = int(r.integers(6, 41)) if words is None else words
+    span = 3 if words is None else 26      # a large dictionary gets an alphabet that keeps its chains short
+    stem = bytes(r.integers(97, 97 + span, 4, dtype=np.uint8))
+    ws = []
+    for _ in range(k):
+        ln = int(r.integers(2, 10))
+        pre = int(r.integers(0, min(ln, 5)))
+        ws.append(stem[:pre] + bytes(r.integers(97, 97 + span, ln - pre, dtype=np.uint8)))
+    picks = r.integers(0, k, n // 2 + 1)
+    return b"".join(ws[int(i)] for i in picks)[:n]
+
+
+def _vol_motifs(r, n):
+    """c: motifs of period 2..9 -- never a run -- each repeated for 20..200 bytes, then a fresh motif, one byte of each
+    stretch mutated: the first repeat of a fresh motif has the hash of a position a few bytes back that nothing else
+    in the tables has, i.e. of an earlier step of the same look-ahead group"""
+    out = bytearray()
+    while len(out) < n:
+        p = int(r.integers(2, 10))
+        motif = r.integers(0, 256, p, dtype=np.uint8)
+        while len(set(motif.tolist())) < 2:
+            motif = r.integers(0, 256, p, dtype=np.uint8)
+        ln = int(r.integers(20, 201))
+        s = bytearray((bytes(motif) * (ln // p + 1))[:ln])
+        k = int(r.integers(p, ln))
+        s[k] = (s[k] + 1 + int(r.integers(0, 255))) & 0xFF
+        out += s
+    return bytes(out[:n])
+
+
+def _vol_rescue(r, n):
+    """d: 5-byte words whose first four bytes recur with another fifth (the 4-table's rescue, both outcomes)"""
+    heads = [bytes(r.integers(0, 256, 4, dtype=np.uint8)) for _ in range(int(r.integers(8, 60)))]
+    out = bytearray()
+    while len(out) < n:
+        out += heads[int(r.integers(0, len(heads)))] + bytes(r.integers(0, 256, int(r.integers(1, 4)), dtype=np.uint8))
+    return bytes(out[:n])
+
+
+def _vol_skip(r, n):
+    """e: an incompressible stretch of 600..6 000 bytes and one of 5 000..40 000, each followed by a copy of an earlier
+    part (skip-ahead at shift 6, 9 and 12; the scan range ending inside a skipping group); cut to n, so short streams
+    hold the head of it"""
+    out = bytearray()
+    for lo, hi in ((600, 6001), (5000, 40001)):
+        ln = int(r.integers(lo, hi))
+        ln = min(ln, max(n - len(out), 16))
+        x = bytes(r.integers(0, 256, ln, dtype=np.uint8))
+        a = int(r.integers(0, max(ln - 8, 1)))
+        out += x + x[a:a + int(r.integers(8, 300))]
+    while len(out) < n:
+        out += bytes(r.integers(0, 256, 64, dtype=np.uint8))
+    return bytes(out[:n])
+
+
+def _vol_window(r, n):
+    """f: a block repeated at distances 1..9 and 32 760..32 776 (the window edge, the alias at exactly 32 768); streams
+    too short for the far distances keep the near ones.  The far copies: 40 bytes at 17 places 64 apart in a random
+    head, each copied to its place + d, one d each."""
+    head = 17 * 64 if n >= 36000 else 0
+    out = bytearray(bytes(r.integers(0, 256, head, dtype=np.uint8)))
+    while len(out) < n:
+        blk = bytes(r.integers(0, 256, int(r.integers(12, 80)), dtype=np.uint8))
+        d = int(r.integers(1, 10))
+        unit = blk[:d]
+        out += blk + (unit * 40)[:int(r.integers(d + 4, 60))] + blk[:int(r.integers(4, len(blk)))]
+    del out[n:]
+    if head:
+        for j, d in enumerate(range(32760, 32777)):
+            out[64 * j + d:64 * j + d + 40] = out[64 * j:64 * j + 40]
+    return bytes(out)
+
+
+def _vol_runs(r, n, p_long=0.2):
+    """g: runs of 4..600 equal bytes between matches (a run next to a table candidate in one group).  One run in five
+    is drawn from the whole range, the others from 4..23; with p_long = 0.01 and short words a run match comes every
+    17 bytes or so at every level, level 2 included, which finds little else to match in the other families."""
+    ws = [bytes(r.integers(0, 256, int(r.integers(5, 12)), dtype=np.uint8)) for _ in range(8)]
+    out = bytearray()
+    while len(out) < n:
+        if p_long >= 0.1:
+            out += ws[int(r.integers(0, 8))]
+        ln = int(r.integers(4, 601)) if r.random() < p_long else int(r.integers(4, 24 if p_long >= 0.1 else 13))
+        out += bytes([int(r.integers(0, 256))]) * ln
+        out += ws[int(r.integers(0, 8))][:int(r.integers(1, 12))]
+    return bytes(out[:n])
+
+
+def _vol_rows(r, n):
+    """h: the bench's synthetic PNG-filter rows"""
+    return synth.gen_stream_np(int(r.integers(0, 1 << 20)), max(n, 1)).tobytes()[:n]
+
+
+_VOLUME_MAKERS = dict(a=_vol_noise, b=_vol_text, c=_vol_motifs, d=_vol_rescue, e=_vol_skip, f=_vol_window, g=_vol_runs,
+                      h=_vol_rows)
+
+_H_MULT = np.uint64(11400714785074694791)
+
+
+def head_hashes(x, nbytes):
+    """The encoder's table index of every position of x that has 8 bytes to read: the 64-bit load masked to `nbytes`
+    bytes, times the multiplier, bits 40..55 (matchfinder/mod.rs:42-44 with `% CACHE_SIZE`)."""
+    a = np.frombuffer(x, dtype=np.uint8)
+    if a.size < 8:
+        return np.zeros(0, dtype=np.uint32)
+    v = np.zeros(a.size - 7, dtype=np.uint64)
+    for k in range(nbytes):
+        v |= a[k:a.size - 7 + k].astype(np.uint64) << np.uint64(8 * k)
+    with np.errstate(over="ignore"):
+        return (((v * _H_MULT) >> np.uint64(40)) & np.uint64(0xFFFF)).astype(np.uint32)
+
+
+def group_collisions(x, nbytes=6):
+    """Pairs of positions (i, i + d), d = 1..7 -- near enough for one look-ahead group of eight steps -- with the same
+    head-table index, where i is the first position of x with that index: the later one finds in the table what the
+    earlier step of its group put there.  With nbytes = 6 (min_match 5 + 1) the pair collides at min_match 4 as well."""
+    h = head_hashes(x, nbytes)
+    if h.size < 9:
+        return 0
+    first = np.zeros(h.size, dtype=bool)
+    first[np.unique(h, return_index=True)[1]] = True
+    total = 0
+    for d in range(1, 8):
+        total += int(np.count_nonzero(first[:-d] & (h[:-d] == h[d:])))
+    return total
+
+
+_volume_cache = {}
+
+
+def level_volume_inputs(count=2000):
+    """The volume corpus of the encoder levels 2..9 (tests/test_oracle_levels.py, tests/test_gpu_levels_oracle.py):
+    -> (list of (family, bytes), info).  Deterministic.  Families a..h as the makers above say.  Order: first 24 long
+    streams of 40 000..160 000 bytes (19 from the short-chain families: b with 4 000 words, d, h; one of g with short
+    runs, which cuts a block at level 2 as well; one each of e and f, whose far distances need the room; two low-entropy
+    ones of at most 100 000 bytes), so that with few streams resident every later stream runs over a link ring a long
+    one left behind; then the eight clause inputs; then, shuffled, every length 0..300 once and log-uniform lengths up
+    to 20 000, the families in turn.  info["group_collisions"]: group_collisions() summed over family c."""
+    if count in _volume_cache:
+        return _volume_cache[count]
+    import lazy_model
+    r = np.random.default_rng(20261020)
+    rows = []
+    for k in range(19):
+        n = int(r.integers(40000, 160001))
+        fam = "bdh"[k % 3]
+        rows.append((fam, _vol_text(r, n, words=4000) if fam == "b" else _VOLUME_MAKERS[fam](r, n)))
+    rows.append(("g", _vol_runs(r, 160000, p_long=0.01)))
+    for fam in "ef":
+        rows.append((fam, _VOLUME_MAKERS[fam](r, int(r.integers(70000, 120001)))))
+    for a in (2, 4):
+        rows.append(("a", bytes(r.integers(0, a, int(r.integers(40000, 100001)), dtype=np.uint8))))
+    # the two clauses by which a match in hand replaces the deferred one because it starts earlier, or at the same place
+    # and is longer, need a lazy match that reaches backwards past the start of m1 while a match is deferred: about one
+    # stream in a thousand of families a and b does that at a given level.  lazy_model.clause_inputs() are eight such
+    # streams of those two families (noise over two symbols; words over three or four), found by a search over seeds
+    rows += [("a" if max(x) < 67 else "b", x) for x in lazy_model.clause_inputs()]
+    lengths = list(range(301))
+    while len(rows) + len(lengths) < count:
+        lengths.append(int(np.exp(r.uniform(np.log(300.0), np.log(20000.0)))))
+    lengths = [lengths[int(i)] for i in r.permutation(len(lengths))]
+    for k, n in enumerate(lengths):
+        fam = VOLUME_FAMILIES[k % 8]
+        x = _VOLUME_MAKERS[fam](r, n)
+        assert len(x) == n, (fam, n, len(x))
+        rows.append((fam, x))
+    info = {"group_collisions": sum(group_collisions(x) for fam, x in rows if fam == "c")}
+    _volume_cache[count] = (rows, info)
+    return rows, info
+
+
 def late_match_inputs():
     """24 streams whose first match comes late and reaches far back: 1 100 .. 6 000 random bytes, then a copy of their
     own bytes 100..400 (a 300-byte match whose walk backwards has hundreds of bytes of room), then 0, 3, 9 or 40

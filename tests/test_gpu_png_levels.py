@@ -11,6 +11,7 @@ The pipelines: the pictures of tests/png_levels_cases.py in one mixed batch at l
 files of the models (tests/test_png_levels_model.py checks those on the CPU).  Everything is bit-exact.
 """
 import functools
+import zlib
 
 import numpy as np
 import pytest
@@ -453,6 +454,48 @@ def test_callers_slots_at_the_bound_and_one_byte_short():
     assert own_st.cpu().tolist() == [2 if e[0] == 13 else e[0] for e in expected]
     host = own.cpu().numpy()
     assert host[3:own_off[-1]].tobytes() == b"".join(e[1] or b"" for e in expected) and (host[own_off[-1]:] == GUARD).all()
+
+
+@functools.lru_cache(maxsize=None)
+def _bench_pictures():
+    """64 pictures of 341 x 64 RGB8: the bench's synthetic streams 0..63 (fdeflate_amd.synth, 64 filtered rows of 1 + 1023
+    bytes each) unfiltered into pixels.  -> [(RGBA8 bytes with alpha 255, the rows the encoder must filter and compress)],
+    the rows' types chosen by png_choose_model and applied by png_model."""
+    import oracle_binding as ob
+    from fdeflate_amd import synth
+    out = []
+    for i in range(64):
+        st, pix = ob.png_unfilter(synth.gen_stream_np(i, 65536).tobytes(), 1023, 3)
+        assert st == 0 and len(pix) == 64 * 1023
+        rows = np.frombuffer(pix, dtype=np.uint8).reshape(64, 1023)
+        rgba = np.full((64 * 341, 4), 255, dtype=np.uint8)
+        rgba[:, :3] = rows.reshape(-1, 3)
+        filt = png_model.filter_rows(rows, 3, lc.choose(rows, 3))
+        out.append((rgba.reshape(-1), np.ascontiguousarray(filt).tobytes()))
+    return out
+
+
+@pytest.mark.parametrize("level", [1, 3, 6, 9])
+def test_realistic_pictures_idat_is_the_oracles_stream(level):
+    """The pipeline at the workload's shape -- the case pictures above are 48 x 40 and smaller --: 64 pictures of
+    341 x 64 RGB8 (66 KB of filtered rows each) in one batch; every file's IDAT payload is the oracle's stream at that
+    level of the rows the models filter, and the file is the model's around it."""
+    import torch
+    import fdeflate_amd.png_levels as pl
+    import oracle_binding as ob
+    import png_encode_mixed_model as em
+    pictures = _bench_pictures()
+    cases = [("bench-%d" % i, rgba, 341, 64, (8, 2), 0) for i, (rgba, _) in enumerate(pictures)]
+    rgba, r_off, width, height, pairs = _collection(cases)
+    file, f_off, f_len, st, _ = pl.png_encode_mixed_rgba_files_level_batch(rgba, r_off, width, height, level, pairs=pairs)
+    torch.cuda.synchronize()
+    assert st.cpu().tolist() == [0] * 64
+    for i, (got, (_, filt)) in enumerate(zip(_files(file, f_off, f_len), pictures)):
+        want = ob.compress_level(filt, level)
+        idat = lc.idat_of(got)
+        assert idat == want, (level, i, len(idat), len(want))
+        assert got == em.write_file(want, 341, 64, 8, 2, crc=zlib.crc32), (level, i)
+        assert lc.inflate(idat) == filt
 
 
 def test_levels_that_do_not_exist_and_the_empty_batch():

@@ -1,5 +1,5 @@
 """CPU checks of tests/lazy_model.py, the pure-Python restatement that supplies the expected bytes of encoder levels 4-9
-(LazyParser + HybridMatchFinder; the oracle has neither), and of the lazy levels' launch plan.
+(LazyParser + HybridMatchFinder) next to the oracle's C restatement of the same levels, and of the lazy levels' launch plan.
 
 - every output round-trips through zlib and the oracle's decoder, starts 78 01 and fits fdh_compress_bound's formula;
 - the empty input, levels 7 = 8 = 9;
@@ -11,7 +11,8 @@
 - no link slot is read before the stream has written it (the device does not clear the ring);
 - level 6 against level 3 in size, as a sanity condition on the model;
 - fdh_debug_level_plan on 256 CUs against the rule worked by hand.
-What stays unpinned by a second implementation: lazy_model.Hybrid and lazy_model.LazyParser.compress.
+lazy_model.Hybrid and lazy_model.LazyParser.compress against the second reading of the Rust, the oracle's: bytes and
+branch counts, in tests/test_oracle_levels.py.  The real crate still cannot be run here.
 """
 import ctypes as C
 import zlib

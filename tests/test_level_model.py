@@ -1,13 +1,12 @@
 """CPU checks of tests/level_model.py, the pure-Python restatement that supplies the expected bytes of
-encoder levels 2 and 3 (the oracle has level 1 and RLE only), and of the level-selecting entry point's
-behaviour without a GPU.
+encoder levels 2 and 3, and of the level-selecting entry point's behaviour without a GPU.
 
 - the pin: the model equals the oracle, byte for byte, at level 1 and in RLE mode over the oracle
   tests' encoder inputs and the run-edge inputs -- parser, runs, match_length::<true>, block cutting,
   the block writer;
 - levels 2 and 3 round-trip through zlib and stay inside fdh_compress_bound's formula;
 - the chain inputs reach every exit of the chain search at both levels (coverage is asserted, not hoped
-  for).  What stays unpinned by a second implementation is the chain finder and match_length::<false>;
+  for).  The chain finder and match_length::<false> against the oracle's own statement of them: tests/test_oracle_levels.py;
 - the inputs reach every exit of the device's counter of equal bytes in each of its four uses;
 - the general encoder's launch plan (lanes, wavefronts), through the library's hook: no device needed.
 """
