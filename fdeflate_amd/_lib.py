@@ -127,7 +127,16 @@ PNG_LEVELS_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name
     "fdh_png_level_bound": "u64 u64 u32",
     "fdh_png_level_file_bound": "u64 u64 u64 u32 u64",
 }.items()}
-_ALL_TABLES = (*TABLES.values(), LEVELS_SIGNATURES, PNG_LEVELS_SIGNATURES)
+# include/fdeflate_hip_pieces.h, the calls behind fdeflate_amd.pieces (tests/test_abi_pieces.py compares): beside TABLES
+# for the same reason.
+PIECES_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
+    "fdh_deflate_level_pieces_batch": "int 1 8 1 1 8 4 4 u64 u32 stream",
+    "fdh_deflate_stitch_batch": "int 1 8 4 4 8 8 1 8 4 u64 stream",
+    "fdh_deflate_pieces_count": "u64 u64 u64",
+    "fdh_deflate_pieces_bound": "u64 u64 u32 u64",
+    "fdh_png_level_pieces_file_bound": "u64 u64 u64 u32 u64 u64",
+}.items()}
+_ALL_TABLES = (*TABLES.values(), LEVELS_SIGNATURES, PNG_LEVELS_SIGNATURES, PIECES_SIGNATURES)
 
 
 def signature(symbol):

@@ -22,7 +22,9 @@
 //    the next 1024 positions are dropped into an LDS array of marks first), once to count symbol
 //    frequencies with LDS atomics, then -- after the Huffman codes are built -- once more to emit:
 //    per-lane bit counts are prefix-summed and every lane ORs its code into the LDS bit ring
-//    (bit_ring.h).  The Adler-32 rides on the second walk.
+//    (bit_ring.h).  The Adler-32 rides on the second walk.  A second instance writes a raw-deflate
+//    PIECE of a longer input instead of a zlib stream (include/fdeflate_hip_pieces.h; deflate_stitch.hip
+//    joins the pieces).
 //
 // The Huffman construction follows Rust's BinaryHeap exactly as the reference uses it (see the
 // oracle's section header for what is pinned and what is not); the order-dependent part (heap
@@ -1098,6 +1100,7 @@ struct GWriteArgs {
     const GMatchRec* matches;
     const GBlockRec* blocks;
     const uint32_t* nblocks;
+    static constexpr bool kPieces = false;
 };
 
 
@@ -1284,7 +1287,20 @@ __device__ void g_walk(GWriteLds& lds, BitRing& br, const uint8_t* in, const GMa
     wave_sync();
 }
 
-__global__ __launch_bounds__(kWave, 4) void deflate_write_kernel(GWriteArgs a) {
+// Piece mode (include/fdeflate_hip_pieces.h): stream `sid` is a piece of a longer input.
+struct GPieceWriteArgs : GWriteArgs {
+    static constexpr bool kPieces = true;
+    const uint8_t* last;  // per piece: not 0 where the piece ends its input
+    uint32_t* adler;      // per piece: the Adler-32 of its bytes, which a stream carries in its trailer
+};
+
+// One stream per wavefront.  ARGS = GWriteArgs is the zlib stream; GPieceWriteArgs a raw-deflate piece: no 78 01, BFINAL
+// only in a last piece, behind a non-last piece the sync marker of Flush::Sync (compress/mod.rs:284-287) where the
+// stream has its trailer, and the checksum to `a.adler`.  The differences are compile-time and the kernel is its own
+// body in both, so the stream instance is the code it was (a body shared through a function was not: two more spills).
+template <typename ARGS>
+__global__ __launch_bounds__(kWave, 4) void deflate_write_kernel(ARGS a) {
+    constexpr bool PIECES = ARGS::kPieces;
     __shared__ GWriteLds lds;
     const int lane = threadIdx.x;
     const uint64_t sid = blockIdx.x;
@@ -1294,8 +1310,12 @@ __global__ __launch_bounds__(kWave, 4) void deflate_write_kernel(GWriteArgs a) {
     const uint32_t nblocks = a.nblocks[sid];
     if (nblocks == 0xFFFFFFFFu) {
         if (lane == 0) a.out_len[sid] = 0xFFFFFFFFu;
+        if constexpr (PIECES)
+            if (lane == 0) a.adler[sid] = 0;
         return;
     }
+    bool last = true;
+    if constexpr (PIECES) last = uni((uint32_t)a.last[sid]) != 0;
     const GMatchRec* recs = a.matches + g_match_slice(off - in0, sid);
     const GBlockRec* blks = a.blocks + g_block_slice(off - in0, sid);
     if (len < 4) {
@@ -1322,7 +1342,7 @@ __global__ __launch_bounds__(kWave, 4) void deflate_write_kernel(GWriteArgs a) {
     br.qbits = (uint64_t)br.gmis * 8;
     br.qflushed = 0;
     br.overflow = false;
-    br.emit_uniform(0x0178, 16);  // zlib header 78 01 (compress/mod.rs:61-63)
+    if (!PIECES) br.emit_uniform(0x0178, 16);  // zlib header 78 01 (compress/mod.rs:61-63)
 
     uint64_t acc_a = 0, acc_b = 0;
     uint32_t b0 = 0, m0 = 0;
@@ -1342,7 +1362,7 @@ __global__ __launch_bounds__(kWave, 4) void deflate_write_kernel(GWriteArgs a) {
     for (uint32_t blk = 0; blk < nblocks; blk++) {
         const uint32_t b1 = uni(blks[blk].end_pos), m1 = uni(blks[blk].match_end), flags = uni(blks[blk].flags);
         if (flags & kGBlockEmptyFixed) {  // compress/mod.rs:234-238: BFINAL, fixed codes, end of block; flush
-            br.emit_uniform(3, 10);
+            if (last) br.emit_uniform(3, 10);  // (under Flush::Sync the empty slice has no block: the marker alone)
             continue;
         }
         // ---- frequencies (bitstream.rs:42-66) ----
@@ -1417,7 +1437,7 @@ __global__ __launch_bounds__(kWave, 4) void deflate_write_kernel(GWriteArgs a) {
             g_huff_codes(vc, lds.clcl, lds.h.small.first, lane);
             wave_sync();
         }
-        br.emit_uniform(((flags & kGBlockEof) ? 5u : 4u) | ((num_litlen - 257) << 3) | ((num_dist - 1) << 8) | (15u << 13), 17);
+        br.emit_uniform((((flags & kGBlockEof) && last) ? 5u : 4u) | ((num_litlen - 257) << 3) | ((num_dist - 1) << 8) | (15u << 13), 17);
         if (br.qbits + 57 - br.qflushed > kEncTileBudget) br.flush(false);
         if (lane < 19) br.or_bits(br.qbits + 3 * (uint32_t)lane, lds.clcl[kClclOrder[lane]] >> 16);
         br.qbits += 57;
@@ -1446,11 +1466,17 @@ __global__ __launch_bounds__(kWave, 4) void deflate_write_kernel(GWriteArgs a) {
         m0 = m1;
     }
     // ---- Compressor::finish (compress/mod.rs:194-214): pad to a byte, Adler-32 big-endian ----
+    if (PIECES && !last) br.emit_uniform(0, 3);  // :285, the empty stored block's BFINAL = 0, BTYPE = 00
     br.emit_uniform(0, (uint32_t)(8 - (br.qbits & 7)) & 7);
-    const uint32_t pa = (uint32_t)(acc_a % kAdlerMod), pb = (uint32_t)(acc_b % kAdlerMod);
-    const uint32_t A = (1u + wave_sum_u32(pa)) % kAdlerMod;
-    const uint32_t B = (uint32_t)(((len % kAdlerMod) + wave_sum_u32(pb)) % kAdlerMod);
-    br.emit_uniform(__builtin_bswap32((B << 16) | A), 32);
+    const uint32_t part_a = (uint32_t)(acc_a % kAdlerMod), part_b = (uint32_t)(acc_b % kAdlerMod);
+    const uint32_t A = (1u + wave_sum_u32(part_a)) % kAdlerMod;
+    const uint32_t B = (uint32_t)(((len % kAdlerMod) + wave_sum_u32(part_b)) % kAdlerMod);
+    if (!PIECES)
+        br.emit_uniform(__builtin_bswap32((B << 16) | A), 32);
+    else if (!last)
+        br.emit_uniform(0xFFFF0000u, 32);  // :286, LEN = 0 and NLEN: 00 00 FF FF
+    if constexpr (PIECES)
+        if (lane == 0) a.adler[sid] = (B << 16) | A;
     br.flush(true);
     if (lane == 0) a.out_len[sid] = br.overflow ? 0xFFFFFFFFu : (uint32_t)((br.qbits >> 3) - br.gmis);
 #ifdef FDH_DEBUG_GEN
@@ -1563,7 +1589,8 @@ extern "C" int fdh_debug_level_plan(uint64_t n, int cus, uint32_t level, uint32_
 // Both launchers: the parser of the mode `m` -- with `lazy`, the lazy parser of kLazyMode with these parameters -- then
 // the block writer.
 static int launch_encoder(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint64_t n,
-                          const GenMode* m, const fdh::LazyParams* lazy, uint64_t total_in, hipStream_t stream) {
+                          const GenMode* m, const fdh::LazyParams* lazy, uint64_t total_in, hipStream_t stream,
+                          const fdh::GPieceWriteArgs* pieces = nullptr) {
     if (n == 0) return 0;
     if (!m) return -1;
     int dev = 0, cus = 0;
@@ -1607,7 +1634,13 @@ static int launch_encoder(const uint8_t* in, const uint64_t* in_off, uint8_t* ou
     else
         hipLaunchKernelGGL(fdh::deflate_parse_kernel<false>, grid, block, 0, stream, p);
     fdh::GWriteArgs wa{in, in_off, out, out_off, out_len, n, p.matches, p.blocks, nblocks};
-    hipLaunchKernelGGL(fdh::deflate_write_kernel, dim3((unsigned)n), block, 0, stream, wa);
+    if (pieces) {
+        fdh::GPieceWriteArgs pw = *pieces;
+        static_cast<fdh::GWriteArgs&>(pw) = wa;
+        hipLaunchKernelGGL(fdh::deflate_write_kernel<fdh::GPieceWriteArgs>, dim3((unsigned)n), block, 0, stream, pw);
+    } else {
+        hipLaunchKernelGGL(fdh::deflate_write_kernel<fdh::GWriteArgs>, dim3((unsigned)n), block, 0, stream, wa);
+    }
     if (e = hipGetLastError(); e != hipSuccess) return (int)failed(e, "general-encoder kernel launch");
     // the workspace is per device, not per stream: calls are serialised by finishing this one
     if (e = hipStreamSynchronize(stream); e != hipSuccess) return (int)failed(e, "hipStreamSynchronize(stream)");
@@ -1623,4 +1656,17 @@ extern "C" int fdh_launch_deflate_level(const uint8_t* in, const uint64_t* in_of
                                         uint32_t* out_len, uint64_t n, uint32_t level, uint64_t total_in, hipStream_t stream) {
     const fdh::LazyParams* lazy = fdh::lazy_params(level);
     return launch_encoder(in, in_off, out, out_off, out_len, n, lazy ? &fdh::kLazyMode : nullptr, lazy, total_in, stream);
+}
+
+// include/fdeflate_hip_pieces.h: the parser of `level`, 1 .. 9, then the block writer in piece mode
+extern "C" int fdh_launch_deflate_pieces(const uint8_t* in, const uint64_t* piece_off, const uint8_t* piece_last, uint8_t* out,
+                                         const uint64_t* out_off, uint32_t* out_len, uint32_t* piece_adler, uint64_t n, uint32_t level,
+                                         uint64_t total_in, hipStream_t stream) {
+    static const uint32_t kGreedy[] = {FDH_MODE_LEVEL1, FDH_MODE_LEVEL2, FDH_MODE_LEVEL3};
+    const fdh::LazyParams* lazy = fdh::lazy_params(level);
+    const GenMode* m = lazy ? &fdh::kLazyMode : level >= 1 && level <= 3 ? fdh::gen_mode(kGreedy[level - 1]) : nullptr;
+    fdh::GPieceWriteArgs pa{};
+    pa.last = piece_last;
+    pa.adler = piece_adler;
+    return launch_encoder(in, piece_off, out, out_off, out_len, n, m, lazy, total_in, stream, &pa);
 }

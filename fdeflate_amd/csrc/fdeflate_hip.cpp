@@ -556,8 +556,13 @@ uint64_t fdh_compress_bound(uint64_t len) { return len + len / 2 + 1024; }
 
 // fdh_deflate_general_batch (`lazy_level` 0: the FDH_MODE_* `mode`) and the lazy levels of fdh_deflate_level_batch
 // (`lazy_level` 4 .. 9, include/fdeflate_hip_levels.h): one contract, one body
+// (`pieces`, include/fdeflate_hip_pieces.h: the streams are pieces, `lazy_level` is the level, 1 .. 9)
+struct PieceMode {
+    const uint8_t* last;
+    uint32_t* adler;
+};
 static int general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint64_t n,
-                         uint32_t mode, uint32_t lazy_level, void* hip_stream) {
+                         uint32_t mode, uint32_t lazy_level, void* hip_stream, const PieceMode* pieces = nullptr) {
     if (n == 0) return FDH_SUCCESS;
     if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
     if (!out) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");  // (`in` may be null for a batch of empty inputs: below)
@@ -578,8 +583,9 @@ static int general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out
     // an empty input has a defined encoding (78 01 03 00 00 00 00 01), and a zero-element buffer has no address
     if (!in && total_in != 0) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");
     // the launcher (deflate_general.hip) plans the launch, keeps the workspace and has left the text of a failure
-    const int rc = lazy_level ? fdh_launch_deflate_level(in, in_off, out, out_off, out_len, n, lazy_level, total_in, stream)
-                              : fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, mode, total_in, stream);
+    const int rc = pieces       ? fdh_launch_deflate_pieces(in, in_off, pieces->last, out, out_off, out_len, pieces->adler, n, lazy_level, total_in, stream)
+                   : lazy_level ? fdh_launch_deflate_level(in, in_off, out, out_off, out_len, n, lazy_level, total_in, stream)
+                                : fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, mode, total_in, stream);
     return rc == 0 ? FDH_SUCCESS : hip_code(static_cast<hipError_t>(rc));
 }
 
@@ -623,6 +629,58 @@ uint64_t fdh_png_level_bound(uint64_t len, uint32_t level) {
 
 uint64_t fdh_png_level_file_bound(uint64_t rows, uint64_t row_bytes, uint32_t level, uint64_t prefix) {
     return level > 9 ? 0 : prefix + fdh_png_level_bound(rows * (row_bytes + 1), level) + FDH_PNG_FILE_SUFFIX;
+}
+
+// ---- long inputs in pieces (include/fdeflate_hip_pieces.h): deflate_general.hip in piece mode, deflate_stitch.hip ----
+static bool piece_bytes_ok(uint64_t piece_bytes) { return piece_bytes >= FDH_PIECE_BYTES_MIN && piece_bytes <= FDH_PIECE_BYTES_MAX; }
+
+// the one implementation behind the three host functions: the number of pieces and the stitched slot of `len` bytes
+static void pieces_of(uint64_t len, uint64_t piece_bytes, uint64_t* count, uint64_t* bound) {
+    const uint64_t full = len / piece_bytes, rest = len - full * piece_bytes;
+    *count = full + (rest || !full ? 1 : 0);
+    *bound = 2 + full * fdh_compress_bound(piece_bytes) + (rest || !full ? fdh_compress_bound(rest) : 0) + 4;
+}
+
+uint64_t fdh_deflate_pieces_count(uint64_t len, uint64_t piece_bytes) {
+    uint64_t count = 0, bound = 0;
+    if (piece_bytes_ok(piece_bytes)) pieces_of(len, piece_bytes, &count, &bound);
+    return count;
+}
+
+uint64_t fdh_deflate_pieces_bound(uint64_t len, uint32_t level, uint64_t piece_bytes) {
+    uint64_t count = 0, bound = 0;
+    if (level > 9 || !piece_bytes_ok(piece_bytes)) return 0;
+    if (level == 0) return fdh_stored_size(len);
+    pieces_of(len, piece_bytes, &count, &bound);
+    return bound;
+}
+
+uint64_t fdh_png_level_pieces_file_bound(uint64_t rows, uint64_t row_bytes, uint32_t level, uint64_t piece_bytes, uint64_t prefix) {
+    const uint64_t stream = fdh_deflate_pieces_bound(rows * (row_bytes + 1), level, piece_bytes);
+    return stream ? prefix + stream + FDH_PNG_FILE_SUFFIX : 0;
+}
+
+int fdh_deflate_level_pieces_batch(const uint8_t* raw, const uint64_t* piece_off, const uint8_t* piece_last, uint8_t* out,
+                                   const uint64_t* out_off, uint32_t* out_len, uint32_t* piece_adler, uint64_t n_pieces, uint32_t level,
+                                   void* hip_stream) {
+    if (level == 0 || level > 9) return fail(FDH_ERR_INVALID_ARGUMENT, "compression level outside 1 .. 9: piece mode exists at levels 1 .. 9");
+    if (n_pieces == 0) return FDH_SUCCESS;
+    if (!piece_last || !piece_adler) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
+    const PieceMode pieces{piece_last, piece_adler};
+    return general_batch(raw, piece_off, out, out_off, out_len, n_pieces, 0, level, hip_stream, &pieces);
+}
+
+int fdh_deflate_stitch_batch(const uint8_t* pieces, const uint64_t* piece_slot_off, const uint32_t* piece_len, uint32_t* piece_adler,
+                             const uint64_t* piece_off, const uint64_t* first_piece, uint8_t* out, const uint64_t* out_off,
+                             uint32_t* out_len, uint64_t n, void* hip_stream) {
+    if (n == 0) return FDH_SUCCESS;
+    if (pieces && pieces == out)
+        return fail(FDH_ERR_INVALID_ARGUMENT, "pieces and out are the same buffer: the piece slots are a scratch buffer of their own");
+    if (int rc = batch_ok({pieces, piece_slot_off, piece_len, piece_adler, piece_off, first_piece, out, out_off, out_len}, "null pointer", n,
+                          "streams"))
+        return rc;
+    return launched("stitch kernel launch", fdh_launch_deflate_stitch(pieces, piece_slot_off, piece_len, piece_adler, piece_off, first_piece,
+                    out, out_off, out_len, n, stream_of(hip_stream)));
 }
 
 // ---- single-buffer conveniences (host memory) --------------------------------------------

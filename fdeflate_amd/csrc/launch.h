@@ -14,6 +14,7 @@
 #include "../../include/fdeflate_hip_png16_encode.h"
 #include "../../include/fdeflate_hip_levels.h"
 #include "../../include/fdeflate_hip_png_levels.h"
+#include "../../include/fdeflate_hip_pieces.h"
 
 namespace fdh { struct SegArgs; }
 int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);  // inflate_seg3.hip, for inflate.hip
@@ -46,6 +47,14 @@ int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_
 // the same for a lazy level, 4 .. 9 (include/fdeflate_hip_levels.h): the parser kernel of deflate_lazy.h, the same block writer
 int fdh_launch_deflate_level(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
                              uint64_t n, uint32_t level, uint64_t total_in, hipStream_t stream);
+// the same in piece mode for a level 1 .. 9 (include/fdeflate_hip_pieces.h): stream k is a piece, raw deflate, closed by
+// the sync marker unless piece_last[k]; its Adler-32 goes to piece_adler[k]
+int fdh_launch_deflate_pieces(const uint8_t* in, const uint64_t* piece_off, const uint8_t* piece_last, uint8_t* out, const uint64_t* out_off,
+                              uint32_t* out_len, uint32_t* piece_adler, uint64_t n, uint32_t level, uint64_t total_in, hipStream_t stream);
+// deflate_stitch.hip (include/fdeflate_hip_pieces.h): the plan kernel and the copy kernel; enqueues only
+int fdh_launch_deflate_stitch(const uint8_t* pieces, const uint64_t* piece_slot_off, const uint32_t* piece_len, uint32_t* piece_adler,
+                              const uint64_t* piece_off, const uint64_t* first_piece, uint8_t* out, const uint64_t* out_off,
+                              uint32_t* out_len, uint64_t n, hipStream_t stream);
 // png_filter.hip
 int fdh_launch_png_unfilter(const uint8_t* filt, const uint64_t* filt_off, uint8_t* pix, const uint64_t* pix_off, uint32_t* status,
                             const uint32_t* gate, const uint32_t* gate_len, uint64_t n, uint32_t row_bytes, uint32_t bpp,

@@ -55,11 +55,13 @@ def png_filter_mixed_batch(pix, pix_off, types, types_off, filt, filt_off, info,
     return png_status
 
 
-def _file_sizes(level):
-    """The default file slots of a plan at `level`: prefix + level_bound(filtered size) + 16, 0 where the plan failed."""
+def _file_sizes(level, bound=None):
+    """The default file slots of a plan at `level`: prefix + level_bound(filtered size) + 16, 0 where the plan failed.
+    bound: the stream slot of a tensor of sizes where it is not level_bound's (fdeflate_amd.pieces)."""
     def sizes(pix_size, types_size, prefix, planned):
         import torch
-        size = prefix + level_bound(pix_size + types_size, level) + PNG_FILE_SUFFIX
+        stream = bound(pix_size + types_size) if bound else level_bound(pix_size + types_size, level)
+        size = prefix + stream + PNG_FILE_SUFFIX
         return torch.where(planned == 0, size, torch.zeros_like(size))
     return sizes
 
@@ -78,13 +80,14 @@ def _encoder_slots(file_off, prefix, status):
 
 
 def _behind_the_pixels(pix, pix_off, types, types_off, filt_off, total_filt, info, status, level, file, file_off, prefix,
-                       pal, colour, trns_len):
-    """Steps 2 .. 5 of every pipeline here: the filtered rows, the level encoder behind each prefix, the framing."""
+                       pal, colour, trns_len, encoder=None):
+    """Steps 2 .. 5 of every pipeline here: the filtered rows, the level encoder behind each prefix, the framing.
+    encoder: levels.deflate_level_batch, or a call with its first five parameters and its result (fdeflate_amd.pieces)."""
     import torch
     filt = torch.empty(max(1, total_filt), dtype=torch.uint8, device=pix.device)
     status = png_filter_mixed_batch(pix, pix_off, types, types_off, filt, filt_off, info, upstream=status,
                                     flags=PNG_FILTER_GIVEN_TYPES if types is not None else 0)
-    idat_len = levels.deflate_level_batch(filt, filt_off, file, _encoder_slots(file_off, prefix, status), level)
+    idat_len = (encoder or levels.deflate_level_batch)(filt, filt_off, file, _encoder_slots(file_off, prefix, status), level)
     status = torch.where((status == 0) & (idat_len == -1), torch.full_like(status, PNG_BAD_SIZES), status)
     idat_len = torch.where(status != 0, torch.zeros_like(idat_len), idat_len)     # (the framing then writes nothing)
     file_len, framed = api.png_frame_mixed_batch(file, file_off, idat_len, info, pal, colour, trns_len)
@@ -104,6 +107,12 @@ def png_encode_mixed_files_level_batch(pix, pix_off, info, level, pal=None, colo
     -> (file, file_off, file_len, png_status, info): png_status[i] the first that is not 0 of upstream, the plan (2, 3,
     10, 11), the filters (1, 2, 3), the encoder (2: the slot is too small) and the framing; a picture that fails gets
     file_len[i] = 0 and nothing is written to its slot.  ValueError for a level outside 0 .. 9, before any device work."""
+    return _files_level_pipeline(pix, pix_off, info, level, pal, colour, trns_len, upstream, types, types_off, file, file_off)
+
+
+def _files_level_pipeline(pix, pix_off, info, level, pal, colour, trns_len, upstream, types, types_off, file, file_off, bound=None,
+                          encoder=None):
+    """png_encode_mixed_files_level_batch, with the stream slots and the encoder of the caller where it names them."""
     import torch
     level = _level(level)
     n = pix_off.numel() - 1
@@ -121,7 +130,7 @@ def png_encode_mixed_files_level_batch(pix, pix_off, info, level, pal=None, colo
     if upstream is not None:
         planned = api._first(upstream, planned)
     filt_size = torch.where(planned == 0, pix_size + types_size, torch.zeros_like(pix_size))
-    file_size = _file_sizes(level)(pix_size, types_size, prefix, planned)
+    file_size = _file_sizes(level, bound)(pix_size, types_size, prefix, planned)
     offs = torch.zeros((2, n + 1), dtype=torch.int64, device=dev)
     torch.cumsum(torch.stack((filt_size, file_size)), 1, out=offs[:, 1:])
     total_filt, total_file = api._read_back(offs[:, n])                            # the one read-back: 16 bytes
@@ -133,14 +142,15 @@ def png_encode_mixed_files_level_batch(pix, pix_off, info, level, pal=None, colo
         planned = torch.where((planned == 0) & (slot < prefix + PNG_FILE_SUFFIX), torch.full_like(planned, PNG_BAD_SIZES), planned)
         prefix = torch.minimum(prefix, slot)
     file_len, status = _behind_the_pixels(pix, pix_off, types, types_off, offs[0], total_filt, info, planned, level, file, file_off,
-                                          prefix, pal, colour, trns_len)
+                                          prefix, pal, colour, trns_len, encoder)
     return file, file_off, file_len, status, info
 
 
-def _rgba_level_pipeline(pictures, pictures_off, width, height, level, allowed, pairs, file, file_off, analyse, plan, pack):
+def _rgba_level_pipeline(pictures, pictures_off, width, height, level, allowed, pairs, file, file_off, analyse, plan, pack,
+                         bound=None, encoder=None):
     level = _level(level)
     front = api._png_encode_mixed_front(pictures, pictures_off, width, height, allowed, pairs, file, file_off, analyse, plan, pack,
-                                        file_size=_file_sizes(level))
+                                        file_size=_file_sizes(level, bound))
     if len(front) == 5:
         return front
     pix, offs, total_types, file, file_off, prefix, status, info, pal, colour, trns_len = front
@@ -149,7 +159,7 @@ def _rgba_level_pipeline(pictures, pictures_off, width, height, level, allowed, 
     filt_off = offs[0] + offs[1]
     total_filt = pix.numel() + total_types if total_types else 0
     file_len, status = _behind_the_pixels(pix, offs[0], None, None, filt_off, total_filt, info, status, level, file, file_off, prefix,
-                                          pal, colour, trns_len)
+                                          pal, colour, trns_len, encoder)
     return file, file_off, file_len, status, info
 
 
