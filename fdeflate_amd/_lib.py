@@ -108,27 +108,19 @@ PNG16_ENCODE_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for na
     "fdh_png_encode16_plan_batch": "int 4 4 4 4 4 u32 8 8 8 8 4 u64 stream",
     "fdh_png_pack16_mixed_batch": "int 1 8 1 8 4 4 4 4 4 u64 stream",
 }.items()}
-# Every table by the header that declares its symbols: signature() and lib() walk this.
-TABLES = {"fdeflate_hip.h": SIGNATURES, "fdeflate_hip_png16.h": EXTENSION_SIGNATURES,
-          "fdeflate_hip_png16_encode.h": PNG16_ENCODE_SIGNATURES}
-
-# include/fdeflate_hip_levels.h, the calls behind fdeflate_amd.levels (tests/test_abi_levels.py compares).  Not a key of
-# TABLES: a merged test (tests/test_abi_png16_encode.py) pins that dict at exactly the three headers above, so this
-# table stands beside it and signature() and lib() walk _ALL_TABLES.
+# include/fdeflate_hip_levels.h, the calls behind fdeflate_amd.levels (tests/test_abi_levels.py compares).
 LEVELS_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
     "fdh_deflate_level_batch": "int 1 8 1 8 4 u64 u32 stream",
     "fdh_compress_to_vec_level": "int host size u32 host host",
     "fdh_debug_level_plan": "int u64 int u32 host",
 }.items()}
-# include/fdeflate_hip_png_levels.h, the calls behind fdeflate_amd.png_levels (tests/test_abi_png_levels.py compares):
-# beside TABLES for the same reason.
+# include/fdeflate_hip_png_levels.h, the calls behind fdeflate_amd.png_levels (tests/test_abi_png_levels.py compares).
 PNG_LEVELS_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
     "fdh_png_filter_mixed_batch": "int 1 8 1 8 1 8 4 4 u32 4 u64 stream",
     "fdh_png_level_bound": "u64 u64 u32",
     "fdh_png_level_file_bound": "u64 u64 u64 u32 u64",
 }.items()}
-# include/fdeflate_hip_pieces.h, the calls behind fdeflate_amd.pieces (tests/test_abi_pieces.py compares): beside TABLES
-# for the same reason.
+# include/fdeflate_hip_pieces.h, the calls behind fdeflate_amd.pieces (tests/test_abi_pieces.py compares).
 PIECES_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, sig in {
     "fdh_deflate_level_pieces_batch": "int 1 8 1 1 8 4 4 u64 u32 stream",
     "fdh_deflate_stitch_batch": "int 1 8 4 4 8 8 1 8 4 u64 stream",
@@ -136,12 +128,16 @@ PIECES_SIGNATURES = {name: (sig.split()[0], tuple(sig.split()[1:])) for name, si
     "fdh_deflate_pieces_bound": "u64 u64 u32 u64",
     "fdh_png_level_pieces_file_bound": "u64 u64 u64 u32 u64 u64",
 }.items()}
-_ALL_TABLES = (*TABLES.values(), LEVELS_SIGNATURES, PNG_LEVELS_SIGNATURES, PIECES_SIGNATURES)
+# Every table by the header that declares its symbols, in the order the headers were added: signature() and lib() walk
+# this (tests/test_abi.py holds it to include/).
+TABLES = {"fdeflate_hip.h": SIGNATURES, "fdeflate_hip_png16.h": EXTENSION_SIGNATURES,
+          "fdeflate_hip_png16_encode.h": PNG16_ENCODE_SIGNATURES, "fdeflate_hip_levels.h": LEVELS_SIGNATURES,
+          "fdeflate_hip_png_levels.h": PNG_LEVELS_SIGNATURES, "fdeflate_hip_pieces.h": PIECES_SIGNATURES}
 
 
 def signature(symbol):
     """(result, parameters) of a symbol of any table."""
-    for table in _ALL_TABLES:
+    for table in TABLES.values():
         if symbol in table:
             return table[symbol]
     raise KeyError(symbol)
@@ -156,7 +152,7 @@ def lib():
             "%s is missing: the HIP extension has not been built (make -C fdeflate_amd/csrc); "
             "fdeflate_amd has no CPU fallback" % SO_PATH)
     L = C.CDLL(SO_PATH)
-    for table in _ALL_TABLES:
+    for table in TABLES.values():
         for name, (result, params) in table.items():
             fn = getattr(L, name)
             fn.restype = _CTYPES[result]

@@ -1500,11 +1500,13 @@ extern "C" int fdh_debug_gen_timers(uint64_t* host /* 8 x 32768 */) {
 // ---- the launch: plan, per-device workspace, the two kernels ----
 namespace {
 
-using fdh::GenMode;
+using fdh::EncoderRow;
+using fdh::Parser;
 
-static_assert(fdh::kGenModes[FDH_MODE_LEVEL1 - 1].table_bytes == fdh::kGHashSize * 4 &&
-              fdh::kGenModes[FDH_MODE_LEVEL2 - 1].table_bytes == (fdh::kGHashSize + fdh::kGWindow) * 4, "launch.h's table sizes");
-static_assert(fdh::kLazyMode.table_bytes == (2 * fdh::kGHashSize + fdh::kGWindow) * 4, "launch.h's table sizes");
+static_assert(fdh::kEncoders[1].table_bytes == fdh::kGHashSize * 4 && fdh::kEncoders[2].table_bytes == (fdh::kGHashSize + fdh::kGWindow) * 4 &&
+              fdh::kEncoders[3].table_bytes == fdh::kEncoders[2].table_bytes, "launch.h's table sizes");
+static_assert(fdh::kEncoders[4].table_bytes == (2 * fdh::kGHashSize + fdh::kGWindow) * 4 && fdh::kEncoders[0].table_bytes == 0,
+              "launch.h's table sizes");
 
 // The parser runs one stream per lane and is bound by the latency of dependent loads: what helps is wavefronts in
 // flight.  A batch that does not fill the device with full wavefronts is given fewer lanes per wavefront and more
@@ -1523,27 +1525,27 @@ static_assert(fdh::kLazyMode.table_bytes == (2 * fdh::kGHashSize + fdh::kGWindow
 struct GenPlan {
     unsigned lanes, waves;  // streams per wavefront of the parser, wavefronts
 };
-GenPlan general_plan(uint64_t n, int cus, const GenMode& m) {
+GenPlan general_plan(uint64_t n, int cus, const EncoderRow& m) {
     unsigned lanes = 64;
     const uint64_t want_waves = (uint64_t)cus * m.waves_per_cu;
     while (lanes > 4 && (n + lanes - 1) / lanes < want_waves) lanes /= 2;
     if (const int v = fdh::env_int("FDH_GEN_LANES", 0); v >= 1 && v <= 64) lanes = (unsigned)v;
     uint64_t max_resident = m.max_resident;
     if (const int v = fdh::env_int("FDH_GEN_RESIDENT", 0); v >= 64 && v <= (1 << 20))
-        max_resident = m.chain ? std::min<uint64_t>((uint64_t)v, m.max_resident) : (uint64_t)v;
+        max_resident = m.parser == Parser::kHashTable ? (uint64_t)v : std::min<uint64_t>((uint64_t)v, m.max_resident);  // (RLE: no cap to keep)
     return {lanes, (unsigned)std::min<uint64_t>((n + lanes - 1) / lanes, std::max<uint64_t>(1, max_resident / lanes))};
 }
 
 // per-device workspace, grown on demand, never shrunk
 struct GenWork {
     std::mutex mutex;         // the workspace is shared by the calls on ITS device only
-    void* hash = nullptr;     // the resident lanes' tables (GenMode::table_bytes each)
+    void* hash = nullptr;     // the resident lanes' tables (EncoderRow::table_bytes each)
     void* matches = nullptr;  // what the parser hands to the block writer, sliced per stream
     void* blocks = nullptr;
     void* nblocks = nullptr;
     size_t hash_bytes = 0, match_bytes = 0, block_bytes = 0, nblock_bytes = 0;
 };
-GenWork g_gen_work[64];
+GenWork g_gen_work[fdh::kMaxDevices];
 
 hipError_t failed(hipError_t e, const char* what) {
     fdh_set_last_error((std::string(what) + ": " + hipGetErrorString(e)).c_str());
@@ -1565,47 +1567,43 @@ hipError_t grow(void** p, size_t* have, size_t want, const char* what, bool head
     return hipSuccess;
 }
 
+// what general_plan gives a batch of n streams on a device of `cus` CUs: out = {lanes, waves}; needs no device
+int debug_plan(uint64_t n, int cus, const EncoderRow* row, uint32_t* out) {
+    if (!row || !out || n == 0) return -1;
+    const GenPlan p = general_plan(n, cus, *row);
+    out[0] = p.lanes;
+    out[1] = p.waves;
+    return 0;
+}
+
 }  // namespace
 
-// what general_plan gives a batch of n streams on a device of `cus` CUs: out = {lanes, waves}; needs no device
+// ... of an FDH_MODE_*, and of a lazy level, 4 .. 9 (include/fdeflate_hip_levels.h)
 extern "C" int fdh_debug_general_plan(uint64_t n, int cus, uint32_t mode, uint32_t* out) {
-    const GenMode* m = fdh::gen_mode(mode);
-    if (!m || !out || n == 0) return -1;
-    const GenPlan p = general_plan(n, cus, *m);
-    out[0] = p.lanes;
-    out[1] = p.waves;
-    return 0;
+    return debug_plan(n, cus, fdh::encoder_of_mode(mode), out);
 }
-
-// what general_plan gives a lazy level, 4 .. 9 (include/fdeflate_hip_levels.h)
 extern "C" int fdh_debug_level_plan(uint64_t n, int cus, uint32_t level, uint32_t* out) {
-    if (!fdh::lazy_params(level) || !out || n == 0) return -1;
-    const GenPlan p = general_plan(n, cus, fdh::kLazyMode);
-    out[0] = p.lanes;
-    out[1] = p.waves;
-    return 0;
+    return debug_plan(n, cus, level >= 4 ? fdh::encoder_of_level(level) : nullptr, out);
 }
 
-// Both launchers: the parser of the mode `m` -- with `lazy`, the lazy parser of kLazyMode with these parameters -- then
-// the block writer.
-static int launch_encoder(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint64_t n,
-                          const GenMode* m, const fdh::LazyParams* lazy, uint64_t total_in, hipStream_t stream,
-                          const fdh::GPieceWriteArgs* pieces = nullptr) {
+extern "C" int fdh_launch_deflate_encoder(const uint8_t* in, const uint64_t* in_off, const uint8_t* piece_last, uint8_t* out,
+                                          const uint64_t* out_off, uint32_t* out_len, uint32_t* piece_adler, uint64_t n,
+                                          const EncoderRow* row, uint64_t total_in, hipStream_t stream) {
     if (n == 0) return 0;
-    if (!m) return -1;
+    if (!row) return -1;
     int dev = 0, cus = 0;
     if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return (int)failed(e, "hipGetDevice(&dev)");
-    if (dev < 0 || dev >= 64) return (int)failed(hipErrorInvalidDevice, "general encoder: device ordinal out of range");
+    if (!fdh::device_ordinal_ok(dev)) return (int)failed(hipErrorInvalidDevice, "general encoder: device ordinal out of range");
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    GenPlan plan = general_plan(n, cus, *m);
+    GenPlan plan = general_plan(n, cus, *row);
     GenWork& w = g_gen_work[dev];
     std::lock_guard<std::mutex> lock(w.mutex);
     hipError_t e = hipSuccess;
-    if (!m->rle) {
+    if (row->parser != Parser::kRle) {
         // exactly the resident lanes' tables (no headroom: at the cap that is the whole 16 GiB); on a smaller or busy
         // device the batch runs with fewer resident wavefronts instead of failing
         for (;;) {
-            e = grow(&w.hash, &w.hash_bytes, (size_t)plan.waves * plan.lanes * m->table_bytes, "hipMalloc(hash tables)", false);
+            e = grow(&w.hash, &w.hash_bytes, (size_t)plan.waves * plan.lanes * row->table_bytes, "hipMalloc(hash tables)", false);
             if (e == hipSuccess || plan.waves <= 1) break;
             (void)hipGetLastError();
             plan.waves /= 2;
@@ -1623,19 +1621,18 @@ static int launch_encoder(const uint8_t* in, const uint64_t* in_off, uint8_t* ou
     fdh::GParseArgs p{in, in_off, n, static_cast<uint32_t*>(w.hash), static_cast<fdh::GMatchRec*>(w.matches),
                       static_cast<fdh::GBlockRec*>(w.blocks), nblocks, plan.lanes};
     const dim3 grid(plan.waves), block(fdh::kWave);
-    if (lazy)
-        hipLaunchKernelGGL(fdh::deflate_lazy_parse_kernel, grid, block, 0, stream, p, *lazy);
-    else if (m->rle)
-        hipLaunchKernelGGL(fdh::deflate_parse_kernel<true>, grid, block, 0, stream, p);
-    else if (m->chain == 2)
-        hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 2>), grid, block, 0, stream, p);
-    else if (m->chain == 3)
-        hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 3>), grid, block, 0, stream, p);
-    else
-        hipLaunchKernelGGL(fdh::deflate_parse_kernel<false>, grid, block, 0, stream, p);
+    switch (row->parser) {
+        case Parser::kLazy: hipLaunchKernelGGL(fdh::deflate_lazy_parse_kernel, grid, block, 0, stream, p, row->lazy); break;
+        case Parser::kRle: hipLaunchKernelGGL(fdh::deflate_parse_kernel<true>, grid, block, 0, stream, p); break;
+        case Parser::kChain2: hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 2>), grid, block, 0, stream, p); break;
+        case Parser::kChain3: hipLaunchKernelGGL((fdh::deflate_parse_kernel<false, 3>), grid, block, 0, stream, p); break;
+        case Parser::kHashTable: hipLaunchKernelGGL(fdh::deflate_parse_kernel<false>, grid, block, 0, stream, p); break;
+    }
     fdh::GWriteArgs wa{in, in_off, out, out_off, out_len, n, p.matches, p.blocks, nblocks};
-    if (pieces) {
-        fdh::GPieceWriteArgs pw = *pieces;
+    if (piece_last) {
+        fdh::GPieceWriteArgs pw{};
+        pw.last = piece_last;
+        pw.adler = piece_adler;
         static_cast<fdh::GWriteArgs&>(pw) = wa;
         hipLaunchKernelGGL(fdh::deflate_write_kernel<fdh::GPieceWriteArgs>, dim3((unsigned)n), block, 0, stream, pw);
     } else {
@@ -1647,26 +1644,3 @@ static int launch_encoder(const uint8_t* in, const uint64_t* in_off, uint8_t* ou
     return 0;
 }
 
-extern "C" int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                                          uint32_t* out_len, uint64_t n, uint32_t mode, uint64_t total_in, hipStream_t stream) {
-    return launch_encoder(in, in_off, out, out_off, out_len, n, fdh::gen_mode(mode), nullptr, total_in, stream);
-}
-
-extern "C" int fdh_launch_deflate_level(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
-                                        uint32_t* out_len, uint64_t n, uint32_t level, uint64_t total_in, hipStream_t stream) {
-    const fdh::LazyParams* lazy = fdh::lazy_params(level);
-    return launch_encoder(in, in_off, out, out_off, out_len, n, lazy ? &fdh::kLazyMode : nullptr, lazy, total_in, stream);
-}
-
-// include/fdeflate_hip_pieces.h: the parser of `level`, 1 .. 9, then the block writer in piece mode
-extern "C" int fdh_launch_deflate_pieces(const uint8_t* in, const uint64_t* piece_off, const uint8_t* piece_last, uint8_t* out,
-                                         const uint64_t* out_off, uint32_t* out_len, uint32_t* piece_adler, uint64_t n, uint32_t level,
-                                         uint64_t total_in, hipStream_t stream) {
-    static const uint32_t kGreedy[] = {FDH_MODE_LEVEL1, FDH_MODE_LEVEL2, FDH_MODE_LEVEL3};
-    const fdh::LazyParams* lazy = fdh::lazy_params(level);
-    const GenMode* m = lazy ? &fdh::kLazyMode : level >= 1 && level <= 3 ? fdh::gen_mode(kGreedy[level - 1]) : nullptr;
-    fdh::GPieceWriteArgs pa{};
-    pa.last = piece_last;
-    pa.adler = piece_adler;
-    return launch_encoder(in, piece_off, out, out_off, out_len, n, m, lazy, total_in, stream, &pa);
-}

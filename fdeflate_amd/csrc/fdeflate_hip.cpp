@@ -53,12 +53,18 @@ hipStream_t stream_of(void* hip_stream) { return static_cast<hipStream_t>(hip_st
 
 // The shared decode tables of the ultra-fast prefix are built on the device once per device.
 std::mutex g_canon_mutex;
-bool g_canon_ready[64] = {};
+bool g_canon_ready[fdh::kMaxDevices] = {};
+
+// the current device, where the per-device arrays have a slot for it
+int device_slot(int& dev) {
+    HIP_TRY(hipGetDevice(&dev));
+    if (!fdh::device_ordinal_ok(dev)) return fail(FDH_ERR_INVALID_ARGUMENT, "device ordinal out of range");
+    return FDH_SUCCESS;
+}
 
 int ensure_canon_tables(hipStream_t stream) {
     int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(FDH_ERR_INVALID_ARGUMENT, "device ordinal out of range");
+    if (int rc = device_slot(dev)) return rc;
     std::lock_guard<std::mutex> lock(g_canon_mutex);
     if (g_canon_ready[dev]) return FDH_SUCCESS;
     uint32_t st = 0xFFFFFFFFu;
@@ -554,25 +560,24 @@ int fdh_png_frame_mixed_batch(uint8_t* file, const uint64_t* file_off, const uin
 
 uint64_t fdh_compress_bound(uint64_t len) { return len + len / 2 + 1024; }
 
-// fdh_deflate_general_batch (`lazy_level` 0: the FDH_MODE_* `mode`) and the lazy levels of fdh_deflate_level_batch
-// (`lazy_level` 4 .. 9, include/fdeflate_hip_levels.h): one contract, one body
-// (`pieces`, include/fdeflate_hip_pieces.h: the streams are pieces, `lazy_level` is the level, 1 .. 9)
+// fdh_deflate_general_batch, fdh_deflate_level_batch at levels 1 .. 9 and fdh_deflate_level_pieces_batch: one contract,
+// one body.  Each resolves its mode or level to a row of launch.h's kEncoders (`row` null: a number that is none);
+// with `pieces` (include/fdeflate_hip_pieces.h) the streams are pieces.
 struct PieceMode {
     const uint8_t* last;
     uint32_t* adler;
 };
 static int general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len, uint64_t n,
-                         uint32_t mode, uint32_t lazy_level, void* hip_stream, const PieceMode* pieces = nullptr) {
+                         const fdh::EncoderRow* row, void* hip_stream, PieceMode pieces = {nullptr, nullptr}) {
     if (n == 0) return FDH_SUCCESS;
     if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
     if (!out) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");  // (`in` may be null for a batch of empty inputs: below)
-    if (!lazy_level && !fdh::gen_mode(mode)) return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
+    if (!row) return fail(FDH_ERR_INVALID_ARGUMENT, "unknown encoder mode");
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call");
     if (!have_device()) return no_device();
     hipStream_t stream = stream_of(hip_stream);
     int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(FDH_ERR_INVALID_ARGUMENT, "device ordinal out of range");
+    if (int rc = device_slot(dev)) return rc;
     // the launcher sizes its record arrays by the bytes the batch spans
     uint64_t ends[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(&ends[0], in_off, 8, hipMemcpyDeviceToHost, stream));
@@ -583,30 +588,28 @@ static int general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out
     // an empty input has a defined encoding (78 01 03 00 00 00 00 01), and a zero-element buffer has no address
     if (!in && total_in != 0) return fail(FDH_ERR_INVALID_ARGUMENT, "null data pointer");
     // the launcher (deflate_general.hip) plans the launch, keeps the workspace and has left the text of a failure
-    const int rc = pieces       ? fdh_launch_deflate_pieces(in, in_off, pieces->last, out, out_off, out_len, pieces->adler, n, lazy_level, total_in, stream)
-                   : lazy_level ? fdh_launch_deflate_level(in, in_off, out, out_off, out_len, n, lazy_level, total_in, stream)
-                                : fdh_launch_deflate_general(in, in_off, out, out_off, out_len, n, mode, total_in, stream);
+    const int rc = fdh_launch_deflate_encoder(in, in_off, pieces.last, out, out_off, out_len, pieces.adler, n, row, total_in, stream);
     return rc == 0 ? FDH_SUCCESS : hip_code(static_cast<hipError_t>(rc));
 }
 
 int fdh_deflate_general_batch(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off,
                               uint32_t* out_len, uint64_t n, uint32_t mode, void* hip_stream) {
-    return general_batch(in, in_off, out, out_off, out_len, n, mode, 0, hip_stream);
+    return general_batch(in, in_off, out, out_off, out_len, n, fdh::encoder_of_mode(mode), hip_stream);
 }
 
-// include/fdeflate_hip_levels.h: levels 0-3 are the calls above, 4-9 the lazy parser
-static const uint32_t kLevelModes[] = {0, FDH_MODE_LEVEL1, FDH_MODE_LEVEL2, FDH_MODE_LEVEL3};
+// include/fdeflate_hip_levels.h: level 0 is the stored encoder, 1 .. 9 are rows
 static int bad_level() { return fail(FDH_ERR_INVALID_ARGUMENT, "compression level above 9: levels 0 .. 9 exist"); }
 
 int fdh_deflate_level_batch(const uint8_t* raw, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
                             uint64_t n, uint32_t level, void* hip_stream) {
     if (level > 9) return bad_level();
     if (n == 0) return FDH_SUCCESS;
+    // This door's own order and, at level 0, its own texts: the count is refused before a null `out` is (general_batch has
+    // them the other way round) and in general_batch's words, not in the stored call's (tests/test_abi_levels.py).
     if (!in_off || !out_off || !out_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
     if (n > 0x7FFFFFFFull) return fail(FDH_ERR_INVALID_ARGUMENT, "too many streams in one call");
     if (level == 0) return fdh_deflate_stored_batch(raw, in_off, out, out_off, out_len, n, hip_stream);
-    return level <= 3 ? general_batch(raw, in_off, out, out_off, out_len, n, kLevelModes[level], 0, hip_stream)
-                      : general_batch(raw, in_off, out, out_off, out_len, n, 0, level, hip_stream);
+    return general_batch(raw, in_off, out, out_off, out_len, n, fdh::encoder_of_level(level), hip_stream);
 }
 
 // ---- PNG encode at a compression level (include/fdeflate_hip_png_levels.h): png_filter_mixed.hip ----
@@ -666,8 +669,7 @@ int fdh_deflate_level_pieces_batch(const uint8_t* raw, const uint64_t* piece_off
     if (level == 0 || level > 9) return fail(FDH_ERR_INVALID_ARGUMENT, "compression level outside 1 .. 9: piece mode exists at levels 1 .. 9");
     if (n_pieces == 0) return FDH_SUCCESS;
     if (!piece_last || !piece_adler) return fail(FDH_ERR_INVALID_ARGUMENT, "null metadata pointer");
-    const PieceMode pieces{piece_last, piece_adler};
-    return general_batch(raw, piece_off, out, out_off, out_len, n_pieces, 0, level, hip_stream, &pieces);
+    return general_batch(raw, piece_off, out, out_off, out_len, n_pieces, fdh::encoder_of_level(level), hip_stream, {piece_last, piece_adler});
 }
 
 int fdh_deflate_stitch_batch(const uint8_t* pieces, const uint64_t* piece_slot_off, const uint32_t* piece_len, uint32_t* piece_adler,
@@ -758,11 +760,12 @@ int fdh_decompress_to_vec(const uint8_t* input, size_t input_len, uint8_t** outp
     return inflate_growing(input, input_len, 0xFFFFFFF0ull, output, output_len, stream_status);
 }
 
-// which encoder a host call runs: the ultra-fast one, the stored one, or the general one in an FDH_MODE_*
+// which encoder a host call runs: the ultra-fast one, the stored one, or the general one in a row of launch.h's kEncoders
 struct Encoder {
-    enum Type { kUltraFast, kStored, kGeneral, kLazy } type;
-    uint32_t mode = 0;  // kLazy: the level, 4 .. 9 (include/fdeflate_hip_levels.h)
+    enum Type { kUltraFast, kStored, kGeneral } type;
+    const fdh::EncoderRow* row = nullptr;  // kGeneral
 };
+static Encoder encoder_of_level(uint32_t level) { return level ? Encoder{Encoder::kGeneral, fdh::encoder_of_level(level)} : Encoder{Encoder::kStored}; }
 
 static int compress_one(Encoder enc, const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
     if (!output || !output_len) return fail(FDH_ERR_INVALID_ARGUMENT, "null result pointer");
@@ -782,8 +785,7 @@ static int compress_one(Encoder enc, const uint8_t* input, size_t input_len, uin
     uint32_t* res = reinterpret_cast<uint32_t*>(m + 4);
     int rc = enc.type == Encoder::kStored      ? fdh_deflate_stored_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
              : enc.type == Encoder::kUltraFast ? fdh_deflate_ultrafast_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, nullptr)
-             : enc.type == Encoder::kLazy      ? fdh_deflate_level_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, enc.mode, nullptr)
-                                               : fdh_deflate_general_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, enc.mode, nullptr);
+                                               : general_batch(d_in.as<uint8_t>(), m, d_out.as<uint8_t>(), m + 2, res, 1, enc.row, nullptr);
     if (rc != FDH_SUCCESS) return rc;
     HIP_TRY(hipDeviceSynchronize());
     uint32_t n32 = 0;
@@ -812,27 +814,24 @@ int fdh_compress_to_vec_stored(const uint8_t* input, size_t input_len, uint8_t**
 }
 
 int fdh_compress_to_vec(const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
-    return compress_one({Encoder::kGeneral, FDH_MODE_LEVEL1}, input, input_len, output, output_len);
+    return compress_one({Encoder::kGeneral, fdh::encoder_of_mode(FDH_MODE_LEVEL1)}, input, input_len, output, output_len);
 }
 
 int fdh_compress_to_vec_rle(const uint8_t* input, size_t input_len, uint8_t** output, size_t* output_len) {
-    return compress_one({Encoder::kGeneral, FDH_MODE_RLE}, input, input_len, output, output_len);
+    return compress_one({Encoder::kGeneral, fdh::encoder_of_mode(FDH_MODE_RLE)}, input, input_len, output, output_len);
 }
 
 int fdh_compress_to_vec_with_level(const uint8_t* input, size_t input_len, uint32_t level, uint8_t** output,
                                    size_t* output_len) {
-    static const Encoder kLevels[] = {{Encoder::kStored}, {Encoder::kGeneral, FDH_MODE_LEVEL1}, {Encoder::kGeneral, FDH_MODE_LEVEL2},
-                                      {Encoder::kGeneral, FDH_MODE_LEVEL3}};
     if (level > 3)
         return fail(FDH_ERR_INVALID_ARGUMENT, "compression level not provided by this call: levels 0, 1, 2 and 3 are (4-9, the lazy parser: "
                                               "fdh_compress_to_vec_level of fdeflate_hip_levels.h)");
-    return compress_one(kLevels[level], input, input_len, output, output_len);
+    return compress_one(encoder_of_level(level), input, input_len, output, output_len);
 }
 
 int fdh_compress_to_vec_level(const uint8_t* input, size_t input_len, uint32_t level, uint8_t** output, size_t* output_len) {
     if (level > 9) return bad_level();
-    if (level <= 3) return fdh_compress_to_vec_with_level(input, input_len, level, output, output_len);
-    return compress_one({Encoder::kLazy, level}, input, input_len, output, output_len);
+    return compress_one(encoder_of_level(level), input, input_len, output, output_len);
 }
 
 void fdh_free(void* p) { std::free(p); }

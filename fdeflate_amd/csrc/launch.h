@@ -16,7 +16,7 @@
 #include "../../include/fdeflate_hip_png_levels.h"
 #include "../../include/fdeflate_hip_pieces.h"
 
-namespace fdh { struct SegArgs; }
+namespace fdh { struct SegArgs; struct EncoderRow; }
 int fdh_launch_seg3(const fdh::SegArgs& sa, unsigned blocks, hipStream_t stream);  // inflate_seg3.hip, for inflate.hip
 
 extern "C" {
@@ -40,17 +40,14 @@ int fdh_launch_png_filter_deflate_ultrafast(const uint8_t* pix, const uint64_t* 
 int fdh_launch_png_filter_deflate_ultrafast_mixed(const uint8_t* pix, const uint64_t* pix_off, const uint8_t* types, const uint64_t* types_off,
                                                   uint8_t* out, const uint64_t* out_off, uint32_t* out_len, const fdh_png_info* info,
                                                   const uint32_t* upstream, uint32_t* png_status, uint64_t n, hipStream_t stream);
-// deflate_general.hip: `mode` is an FDH_MODE_*, `total_in` = in_off[n] - in_off[0].  Plans the launch, grows the device's
-// workspace, and returns when both kernels have finished; on failure fdh_last_error's text names the step that failed.
-int fdh_launch_deflate_general(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
-                               uint64_t n, uint32_t mode, uint64_t total_in, hipStream_t stream);
-// the same for a lazy level, 4 .. 9 (include/fdeflate_hip_levels.h): the parser kernel of deflate_lazy.h, the same block writer
-int fdh_launch_deflate_level(const uint8_t* in, const uint64_t* in_off, uint8_t* out, const uint64_t* out_off, uint32_t* out_len,
-                             uint64_t n, uint32_t level, uint64_t total_in, hipStream_t stream);
-// the same in piece mode for a level 1 .. 9 (include/fdeflate_hip_pieces.h): stream k is a piece, raw deflate, closed by
-// the sync marker unless piece_last[k]; its Adler-32 goes to piece_adler[k]
-int fdh_launch_deflate_pieces(const uint8_t* in, const uint64_t* piece_off, const uint8_t* piece_last, uint8_t* out, const uint64_t* out_off,
-                              uint32_t* out_len, uint32_t* piece_adler, uint64_t n, uint32_t level, uint64_t total_in, hipStream_t stream);
+// deflate_general.hip: the parser of `row` (a row of kEncoders below), then the block writer; `total_in` = in_off[n] -
+// in_off[0].  Plans the launch, grows the device's workspace, and returns when both kernels have finished; on failure
+// fdh_last_error's text names the step that failed.  With `piece_last` and `piece_adler` (both, or both null for whole
+// streams; include/fdeflate_hip_pieces.h) stream k is a piece: raw deflate, closed by the sync marker unless
+// piece_last[k], its Adler-32 written to piece_adler[k].
+int fdh_launch_deflate_encoder(const uint8_t* in, const uint64_t* in_off, const uint8_t* piece_last, uint8_t* out, const uint64_t* out_off,
+                               uint32_t* out_len, uint32_t* piece_adler, uint64_t n, const fdh::EncoderRow* row, uint64_t total_in,
+                               hipStream_t stream);
 // deflate_stitch.hip (include/fdeflate_hip_pieces.h): the plan kernel and the copy kernel; enqueues only
 int fdh_launch_deflate_stitch(const uint8_t* pieces, const uint64_t* piece_slot_off, const uint32_t* piece_len, uint32_t* piece_adler,
                               const uint64_t* piece_off, const uint64_t* first_piece, uint8_t* out, const uint64_t* out_off,
@@ -153,35 +150,52 @@ inline int env_int(const char* name, int fallback) {
     return e ? std::atoi(e) : fallback;
 }
 
-// The general encoder's modes, by FDH_MODE_* (gen_mode: nullptr for any other number).
-struct GenMode {
-    bool rle;               // RleParser: runs only, no match finder and no tables
-    int chain;              // 0: HashTableMatchFinder; 2 / 3: the level whose HashChainMatchFinder the parser uses; 4: kLazyMode
-    uint64_t table_bytes;   // per resident stream: a 64 Ki-entry table, at levels 2 and 3 also a 32 Ki-entry link ring
-    unsigned waves_per_cu;  // the parser's wavefronts wanted per CU before a wavefront is given more streams
-    uint64_t max_resident;  // streams in flight: 16 GiB of tables at the most
+// The encoders of deflate_general.hip, one row per parser configuration: everything the public calls, the launcher and
+// the parser kernel need to know about it.
+enum class Parser {
+    kRle,        // RleParser: runs only, no match finder and no tables
+    kHashTable,  // the greedy parser with the HashTableMatchFinder
+    kChain2,     // ... with the HashChainMatchFinder of level 2
+    kChain3,     // ... and of level 3
+    kLazy,       // deflate_lazy.h: LazyParser with the HybridMatchFinder
 };
-constexpr GenMode gen_mode_of(bool rle, int chain) {
-    const uint64_t table_bytes = rle ? 0 : (65536u + (chain ? 32768u : 0u)) * 4;
-    return {rle, chain, table_bytes, !rle && !chain ? 8u : 16u, rle ? 1ull << 40 : (16ull << 30) / table_bytes};
-}
-constexpr GenMode kGenModes[] = {gen_mode_of(false, 0), gen_mode_of(true, 0), gen_mode_of(false, 2), gen_mode_of(false, 3)};
-static_assert(FDH_MODE_LEVEL1 == 1 && FDH_MODE_RLE == 2 && FDH_MODE_LEVEL2 == 3 && FDH_MODE_LEVEL3 == 4, "kGenModes' order");
-inline const GenMode* gen_mode(uint32_t mode) { return mode >= 1 && mode <= 4 ? &kGenModes[mode - 1] : nullptr; }
-
-// Levels 4-9 (include/fdeflate_hip_levels.h) are no FDH_MODE_*: a table beside kGenModes.  One launch class -- the
-// HybridMatchFinder's two 64 Ki-entry tables and its 32 Ki-entry link ring, 640 KiB per resident stream, 26 214 of them
-// under the 16 GiB; wavefronts wanted as for the chain parsers -- and the parameters of the level, which the parser
-// kernel takes as arguments (compress/mod.rs:80-87: LazyParser::new(skip_ahead_shift, max_lazy,
-// HybridMatchFinder::new(min_match, search_depth, nice_length)); `7.. =>` is one set).
-constexpr uint64_t kLazyTableBytes = (2 * 65536u + 32768u) * 4;
-constexpr GenMode kLazyMode = {false, 4 /* neither chain level: the hybrid finder */, kLazyTableBytes, 16u, (16ull << 30) / kLazyTableBytes};
-static_assert(kLazyMode.max_resident == 26214, "16 GiB / 640 KiB");
+// The lazy parser's parameters, which its kernel takes as arguments (compress/mod.rs:80-87: LazyParser::new(
+// skip_ahead_shift, max_lazy, HybridMatchFinder::new(min_match, search_depth, nice_length)); `7.. =>` is one set).
 struct LazyParams {
     uint32_t shift, max_lazy, min_match, depth, nice;
 };
-constexpr LazyParams kLazyParams[] = {{9, 12, 5, 16, 32}, {9, 16, 5, 64, 64}, {9, 16, 4, 128, 128}, {12, 256, 4, 256, 258}};
-inline const LazyParams* lazy_params(uint32_t level) { return level >= 4 && level <= 9 ? &kLazyParams[level < 7 ? level - 4 : 3] : nullptr; }
+struct EncoderRow {
+    Parser parser;
+    uint64_t table_bytes;   // per resident stream: 64 Ki-entry tables (none, one, one, one, two) and, but for the hash-table
+                            // finder, a 32 Ki-entry link ring: 0, 256, 384, 384, 640 KiB
+    unsigned waves_per_cu;  // the parser's wavefronts wanted per CU before a wavefront is given more streams
+    uint64_t max_resident;  // streams in flight: 16 GiB of tables at the most
+    LazyParams lazy;        // Parser::kLazy only
+};
+constexpr EncoderRow encoder_row(Parser p, LazyParams lazy = {}) {
+    const uint64_t entries = p == Parser::kRle ? 0u : (p == Parser::kLazy ? 2 : 1) * 65536u + (p == Parser::kHashTable ? 0u : 32768u);
+    return {p, entries * 4, p == Parser::kHashTable ? 8u : 16u, entries ? (16ull << 30) / (entries * 4) : 1ull << 40, lazy};
+}
+constexpr EncoderRow kEncoders[] = {
+    encoder_row(Parser::kRle),                            // FDH_MODE_RLE
+    encoder_row(Parser::kHashTable),                      // level 1
+    encoder_row(Parser::kChain2),                         // level 2
+    encoder_row(Parser::kChain3),                         // level 3
+    encoder_row(Parser::kLazy, {9, 12, 5, 16, 32}),       // level 4
+    encoder_row(Parser::kLazy, {9, 16, 5, 64, 64}),       // level 5
+    encoder_row(Parser::kLazy, {9, 16, 4, 128, 128}),     // level 6
+    encoder_row(Parser::kLazy, {12, 256, 4, 256, 258}),   // levels 7, 8 and 9
+};
+static_assert(kEncoders[7].max_resident == 26214, "16 GiB / 640 KiB");
+// the row of a level, 1 .. 9, and of an FDH_MODE_*; nullptr for any other number
+inline const EncoderRow* encoder_of_level(uint32_t level) { return level >= 1 && level <= 9 ? &kEncoders[std::min(level, 7u)] : nullptr; }
+static_assert(FDH_MODE_LEVEL1 == 1 && FDH_MODE_RLE == 2 && FDH_MODE_LEVEL2 == 3 && FDH_MODE_LEVEL3 == 4, "kModeRows' order");
+constexpr unsigned kModeRows[] = {1, 0, 2, 3};
+inline const EncoderRow* encoder_of_mode(uint32_t mode) { return mode >= 1 && mode <= 4 ? &kEncoders[kModeRows[mode - 1]] : nullptr; }
+
+// The per-device state (the canonical tables' flags, the general encoder's workspaces) is kept in arrays of this many.
+constexpr int kMaxDevices = 64;
+inline bool device_ordinal_ok(int dev) { return dev >= 0 && dev < kMaxDevices; }
 
 // Wavefronts per range / threads per file in the kernels of png_file.hip and png_mixed.hip that serve one file per
 // workgroup: a batch that fills the device by its count alone gets one wavefront per item.

@@ -30,44 +30,38 @@ def test_library_exports_every_declared_symbol():
     assert L.fdh_ultrafast_bound(0) == 60 and L.fdh_ultrafast_bound(65536) == 98364
 
 
-def _declared_prototypes():
-    """{symbol: (result, [parameter, ...])} as the header spells them, comments and preprocessor lines taken out."""
-    text = open(os.path.join(ROOT, "include", "fdeflate_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    protos = {}
-    for result, name, params in re.findall(r"([^;{}]*?)\b(fdh_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos, name
-        params = [" ".join(p.split()) for p in params.split(",")]
-        protos[name] = (" ".join(result.split()), [] if params == ["void"] else params)
-    return protos
-
-
 def test_signature_table_agrees_with_the_header():
     """Parameter count, the class of every parameter and of the result, the element width of every device pointer and
-    the place of the stream: a miscounted table entry would be undefined behaviour at the call, not an error."""
+    the place of the stream (abi_header.check_table)."""
     from fdeflate_amd import _lib
-    protos = _declared_prototypes()
+    protos = abi_header.check_table(os.path.join(ROOT, "include", "fdeflate_hip.h"), _lib.SIGNATURES)
     assert set(protos) == set(_declared_symbols()) == set(_lib.SIGNATURES) and len(protos) == 65
     assert _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES)
-    for name, (result, params) in protos.items():
-        t_result, t_params = _lib.SIGNATURES[name]
-        if "*" in result:
-            assert t_result == ("str" if result == "const char *" else "host"), name
-        else:
-            assert t_result == ("void" if result == "void" else abi_header.SCALARS[result]), name
-        assert len(t_params) == len(params), name
-        for pos, (token, param) in enumerate(zip(t_params, params)):
-            where = "%s, parameter %d (%s)" % (name, pos, param)
-            pointee = abi_header.pointee(param)
-            if pointee is None:
-                assert token == abi_header.SCALARS[param.split()[0]], where
-            elif token in _lib.DEVICE_WIDTH:
-                assert param.count("*") == 1 and "[" not in param, where
-                assert _lib.DEVICE_WIDTH[token] == abi_header.POINTEE_BYTES[pointee], where
-            else:
-                assert token == ("stream" if param == "void *hip_stream" else "host"), where   # exempt from the widths
-        assert ("stream" in t_params) == (t_params[-1:] == ("stream",)) == (params[-1:] == ["void *hip_stream"]), name
+
+
+HEADERS = {"fdeflate_hip.h": ("SIGNATURES", 65), "fdeflate_hip_png16.h": ("EXTENSION_SIGNATURES", 3),
+           "fdeflate_hip_png16_encode.h": ("PNG16_ENCODE_SIGNATURES", 4), "fdeflate_hip_levels.h": ("LEVELS_SIGNATURES", 3),
+           "fdeflate_hip_png_levels.h": ("PNG_LEVELS_SIGNATURES", 3), "fdeflate_hip_pieces.h": ("PIECES_SIGNATURES", 5)}
+
+
+def test_tables_holds_every_header_of_include_with_its_named_table():
+    """_lib.TABLES is the six headers in the order they were added, each with the table the tests know by name; no symbol
+    is in two tables, and signature() finds every symbol in the table that owns it.  (One test, not one case per header:
+    it stands for the five per-header tests of the tables' arrangement that it replaced.)"""
+    from fdeflate_amd import _lib
+    assert list(_lib.TABLES) == list(HEADERS)
+    assert sorted(_lib.TABLES) == sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
+    names = [name for table in _lib.TABLES.values() for name in table]
+    assert len(names) == len(set(names)) == 83
+    assert _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES)
+    with pytest.raises(KeyError):
+        _lib.signature("fdh_debug_general_plan")                    # exported, but declared by no header
+    for header, (name, count) in HEADERS.items():
+        table = getattr(_lib, name)
+        assert _lib.TABLES[header] is table and len(table) == count, header
+        assert os.path.exists(os.path.join(ROOT, "include", header)), header
+        for symbol, entry in table.items():
+            assert _lib.signature(symbol) is entry, symbol
 
 
 def test_library_prototypes_are_set_from_the_table():

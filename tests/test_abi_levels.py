@@ -3,7 +3,6 @@ checks tests/test_abi_png16_encode.py makes of the second extension, the library
 device, and fdeflate_amd.levels as a module."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -15,19 +14,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fdeflate_hip_levels.h")
 SYMBOLS = ("fdh_deflate_level_batch", "fdh_compress_to_vec_level", "fdh_debug_level_plan")
 NAMES = ("LEVELS_PROVIDED", "compress_to_vec_with_level", "deflate_level_batch", "level_plan")
-
-
-def _declared_prototypes():
-    """{symbol: (result, [parameter, ...])} as the header spells them (test_abi_png16_encode._declared_prototypes on it)."""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    protos = {}
-    for result, name, params in re.findall(r"([^;{}]*?)\b(fdh_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos, name
-        params = [" ".join(p.split()) for p in params.split(",")]
-        protos[name] = (" ".join(result.split()).replace('extern "C"', "").strip(), [] if params == ["void"] else params)
-    return protos
 
 
 def test_header_includes_the_main_header_and_carries_the_contract():
@@ -44,41 +30,10 @@ def test_table_agrees_with_the_header():
     the place of the stream.  The batch call has fdh_deflate_general_batch's prototype, the one-shot
     fdh_compress_to_vec_with_level's."""
     from fdeflate_amd import _lib
-    protos = _declared_prototypes()
-    assert set(protos) == set(_lib.LEVELS_SIGNATURES) == set(SYMBOLS)
-    for name, (result, params) in protos.items():
-        t_result, t_params = _lib.LEVELS_SIGNATURES[name]
-        assert "*" not in result and t_result == abi_header.SCALARS[result], name
-        assert len(t_params) == len(params), name
-        for pos, (token, param) in enumerate(zip(t_params, params)):
-            where = "%s, parameter %d (%s)" % (name, pos, param)
-            pointee = abi_header.pointee(param)
-            if pointee is None:
-                assert token == abi_header.SCALARS[param.split()[0]], where
-            elif token in _lib.DEVICE_WIDTH:
-                assert param.count("*") == 1 and "[" not in param, where
-                assert _lib.DEVICE_WIDTH[token] == abi_header.POINTEE_BYTES[pointee], where
-            else:
-                assert token == ("stream" if param == "void *hip_stream" else "host"), where
-        assert ("stream" in t_params) == (t_params[-1:] == ("stream",)) == (params[-1:] == ["void *hip_stream"]), name
+    protos = abi_header.check_table(HEADER, _lib.LEVELS_SIGNATURES)
+    assert set(protos) == set(SYMBOLS) and all(result in abi_header.SCALARS for result, _ in protos.values())
     assert _lib.LEVELS_SIGNATURES["fdh_deflate_level_batch"] == _lib.SIGNATURES["fdh_deflate_general_batch"]
     assert _lib.LEVELS_SIGNATURES["fdh_compress_to_vec_level"] == _lib.SIGNATURES["fdh_compress_to_vec_with_level"]
-
-
-def test_the_table_stands_beside_the_pinned_ones_which_are_what_they_were():
-    from fdeflate_amd import _lib
-    assert list(_lib.TABLES) == ["fdeflate_hip.h", "fdeflate_hip_png16.h", "fdeflate_hip_png16_encode.h"]
-    assert all(_lib.LEVELS_SIGNATURES is not t for t in _lib.TABLES.values())
-    assert len(_lib.SIGNATURES) == 65 and len(_lib.EXTENSION_SIGNATURES) == 3 and len(_lib.PNG16_ENCODE_SIGNATURES) == 4
-    assert _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES)
-    for table in _lib.TABLES.values():
-        assert not set(table) & set(_lib.LEVELS_SIGNATURES)
-    for name in SYMBOLS:
-        assert _lib.signature(name) == _lib.LEVELS_SIGNATURES[name]
-    assert _lib.signature("fdh_deflate_general_batch") == _lib.SIGNATURES["fdh_deflate_general_batch"]
-    assert _lib.signature("fdh_png_pack16_mixed_batch") == _lib.PNG16_ENCODE_SIGNATURES["fdh_png_pack16_mixed_batch"]
-    with pytest.raises(KeyError):
-        _lib.signature("fdh_debug_general_plan")
 
 
 def test_library_exports_every_declared_symbol_with_its_prototype():

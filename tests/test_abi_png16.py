@@ -2,7 +2,6 @@
 checks tests/test_abi.py makes of the main header, the library's exports, and fdeflate_amd.png16 as a module."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -11,19 +10,6 @@ import abi_header
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "fdeflate_hip_png16.h")
 SYMBOLS = ("fdh_png_expand16_batch", "fdh_png_expand16_mixed_batch", "fdh_png_pack16_batch")
-
-
-def _declared_prototypes():
-    """{symbol: (result, [parameter, ...])} as the extension header spells them (test_abi._declared_prototypes on it)."""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    protos = {}
-    for result, name, params in re.findall(r"([^;{}]*?)\b(fdh_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos, name
-        params = [" ".join(p.split()) for p in params.split(",")]
-        protos[name] = (" ".join(result.split()).replace('extern "C"', "").strip(), [] if params == ["void"] else params)
-    return protos
 
 
 def test_extension_header_includes_the_main_one():
@@ -35,32 +21,8 @@ def test_extension_table_agrees_with_the_header():
     """Parameter count, the class of every parameter and of the result, the element width of every device pointer and
     the place of the stream, as test_abi.test_signature_table_agrees_with_the_header checks them."""
     from fdeflate_amd import _lib
-    protos = _declared_prototypes()
-    assert set(protos) == set(_lib.EXTENSION_SIGNATURES) == set(SYMBOLS)
-    for name, (result, params) in protos.items():
-        t_result, t_params = _lib.EXTENSION_SIGNATURES[name]
-        assert "*" not in result and t_result == abi_header.SCALARS[result], name
-        assert len(t_params) == len(params), name
-        for pos, (token, param) in enumerate(zip(t_params, params)):
-            where = "%s, parameter %d (%s)" % (name, pos, param)
-            pointee = abi_header.pointee(param)
-            if pointee is None:
-                assert token == abi_header.SCALARS[param.split()[0]], where
-            elif token in _lib.DEVICE_WIDTH:
-                assert param.count("*") == 1 and "[" not in param, where
-                assert _lib.DEVICE_WIDTH[token] == abi_header.POINTEE_BYTES[pointee], where
-            else:
-                assert token == ("stream" if param == "void *hip_stream" else "host"), where
-        assert ("stream" in t_params) == (t_params[-1:] == ("stream",)) == (params[-1:] == ["void *hip_stream"]), name
-
-
-def test_no_symbol_is_in_both_tables_and_the_main_table_is_what_it_was():
-    from fdeflate_amd import _lib
-    assert not set(_lib.SIGNATURES) & set(_lib.EXTENSION_SIGNATURES)
-    assert _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES) and len(_lib.SIGNATURES) == 65
-    for name in SYMBOLS:
-        assert _lib.signature(name) == _lib.EXTENSION_SIGNATURES[name]
-    assert _lib.signature("fdh_png_expand_batch") == _lib.SIGNATURES["fdh_png_expand_batch"]
+    protos = abi_header.check_table(HEADER, _lib.EXTENSION_SIGNATURES)
+    assert set(protos) == set(SYMBOLS) and all(result in abi_header.SCALARS for result, _ in protos.values())
 
 
 def test_library_exports_every_declared_symbol_with_its_prototype():

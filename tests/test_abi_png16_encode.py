@@ -3,7 +3,6 @@ _lib.PNG16_ENCODE_SIGNATURES with the checks tests/test_abi_png16.py makes of th
 and fdeflate_amd.png16_encode as a module."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -14,19 +13,6 @@ HEADER = os.path.join(ROOT, "include", "fdeflate_hip_png16_encode.h")
 SYMBOLS = ("fdh_png_analyse16_mixed_batch", "fdh_png_encode16_plan_one", "fdh_png_encode16_plan_batch", "fdh_png_pack16_mixed_batch")
 NAMES = ("png_analyse16_mixed_batch", "png_encode16_plan_one", "png_encode16_plan_batch", "png_pack16_mixed_batch",
          "png_encode_mixed_rgba16_files_batch")
-
-
-def _declared_prototypes():
-    """{symbol: (result, [parameter, ...])} as the header spells them (test_abi_png16._declared_prototypes on it)."""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    protos = {}
-    for result, name, params in re.findall(r"([^;{}]*?)\b(fdh_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos, name
-        params = [" ".join(p.split()) for p in params.split(",")]
-        protos[name] = (" ".join(result.split()).replace('extern "C"', "").strip(), [] if params == ["void"] else params)
-    return protos
 
 
 def test_header_includes_the_first_extension_and_carries_the_contract():
@@ -42,44 +28,11 @@ def test_table_agrees_with_the_header():
     """Parameter count, the class of every parameter and of the result, the element width of every device pointer and
     the place of the stream, as test_abi_png16.test_extension_table_agrees_with_the_header checks them."""
     from fdeflate_amd import _lib
-    protos = _declared_prototypes()
-    assert set(protos) == set(_lib.PNG16_ENCODE_SIGNATURES) == set(SYMBOLS)
-    for name, (result, params) in protos.items():
-        t_result, t_params = _lib.PNG16_ENCODE_SIGNATURES[name]
-        assert "*" not in result and t_result == abi_header.SCALARS[result], name
-        assert len(t_params) == len(params), name
-        for pos, (token, param) in enumerate(zip(t_params, params)):
-            where = "%s, parameter %d (%s)" % (name, pos, param)
-            pointee = abi_header.pointee(param)
-            if pointee is None:
-                assert token == abi_header.SCALARS[param.split()[0]], where
-            elif token in _lib.DEVICE_WIDTH:
-                assert param.count("*") == 1 and "[" not in param, where
-                assert _lib.DEVICE_WIDTH[token] == abi_header.POINTEE_BYTES[pointee], where
-            else:
-                assert token == ("stream" if param == "void *hip_stream" else "host"), where
-        assert ("stream" in t_params) == (t_params[-1:] == ("stream",)) == (params[-1:] == ["void *hip_stream"]), name
+    protos = abi_header.check_table(HEADER, _lib.PNG16_ENCODE_SIGNATURES)
+    assert set(protos) == set(SYMBOLS) and all(result in abi_header.SCALARS for result, _ in protos.values())
     # the two plans have the prototypes of the RGBA8 plans
     assert _lib.PNG16_ENCODE_SIGNATURES["fdh_png_encode16_plan_one"] == _lib.SIGNATURES["fdh_png_encode_plan_one"]
     assert _lib.PNG16_ENCODE_SIGNATURES["fdh_png_encode16_plan_batch"] == _lib.SIGNATURES["fdh_png_encode_plan_batch"]
-
-
-def test_no_symbol_is_in_two_tables_and_the_other_tables_are_what_they_were():
-    from fdeflate_amd import _lib
-    assert list(_lib.TABLES) == ["fdeflate_hip.h", "fdeflate_hip_png16.h", "fdeflate_hip_png16_encode.h"]
-    assert _lib.TABLES["fdeflate_hip.h"] is _lib.SIGNATURES and _lib.TABLES["fdeflate_hip_png16.h"] is _lib.EXTENSION_SIGNATURES
-    assert _lib.TABLES["fdeflate_hip_png16_encode.h"] is _lib.PNG16_ENCODE_SIGNATURES
-    for header in _lib.TABLES:
-        assert os.path.exists(os.path.join(ROOT, "include", header)), header
-    tables = list(_lib.TABLES.values())
-    for k, a in enumerate(tables):
-        for b in tables[k + 1:]:
-            assert not set(a) & set(b)
-    assert len(_lib.SIGNATURES) == 65 and len(_lib.EXTENSION_SIGNATURES) == 3 and _lib.EXPORTED_SYMBOLS == list(_lib.SIGNATURES)
-    for name in SYMBOLS:
-        assert _lib.signature(name) == _lib.PNG16_ENCODE_SIGNATURES[name]
-    assert _lib.signature("fdh_png_expand_batch") == _lib.SIGNATURES["fdh_png_expand_batch"]
-    assert _lib.signature("fdh_png_pack16_batch") == _lib.EXTENSION_SIGNATURES["fdh_png_pack16_batch"]
 
 
 def test_library_exports_every_declared_symbol_with_its_prototype():

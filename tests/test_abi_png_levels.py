@@ -19,19 +19,6 @@ NAMES = ("PNG_FILTER_GIVEN_TYPES", "level_bound", "level_file_bound", "png_filte
 LENGTHS = (0, 1, 65535, 65536, 1 << 30)
 
 
-def _declared_prototypes():
-    """{symbol: (result, [parameter, ...])} as the header spells them."""
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)
-    protos = {}
-    for result, name, params in re.findall(r"([^;{}]*?)\b(fdh_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos, name
-        params = [" ".join(p.split()) for p in params.split(",")]
-        protos[name] = (" ".join(result.split()).replace('extern "C"', "").strip(), [] if params == ["void"] else params)
-    return protos
-
-
 def test_header_includes_the_headers_it_extends_and_carries_the_contract():
     text = open(HEADER).read()
     assert '#include "fdeflate_hip.h"' in text and '#include "fdeflate_hip_levels.h"' in text and "#ifndef FDEFLATE_HIP_PNG_LEVELS_H" in text
@@ -44,38 +31,11 @@ def test_header_includes_the_headers_it_extends_and_carries_the_contract():
 
 def test_table_agrees_with_the_header():
     from fdeflate_amd import _lib
-    protos = _declared_prototypes()
-    assert set(protos) == set(_lib.PNG_LEVELS_SIGNATURES) == set(SYMBOLS)
-    for name, (result, params) in protos.items():
-        t_result, t_params = _lib.PNG_LEVELS_SIGNATURES[name]
-        assert "*" not in result and t_result == abi_header.SCALARS[result], name
-        assert len(t_params) == len(params), name
-        for pos, (token, param) in enumerate(zip(t_params, params)):
-            where = "%s, parameter %d (%s)" % (name, pos, param)
-            pointee = abi_header.pointee(param)
-            if pointee is None:
-                assert token == abi_header.SCALARS[param.split()[0]], where
-            elif token in _lib.DEVICE_WIDTH:
-                assert param.count("*") == 1 and "[" not in param, where
-                assert _lib.DEVICE_WIDTH[token] == abi_header.POINTEE_BYTES[pointee], where
-            else:
-                assert token == ("stream" if param == "void *hip_stream" else "host"), where
-        assert ("stream" in t_params) == (t_params[-1:] == ("stream",)) == (params[-1:] == ["void *hip_stream"]), name
+    protos = abi_header.check_table(HEADER, _lib.PNG_LEVELS_SIGNATURES)
+    assert set(protos) == set(SYMBOLS) and all(result in abi_header.SCALARS for result, _ in protos.values())
     # the filter call is fdh_png_filter_batch's slots with the record, the gate and the flags where that has row_bytes and bpp
     mixed, uniform = _lib.PNG_LEVELS_SIGNATURES["fdh_png_filter_mixed_batch"][1], _lib.SIGNATURES["fdh_png_filter_batch"][1]
     assert mixed[:6] == uniform[:6] and mixed[6:] == ("4", "4", "u32", "4", "u64", "stream")
-
-
-def test_the_table_stands_beside_the_pinned_ones_which_are_what_they_were():
-    from fdeflate_amd import _lib
-    assert list(_lib.TABLES) == ["fdeflate_hip.h", "fdeflate_hip_png16.h", "fdeflate_hip_png16_encode.h"]
-    assert all(_lib.PNG_LEVELS_SIGNATURES is not t for t in _lib.TABLES.values())
-    assert len(_lib.SIGNATURES) == 65 and len(_lib.LEVELS_SIGNATURES) == 3 and len(_lib.PNG_LEVELS_SIGNATURES) == 3
-    for table in (*_lib.TABLES.values(), _lib.LEVELS_SIGNATURES):
-        assert not set(table) & set(_lib.PNG_LEVELS_SIGNATURES)
-    for name in SYMBOLS:
-        assert _lib.signature(name) == _lib.PNG_LEVELS_SIGNATURES[name]
-    assert _lib.signature("fdh_deflate_level_batch") == _lib.LEVELS_SIGNATURES["fdh_deflate_level_batch"]
 
 
 def test_library_exports_every_declared_symbol_with_its_prototype():

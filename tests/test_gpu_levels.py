@@ -82,11 +82,11 @@ def test_levels_2_and_3_bit_exact(harness, cases, launch, monkeypatch):
             assert np.all(h[out_off[i] + int(ln[i]):out_off[i + 1]] == 0x5A), (launch, level, i)
 
 
-def _c_compress_with_level(data, level):
+def _c_compress_with_level(data, level, symbol="fdh_compress_to_vec_with_level"):
     from fdeflate_amd import _lib
     L = _lib.lib()
     out, n = C.c_void_p(), C.c_size_t()
-    rc = L.fdh_compress_to_vec_with_level(data, len(data), level, C.byref(out), C.byref(n))
+    rc = getattr(L, symbol)(data, len(data), level, C.byref(out), C.byref(n))
     if rc != 0:
         return rc, None
     try:
@@ -131,6 +131,46 @@ def test_unknown_modes_are_still_refused(harness):
     for mode in (0, 5, 99):
         with pytest.raises(FdeflateHipError):
             fd.deflate_general_batch(d_in, off, d_out, o_off, mode)
+
+
+@pytest.mark.parametrize("level", range(10))
+def test_every_door_to_a_level_gives_the_same_bytes(harness, level, monkeypatch):
+    """Inputs of 0, 1, 300 and 70 000 bytes (the last longer than the 32 KiB window), one batch per door, the streams
+    compared whole: fdh_deflate_level_batch, fdh_compress_to_vec_level and deflate_level_pieces_batch with one piece per
+    input at every level; at levels 0 .. 3 also fdh_compress_to_vec_with_level and the batch call that level had before
+    (fdh_deflate_stored_batch, fdh_deflate_general_batch in the level's mode)."""
+    import torch
+    import fdeflate_amd as fd
+    from fdeflate_amd import levels, pieces
+    monkeypatch.delenv("FDH_GEN_LANES", raising=False)
+    monkeypatch.delenv("FDH_GEN_RESIDENT", raising=False)
+    raws = [streams._vol_text(streams.rng(5 + n), n) for n in (0, 1, 300, 70000)]
+    assert [len(x) for x in raws] == [0, 1, 300, 70000]
+    one_piece = 1 << 17
+    buf, in_off = streams.pack_exact(raws)
+    out_off = np.zeros(len(raws) + 1, dtype=np.int64)
+    out_off[1:] = np.cumsum([max(fd.stored_size(len(x)), pieces.pieces_bound(len(x), level, one_piece)) for x in raws])
+    d_in, d_in_off, d_out_off = torch.from_numpy(buf).cuda(), torch.from_numpy(in_off.astype(np.int64)).cuda(), torch.from_numpy(out_off).cuda()
+
+    def batch(door):
+        out = torch.full((int(out_off[-1]),), 0x5A, dtype=torch.uint8, device="cuda")
+        ln = door(d_in, d_in_off, out, d_out_off).cpu().numpy().view(np.uint32)
+        h = out.cpu().numpy()
+        return [h[out_off[i]:out_off[i] + int(ln[i])].tobytes() for i in range(len(raws))]
+
+    doors = {"level_batch": batch(lambda a, b, c, d: levels.deflate_level_batch(a, b, c, d, level)),
+             "one piece each": batch(lambda a, b, c, d: pieces.deflate_level_pieces_batch(a, b, c, d, level, one_piece)),
+             "to_vec_level": [_c_compress_with_level(x, level, "fdh_compress_to_vec_level")[1] for x in raws]}
+    if level <= 3:
+        modes = (None, fd.MODE_LEVEL1, fd.MODE_LEVEL2, fd.MODE_LEVEL3)
+        doors["to_vec_with_level"] = [_c_compress_with_level(x, level)[1] for x in raws]
+        doors["the level's own batch call"] = batch(fd.deflate_stored_batch if level == 0 else
+                                                    lambda a, b, c, d: fd.deflate_general_batch(a, b, c, d, modes[level]))
+    want = doors["level_batch"]
+    assert all(len(w) >= 8 for w in want) and (level == 0 or want[0] == EMPTY)
+    assert level == 0 or len(want[3]) < 35000           # compressed: the doors do not agree on a stored stream
+    for name, got in doors.items():
+        assert got == want, (level, name, [None if g is None else len(g) for g in got], [len(w) for w in want])
 
 
 @pytest.mark.parametrize("lanes", [None, "1", "64"])
