@@ -4,7 +4,8 @@ General encoder (level 1 / RLE) and the PNG kernels against the oracle on random
 contents, with guard bytes; several images per wavefront for the PNG pipeline; zlib / ultra-fast streams whole,
 cut and damaged; cut streams' partial lengths; the resumable batch (FDH_SOAK_ONLY=resume: the last two only; =enc: the general
 encoder only); the streaming object
-at the reference's footprint (FDH_SOAK_ONLY=stream)."""
+at the reference's footprint (FDH_SOAK_ONLY=stream); random streams of tests/deflate_gen.py, which neither zlib nor the
+encoders write (FDH_SOAK_ONLY=foreign)."""
 import os, sys, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -355,6 +356,33 @@ def stream_round(seed):
             assert bytes(got[:m]) == pout[:m] and len(got) + 2 * window + 600 >= len(pout), (seed, k, len(got), len(pout), window)
 
 
+def foreign_round(seed):
+    """Random deflate_gen streams of both kinds -- random complete codes up to 15 bits, blocks of every type, matches of
+    every length and distance; random runs of every byte cut under a random policy behind the ultra-fast prefix --
+    checked three ways on the CPU, then through the whole pipeline and each kernel alone: what is reported is the
+    oracle's status, length, bytes and Adler-32, the guards stay, and only a single-kernel run may leave a stream."""
+    import deflate_gen, gpu_harness
+    r = np.random.default_rng(seed)
+    comps, raws, kinds = [], [], []
+    for k in range(48):
+        uf = k % 2 == 0
+        c, a = deflate_gen.random_uf(r) if uf else deflate_gen.random_general(r)
+        est, eout, ead = ob.decompress_bounded(c, len(a))
+        assert zlib.decompress(c) == a and est == 0 and eout == a and ead == zlib.adler32(a), (seed, k, "the references disagree")
+        comps.append(c); raws.append(a); kinds.append(uf)
+    caps = [len(a) + int(r.choice([0, 0, 16, 100])) for a in raws]
+    gpu_harness.assert_inflate_parity(["s%d_%d" % (seed, k) for k in range(len(comps))], comps, caps)
+    only_uf = (fd.api.FLAG_LANDING_ONLY, fd.api.FLAG_LANDING_ONLY | fd.api.FLAG_NO_LEAN_WRITE, fd.api.FLAG_INTERVALS_ONLY,
+               fd.api.FLAG_NO_INTERVALS | fd.api.FLAG_FIRST_ONLY, fd.api.FLAG_FIRST_ONLY)
+    for flags in only_uf + (0x2000,):
+        st, ln, ad, outs, ok = gpu_harness.gpu_inflate(comps, caps, flags)
+        assert ok, (seed, flags, "guard")
+        for i, a in enumerate(raws):
+            if int(st[i]) >= 0xFFFFFFFD:
+                continue  # left to the kernels behind it (not run here)
+            assert int(st[i]) == 0 and int(ln[i]) == len(a) and outs[i][:len(a)].tobytes() == a and int(ad[i]) == zlib.adler32(a), (seed, flags, i)
+
+
 ONLY = os.environ.get("FDH_SOAK_ONLY", "")
 for s in range(int(sys.argv[1]), int(sys.argv[2])):
     if ONLY == "stream":
@@ -367,6 +395,10 @@ for s in range(int(sys.argv[1]), int(sys.argv[2])):
         continue
     if ONLY == "enc":  # the general encoder alone (new seeds: the default rounds use 1000 + s)
         enc_round(9000 + s)
+        print("seed", s, "ok", flush=True)
+        continue
+    if ONLY == "foreign":
+        foreign_round(13000 + s)
         print("seed", s, "ok", flush=True)
         continue
     if ONLY == "resume":
